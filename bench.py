@@ -11,7 +11,11 @@ steps of configs[3] / configs[4] instead (same JSON contract; `config.workload` 
 N > 1: launched by the driver through torch.distributed.run, one rank per GPU, DDP over RCCL (gradient all-reduce of
 the MLP parameters; the hot-path kernels themselves exchange nothing: images shard over the batch) -> weak scaling.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with these extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the K steps, writes the last
+step's outputs if `--dump-outputs DIR` is given, and prints the line.  `--full` adds these extra objects (each measured in runs of its
+own after the timed steps; `--no-*` switches leave single ones out):
+  extra_legs   -- N > 1: every rank on its own poses and the Fauna per-rank step; 1 GPU magicpony: the trained-like (spiky) mesh;
+  rank_diagnostics -- N > 1: per-rank blocking synchronisations and GPU-busy time per step;
   roofline     -- the dominant IN-SCOPE entry point of the hot path (DMTet, skinning, normals, topology,
                   rasterise, covered pixels, G-buffer, shading, antialias): algorithmic bytes per launch / mean launch duration measured
                   live with HIP events on the launch stream, against the 8 TB/s HBM peak; `in_scope` = the bytes-weighted aggregate
@@ -19,7 +23,17 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with these extra
                   = the kernels that serve model/networks (out of scope, reported for completeness);
   parity       -- the step the CPU oracle re-runs for `cpu_baseline` compared with the HIP step it was snapshotted from;
   dropin       -- the same step with the networks evaluated exactly as the reference's model/networks does (--networks reference);
-  cpu_baseline -- the CPU oracle (kind "port") timed on this box's host cores on a bounded sample of the batch.
+  cpu_baseline -- the CPU oracle (kind "port") timed on this box's host cores on a bounded sample of the batch;
+  attribution, box, host_syncs, config1_geometry, kernels -- launch attribution, box fingerprint, blocking synchronisations of one
+                  step, BASELINE configs[1] beside the CPU oracle, the per-entry-point event times behind the roofline.
+
+`--dump-outputs DIR`: what the timed path handed its caller in the last timed step (the step's output dict: images, losses, ...) as
+DIR/<name>.npy, float32 (float64 stays float64); an array of more than DUMP_SAMPLE elements is stored as a fixed, seeded sample of
+them (the same indices in every run of the same arguments), so that two builds can be compared output for output.  The inputs are
+seeded, and by default every warm-up and timed step of the headline starts from the scene's initial weights and optimiser state
+(from_initial_state), so that two runs of the same arguments differ by rounding only (profiles/r07_dump_reproducibility.json).
+`--carry-state` times the training trajectory instead (weights and Adam state carried over, the mesh drifting): what the committed
+lines and profiles measure (tools/run_bench_lines.sh, tools/prof_bench.sh, tools/pmc_*.sh); its dumps differ from run to run.
 """
 import argparse
 import contextlib
@@ -508,11 +522,84 @@ def dry_launch(args, rank, world):
     return 0
 
 
+def from_initial_state(scene, step_fn):
+    """-> a step function whose every call starts from the state ``scene`` has now: its weights (copied back in place, so that captured
+    HIP graphs keep their pointers) and its optimiser state as the first call creates it (Adam creates every entry -- step, moments --
+    as zeros).  The backward's float atomics round differently from run to run; carried from step to step, Adam and the DMTet level
+    set amplify that into other meshes, covered pixels and images (profiles/r07_dump_reproducibility.json).  Started from the same
+    state, consecutive steps still differ -- the grid jitter (and Fauna's random-view azimuths) are drawn from the global generator on
+    every call -- but the n-th step of one run and the n-th step of another do the same work on the same inputs.  The restore runs
+    inside the timed interval: 21-23 us per step on an MI355X (one foreach copy of 6.8 MB of weights, one foreach zero of the Adam state),
+    0.15 % of a 15.5 ms step (profiles/r07_dump_reproducibility.json)."""
+    params = [p for p in scene.parameters()]
+    initial = [p.detach().clone() for p in params]
+    state = []
+
+    def run():
+        if state:
+            with torch.no_grad():
+                torch._foreach_copy_(params, initial)
+                for group in state:
+                    torch._foreach_zero_(group)
+        out = step_fn()
+        if not state:  # the first call created the optimiser state: zeroed before every later call
+            by_device = {}
+            for s in scene.optimizer.state.values():
+                for t in s.values():
+                    if torch.is_tensor(t):
+                        by_device.setdefault(t.device, []).append(t)
+            state.extend(by_device.values())
+        return out
+
+    return run
+
+
+DUMP_SAMPLE = 1 << 21  # elements kept of a larger output (8 MB in float32); a step hands back at most four such arrays
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out, dirname):
+    """--dump-outputs: every tensor of a step's output dict (nested dicts flattened as <key>_<name>) -> DIR/<name>.npy.  Returns
+    {name: {shape, sampled}} for the result line."""
+    import numpy as np
+
+    flat = {}
+    for k, v in out.items():
+        for kk, vv in (v.items() if isinstance(v, dict) else [(None, v)]):
+            if torch.is_tensor(vv):
+                flat[k if kk is None else f"{k}_{kk}"] = vv.detach()
+    os.makedirs(dirname, exist_ok=True)
+    written, total = {}, 0
+    for name, t in sorted(flat.items()):
+        values = t.reshape(-1)
+        sampled = values.numel() > DUMP_SAMPLE
+        if sampled:  # fixed, seeded indices: the same elements in every run of the same shape
+            idx = torch.randint(values.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+            values = values[idx.to(values.device)]
+        arr = values.cpu().numpy().astype(np.float64 if t.dtype == torch.float64 else np.float32, copy=False)
+        if not sampled:
+            arr = arr.reshape(tuple(t.shape))
+        total += arr.nbytes
+        if total > DUMP_BUDGET_BYTES:
+            raise RuntimeError(f"--dump-outputs: more than {DUMP_BUDGET_BYTES >> 20} MB at '{name}'")
+        np.save(os.path.join(dirname, name + ".npy"), arr)
+        written[name] = dict(shape=list(t.shape), sampled=DUMP_SAMPLE if sampled else None)
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure everything beside the headline: extra legs, "
+                    "rank diagnostics, per-kernel roofline, launch attribution, box fingerprint, host synchronisations, CPU-oracle parity and "
+                    "baseline, drop-in networks, BASELINE configs[1] (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned as DIR/<name>.npy")
+    ap.add_argument("--carry-state", action="store_true", help="time the training trajectory: weights and Adam state carried from step to "
+                    "step (the mesh drifts as the synthetic training goes on; what the committed lines and profiles measure).  Two runs "
+                    "of the same arguments then diverge beyond rounding (the backward's float atomics, amplified from step to step).  "
+                    "Default: every warm-up and timed step starts from the initial state (from_initial_state)")
     ap.add_argument("--batch", type=int, default=None, help="images (sequences for ponymation) per GPU; default 16 (8 sequences)")
     ap.add_argument("--frames", type=int, default=8, help="frames per sequence (ponymation only)")
     ap.add_argument("--grid-res", type=int, default=64)
@@ -523,7 +610,7 @@ def main():
     ap.add_argument("--networks", choices=("fast", "reference", "both"), default="both",
                     help="fast: the output-identical field evaluation of hostnets (headline); reference: model/networks' own formulation "
                          "(per-point feature concat, per-call frequency upload, no TunableOp, no fused kernels); both: headline = fast, and "
-                         "the reference formulation is measured too (single GPU only) and reported under 'dropin'")
+                         "with --full the reference formulation is measured too (single GPU only) and reported under 'dropin'")
     ap.add_argument("--seed", type=int, default=0, help="seed of the synthetic scene's networks, cameras and poses (0: every committed line but the "
                     "long Fauna run, whose random trajectory empties a leg quadrant at seed 0: estimate_bones then raises where the "
                     "reference drops into pdb, skinning.py:183)")
@@ -557,6 +644,8 @@ def main():
                     "Fauna per-rank step) that follow the headline leg")
     args = ap.parse_args()
     assert not args.no_render or args.workload == "ponymation", "--no-render is the ponymation stage-2 configuration"
+    assert args.steps >= 1 and args.warmup >= 0, "--steps >= 1, --warmup >= 0"
+    full = args.full
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:  # plain `python bench.py --gpus N`: spawn the ranks ourselves
         sys.exit(self_launch(args.gpus))
@@ -601,7 +690,7 @@ def main():
     # where eight Python processes stalling at different moments would show; Trainer.py:170-179,304-308, Fauna.py:111-173).  Their
     # scenes (and HIP graphs) exist before the process group does, like the headline's.
     extra_scenes = {}
-    if world > 1 and not args.no_extra_legs and not args.forward_only:
+    if full and world > 1 and not args.no_extra_legs and not args.forward_only:
         if not args.per_rank_poses:
             extra_scenes["per_rank_poses"] = make_scene(per_rank_poses=True)
         if args.workload != "fauna":
@@ -626,8 +715,22 @@ def main():
     # W untimed warm-up steps, then exactly K steps bracketed by barrier + synchronize on both sides, MAX over ranks
     du = importlib.import_module("3danimals_amd.dist_util")
     tdev = dev if (world == 1 or args.backend == "nccl") else "cpu"
-    elapsed, rank_seconds = du.timed_steps(lambda: scene.step(module=module, backward=train), args.steps, args.warmup, device=dev, per_rank=True)
+    calls, last_out = [0], {}
+    train_step = lambda: scene.step(module=module, backward=train)
+    same_step = train_step if args.carry_state else from_initial_state(scene, train_step)
+
+    def headline_step():
+        out = same_step()
+        calls[0] += 1
+        if args.dump_outputs and calls[0] == args.warmup + args.steps:  # the last timed step: what its caller receives
+            last_out.update(out)
+
+    elapsed, rank_seconds = du.timed_steps(headline_step, args.steps, args.warmup, device=dev, per_rank=True)
     images = world * scene.frames * args.steps
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dict(dir=args.dump_outputs, arrays=dump_outputs(last_out, args.dump_outputs))
+    last_out.clear()
 
     def covered_of(sc):
         c = int((sc.last["rast"][..., 3] > 0).sum()) if "rast" in sc.last else 0
@@ -652,7 +755,7 @@ def main():
     # issuing ~600 launches per step and stalling at their own read-backs.  Every rank: blocking synchronisations in one step (torch's
     # sync-debug hook) and the GPU time of ITS OWN kernels over two steps against their wall time; gathered, so that the line shows them.
     rank_diag = None
-    if world > 1 and not args.no_rank_diagnostics:
+    if full and world > 1 and not args.no_rank_diagnostics:
         import warnings
 
         from torch.profiler import ProfilerActivity, profile
@@ -695,14 +798,14 @@ def main():
 
     # ---- per-kernel timing pass (same workload, separate from the headline timing so the events do not perturb it)
     roofline, kernels = None, {}
-    if rank == 0 and not args.no_kernel_timing:
+    if full and rank == 0 and not args.no_kernel_timing:
         kernels, dims = kernel_pass(scene, module, L, min(args.steps, 10), world, dims_of, train)
         roofline = roofline_of(kernels, dims, workload_signature(args, batch))
 
     # ---- the trained-like mesh as an extra leg of the default line: the 25-step-old near-ellipsoid is the cheapest mesh
     # this path will ever see; the reference trains for 1e5 iterations (config/model/magicpony.yaml:31-33).  Same step, same networks, the
     # spiky mesh: images/s, in-scope time, and the two calls whose cost follows depth complexity and silhouette length.
-    if (rank == 0 and world == 1 and train and args.workload == "magicpony" and args.mesh == "quadruped" and not args.no_spiky_leg
+    if (full and rank == 0 and world == 1 and train and args.workload == "magicpony" and args.mesh == "quadruped" and not args.no_spiky_leg
             and not args.no_kernel_timing):
         sp = make_scene(mesh="spiky")
         sp_steps = max(5, min(args.steps, 20))
@@ -725,7 +828,7 @@ def main():
     # ---- who launched what (round 6): in_scope_us_per_step above sums the C-ABI entry points only; the torch kernels the path's own
     # modules launch (copies, slices and their padded gradients, accumulations) belong to the path too.  torch.profiler, 3 steps.
     attribution = None
-    if rank == 0 and world == 1 and not args.no_attribution and not args.no_kernel_timing:
+    if full and rank == 0 and world == 1 and not args.no_attribution and not args.no_kernel_timing:
         try:
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             import glue_attribution
@@ -735,12 +838,12 @@ def main():
             attribution = dict(error=f"{type(e).__name__}: {str(e)[:200]}")
 
     fingerprint = None
-    if rank == 0 and not args.no_fingerprint:
+    if full and rank == 0 and not args.no_fingerprint:
         fingerprint = box_fingerprint(L, dev, (lambda: scene.step(module=module, backward=train)) if world == 1 else None, elapsed / args.steps * 1e3)
 
     # ---- blocking host <-> device synchronisations inside one steady-state step (torch's sync-debug hook; sizes that shapes depend on)
     host_syncs = None
-    if rank == 0 and world == 1:
+    if full and rank == 0 and world == 1:
         import warnings
 
         torch.cuda.synchronize()
@@ -757,13 +860,13 @@ def main():
 
     threads = min(os.cpu_count(), 32)  # torch-CPU stops scaling (and thrashes) far below the 256 logical cores of the GPU box
     parity = cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         parity, cpu_baseline = parity_and_cpu_baseline(scene, args, threads)
 
     # ---- the drop-in figure: the same step with model/networks evaluated the reference's own way (what a maintainer gets who
     # overlays only model/geometry + model/render).  Single GPU only; a fresh scene, since Adam state is per formulation.
     dropin = None
-    if rank == 0 and world == 1 and args.networks == "both":
+    if full and rank == 0 and world == 1 and args.networks == "both":
         hostnets.reference_formulation(True)
         tunable_was = torch.cuda.tunable.is_enabled()
         torch.cuda.tunable.enable(False)
@@ -778,7 +881,7 @@ def main():
         del ref_scene
 
     config1 = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "magicpony":
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "magicpony":
         # BASELINE config 1 (geometry only, no raster): CPU oracle beside the HIP path on the same inputs
         from oracle import geometry_ref
 
@@ -836,6 +939,9 @@ def main():
             "vs_baseline": None,
             "dtype": "f32",
             "data": "synthetic",
+            "full": full,  # False: the objects below that --full measures are null
+            "carry_state": bool(args.carry_state),  # True: a training trajectory; False: every step from the initial state
+            "dump_outputs": dumped,
             "config": {"workload": what, "name": args.workload, "batch_per_gpu": batch, "frames_per_sequence": frames, "global_batch": world * batch,
                        "resolution": [args.resolution, args.resolution], "grid": grid_name(args), "mesh": args.mesh, "seed": args.seed, "dmtet_pass": getattr(scene.netShape.topology, "_last_count_pass", None), "parallelism": f"dp{world}",
                        "networks": headline_networks, "tuned_mlp_gemms": bool(tuned),

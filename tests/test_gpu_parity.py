@@ -2476,7 +2476,7 @@ def test_bench_two_ranks_on_one_gpu_through_both_command_shapes(launcher):
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     tail = [os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu", "--steps", "2", "--warmup", "1", "--grid-res", "16",
-            "--resolution", "64", "--batch", "2", "--no-cpu-baseline", "--no-tuned-gemms"]
+            "--resolution", "64", "--batch", "2", "--no-cpu-baseline", "--no-tuned-gemms", "--full"]
     cmd = [sys.executable] + tail if launcher == "plain" else [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                                                               "--master-addr", "127.0.0.1", "--master-port", "29541"] + tail
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
@@ -2506,7 +2506,7 @@ def test_bench_eight_ranks_on_one_gpu_report_their_host_side_figures():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--backend", "gloo", "--share-gpu", "--steps", "3", "--warmup", "1", "--grid-res", "32",
-           "--resolution", "128", "--batch", "2", "--no-cpu-baseline", "--no-tuned-gemms", "--no-extra-legs", "--no-fingerprint"]
+           "--resolution", "128", "--batch", "2", "--no-cpu-baseline", "--no-tuned-gemms", "--no-extra-legs", "--no-fingerprint", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])
