@@ -283,8 +283,9 @@ __global__ __launch_bounds__(256) void gb_bwd_kernel(const float* __restrict__ g
         const float4* gp = reinterpret_cast<const float4*>(g_out + p * 12);
         const float4 ga = gp[0], gb4 = gp[1], gc = gp[2];
         float g[12] = {ga.x, ga.y, ga.z, ga.w, gb4.x, gb4.y, gb4.z, gb4.w, gc.x, gc.y, gc.z, gc.w};
-        if (g_tex) {  // the canonical position's gradient arrives as rows of its own (the fields' input gradient): columns 9..11 of g_out are not read
-            g[9] = g_tex[3 * p]; g[10] = g_tex[3 * p + 1]; g[11] = g_tex[3 * p + 2];
+        if (g_tex) {  // the canonical position's gradient through the fields' input rows (tex_out) is added to that through columns 9..11 of
+                      // g_out: both are differentiable outputs holding the same position, and a loss may use both
+            g[9] += g_tex[3 * p]; g[10] += g_tex[3 * p + 1]; g[11] += g_tex[3 * p + 2];
         }
         float ex[3][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}}, ge[3] = {0.f, 0.f, 0.f};
         if (NC > 12) {

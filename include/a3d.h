@@ -489,7 +489,7 @@ int a3d_gbuffer_bwd(const float* g_out, const float* rast, const int32_t* tri, c
                     const float* v_nrm, const float* prior, int prior_batch, const float* clip_or_null, int B, int V, int F, int H, int W,
                     float* g_rows, int g_rows_are_clear, int want_prior, const float* extra_or_null, int E, const float* g_extra_out_or_null,
                     const float* g_tex_or_null /* (403) [>= P,3]: the gradient of the canonical position as rows of its own (aux.tex_out's);
-                                                  columns 9..11 of g_out are then ignored */,
+                                                  added to columns 9..11 of g_out */,
                     a3d_stream_t stream);
 /* (403) g_prior[V,3] = the sum over the B images of columns 6..8 of g_rows: the gradient of a canonical mesh that all images share
  * (prior_batch == 1; render.py:209 interpolates prior_mesh.v_pos for every image). */
