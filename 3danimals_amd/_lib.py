@@ -100,6 +100,10 @@ SIGNATURES = {
     "a3d_mask_aa_fwd": (_c_int, [_p, _c_int, _p, _c_int, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p]),
     "a3d_mask_aa_bwd": (_c_int, [_p, _p, _c_int, _p, _c_int, _p, _p, _c_int, _p, _c_int, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _c_int, _p]),
     "a3d_composite_aa_bwd": (_c_int, [_p, _p, _p, ctypes.c_int64, _p, _p, _p, _c_int, _p, _c_int, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _p]),
+    "a3d_texture_fwd": (_c_int, [_p, _p, _p, _p, _c_int, _c_int, _c_int, _p, _p]),
+    "a3d_texture_bwd": (_c_int, [_p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _p, _p, _p, _p]),
+    "a3d_texture_mip_fwd": (_c_int, [_p, _p]),
+    "a3d_texture_mip_bwd": (_c_int, [_p, _p]),
 }
 
 
@@ -172,6 +176,13 @@ class DmtetEmitOpts(ctypes.Structure):
                 ("topo_count", _p), ("topo_adj", _p), ("device_counts", _p), ("n_surf", ctypes.c_int32), ("topo_stride", ctypes.c_int32),
                 ("use_block_lists", ctypes.c_int32), ("n_edge_blocks_listed", ctypes.c_int32), ("n_tet_blocks_listed", ctypes.c_int32),
                 ("surf_bucket", ctypes.c_int32), ("surf_pts", _p)]
+
+
+class TexDesc(ctypes.Structure):
+    """a3d_tex_desc of include/a3d.h."""
+
+    _fields_ = [("size", ctypes.c_uint32), ("C", ctypes.c_int32), ("tex_batch", ctypes.c_int32), ("filter", ctypes.c_int32), ("boundary", ctypes.c_int32),
+                ("levels", ctypes.c_int32), ("height", ctypes.c_int32 * 16), ("width", ctypes.c_int32 * 16), ("level", _p * 16), ("grad", _p * 16)]
 
 
 ABI_VERSION = 404  # a3d_version() of the library these signatures belong to (include/a3d.h)

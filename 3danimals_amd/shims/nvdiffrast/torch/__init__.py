@@ -3,9 +3,10 @@
 Put ``3danimals_amd/shims`` on ``sys.path`` and the reference's unchanged callers --
 ``dr.RasterizeGLContext()`` (AnimalModel.py:235-236), ``dr.DepthPeeler`` / ``dr.interpolate`` / ``dr.antialias``
 (render.py:24,264-267,292-294), ``dr.rasterize`` (render.py:351, visualize_results.py:225-229) -- run on MI355X
-without OpenGL or CUDA.  Instanced and range mode, ``grad_db``, ``diff_attrs`` and ``pos_gradient_boost`` are covered; ``dr.texture`` has
-no call site on the reconstruct-and-render path (only EnvironmentLight, Texture2D mips and image_grad use it, all dead code in every
-config): its 2-D bilinear / nearest tap is provided in torch, mip-mapped and cube-map sampling raise.
+without OpenGL or CUDA.  Instanced and range mode, ``grad_db``, ``diff_attrs`` and ``pos_gradient_boost`` are covered.  ``dr.texture``
+(Texture2D.sample, EnvironmentLight.shade, cubemap_mip, cubemap_to_latlong, the 2-D bilinear taps) runs every mode on the GPU --
+mip-mapped, uv_da, mip_level_bias, custom mip stacks, cube maps -- and ``dr.texture_construct_mip`` builds a stack there; on CPU
+tensors only the 2-D bilinear / nearest tap exists (torch).
 """
 import importlib
 
@@ -225,21 +226,31 @@ def antialias_construct_topology_hash(tri):
 
 
 def texture(tex, uv, uv_da=None, mip_level_bias=None, mip=None, filter_mode="auto", boundary_mode="wrap", max_mip_level=None):
-    """dr.texture for 2-D textures WITHOUT mip-mapping: tex [1|B,Th,Tw,C], uv [B,H,W,2] in texture units (0..1, texel centres at
-    (i + 0.5) / size) -> [B,H,W,C]; filter_mode 'nearest' | 'linear' ('auto' = 'linear' when no uv_da / mip_level_bias is given),
-    boundary_mode 'wrap' | 'clamp' | 'zero'.  Plain torch (differentiable w.r.t. tex and uv): no config of the reference reaches
-    dr.texture from the reconstruct-and-render path (the texture is a coordinate MLP, render.py:53-57); this serves the off-path callers
-    that only need a bilinear tap -- texture2d_mip's backward (texture.py:32), image_grad's tap (regularizer.py:24), the FG look-up table
-    (light.py:118).  Mip-mapped and cube-map sampling (Texture2D.sample with uv_da, EnvironmentLight) raise: out of scope (SURVEY.md
-    section 2 row 12)."""
-    if filter_mode == "auto":
-        filter_mode = "linear-mipmap-linear" if (uv_da is not None or mip_level_bias is not None) else "linear"
-    if filter_mode not in ("nearest", "linear"):
-        raise NotImplementedError(f"dr.texture filter_mode {filter_mode!r}: mip-mapped sampling is not on the reconstruct-and-render path")
-    if boundary_mode == "cube" or tex.dim() != 4 or uv.shape[-1] != 2:
-        raise NotImplementedError("dr.texture: cube maps are not on the reconstruct-and-render path")
+    """dr.texture.  CUDA float32 inputs, every mode: ops.texture (csrc/texture.hip), whose docstring holds the specification -- this
+    project's, written from nvdiffrast's published interface and UNPINNED against upstream.  In short: tex [1|B,Th,Tw,C] or, with
+    boundary_mode='cube', [1|B,6,S,S,C]; uv [B,H,W,2] in texture units (texel centres at (i + 0.5) / size) or [B,H,W,3] directions;
+    uv_da [B,H,W,4|6]; mip_level_bias [B,H,W]; mip = None (built on the device), a list of levels or texture_construct_mip's stack;
+    filter_mode 'nearest' | 'linear' | 'linear-mipmap-nearest' | 'linear-mipmap-linear' ('auto' = 'linear-mipmap-linear' when uv_da
+    or mip_level_bias is given, else 'linear'); boundary_mode 'wrap' | 'clamp' | 'zero' | 'cube' (seamless).
+    CPU tensors (any dtype) and non-float32 CUDA tensors in 2-D 'nearest' / 'linear' take a plain torch tap (differentiable w.r.t. tex
+    and uv) -- texture2d_mip's backward (texture.py:32), image_grad (regularizer.py:24), the FG look-up table (light.py:118) on any
+    device; mip-mapped, uv_da and cube-map sampling of CPU tensors raise NotImplementedError: they need GPU tensors."""
+    filter_mode = _ops.texture_filter_mode(filter_mode, uv_da, mip_level_bias)
+    cube = boundary_mode == "cube" or tex.dim() != 4 or uv.shape[-1] != 2
+    gpu = tex.is_cuda and uv.is_cuda
+    if gpu and (tex.dtype == torch.float32 and uv.dtype == torch.float32 or cube or filter_mode not in ("nearest", "linear")):
+        return _ops.texture(tex, uv, uv_da, mip_level_bias, mip, filter_mode, boundary_mode, max_mip_level)
+    if filter_mode not in ("nearest", "linear") or uv_da is not None:
+        raise NotImplementedError(f"dr.texture filter_mode {filter_mode!r} / uv_da: mip-mapped sampling needs GPU tensors")
+    if cube:
+        raise NotImplementedError("dr.texture: cube-map sampling needs GPU tensors")
     if boundary_mode not in ("wrap", "clamp", "zero"):
         raise ValueError(f"dr.texture: unknown boundary_mode {boundary_mode!r}")
+    return _torch_tap(tex, uv, filter_mode, boundary_mode)
+
+
+def _torch_tap(tex, uv, filter_mode, boundary_mode):
+    """The torch 2-D 'nearest' / 'linear' tap, on any device (tests and tools/bench_texture.py hold the HIP kernel against it)."""
     B = uv.shape[0]
     assert tex.shape[0] in (1, B), "texture batch must be 1 or the uv batch"
     Th, Tw, C = tex.shape[1:]
@@ -263,6 +274,13 @@ def texture(tex, uv, uv_da=None, mip_level_bias=None, mip=None, filter_mode="aut
     top = tap(x0, y0) * (1 - fx) + tap(x0 + 1, y0) * fx
     bot = tap(x0, y0 + 1) * (1 - fx) + tap(x0 + 1, y0 + 1) * fx
     return top * (1 - fy) + bot * fy
+
+
+def texture_construct_mip(tex, max_mip_level=None, cube_mode=False):
+    """The mip stack of ``tex`` (box filter, ops.texture_mip_sizes) built on the GPU, to pass as ``mip=``; its levels are constants."""
+    if not tex.is_cuda:
+        raise NotImplementedError("dr.texture_construct_mip needs a GPU tensor")
+    return _ops.texture_construct_mip(tex, max_mip_level, cube_mode)
 
 
 def get_log_level():

@@ -716,6 +716,56 @@ int a3d_flow_delta_fwd(const float* clip, int N, int F, int V, float* delta, a3d
 int a3d_flow_delta_bwd(const float* g_delta, int g_stride /* floats between two vertices of g_delta (2 = contiguous) */, const float* clip, int N,
                        int F, int V, float* g_clip, a3d_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Texture sampling -- replaces dr.texture for every mode the reference calls it in: Texture2D.sample (2-D, uv_da, mip list,
+ * linear-mipmap-linear; reference model/render/texture.py:67,73,75), EnvironmentLight.shade (cube linear; cube, mip list +
+ * mip_level_bias, linear-mipmap-linear; light.py:109,122), cubemap_mip.backward and cubemap_to_latlong (cube linear; light.py:41,
+ * util.py:133) and the plain 2-D bilinear taps (texture.py:32, light.py:118, util.py:117, regularizer.py:24).
+ * The semantics are this project's specification written from nvdiffrast's published interface, UNPINNED against upstream (no nvdiffrast
+ * build to compare with); 3danimals_amd/ops.py texture() states them in full.  In short: texel centres at (i + 0.5) / size; filters
+ * nearest / linear / linear-mipmap-nearest / linear-mipmap-linear; boundaries wrap / clamp / zero per level, or a seamless cube
+ * (face = largest |component|, ties x < y < z, faces +x -x +y -y +z -z, face coordinates the inverse of the reference's cube_to_dir,
+ * taps across an edge re-projected onto the neighbouring face, a corner tap replaced by the mean of the quad's other three);
+ * level = 0.5 log2(lambda_max(J J^T)) + bias clamped to [0, L-1], J the texel-space Jacobian from uv_da (cube: by the quotient rule at
+ * S/2 texels per unit); uv's gradient treats the level as a constant.
+ * One descriptor carries the stack: level l is [tex_batch, H_l, W_l, C] (cube: [tex_batch, 6, S_l, S_l, C]); lookups uv [B,H,W,2|3],
+ * uv_da [B,H,W,4|6] and bias [B,H,W] (both may be NULL), out [B,H,W,C].
+ *   a3d_texture_fwd     : out (every element written).
+ *   a3d_texture_bwd     : g_out -> g_uv, g_uv_da, g_bias (plain stores, every element written; each may be NULL) and the level gradients
+ *                         grad[l] (ACCUMULATED: the caller zeroes them; a NULL level is skipped).  Texel rows are merged inside the wave
+ *                         (lanes = an 8 x 8 block of lookups) before they leave as float atomics; results do not depend on the merge.
+ *   a3d_texture_mip_fwd : levels 1 .. levels-1 from level 0, each a 2 x 2 (2 x 1, 1 x 2) box mean of the one before (written).
+ *   a3d_texture_mip_bwd : grad[levels-1] .. grad[1] pushed down the box filter into grad[levels-2] .. grad[0] (accumulated, in place).
+ * Level sizes must follow the halving rule for the mip entry points: a dimension > 1 is even and halves, a dimension of 1 stays.
+ */
+#define A3D_TEX_MAX_LEVELS 16
+#define A3D_TEX_NEAREST 0
+#define A3D_TEX_LINEAR 1
+#define A3D_TEX_LINEAR_MIPMAP_NEAREST 2
+#define A3D_TEX_LINEAR_MIPMAP_LINEAR 3
+#define A3D_TEX_WRAP 0
+#define A3D_TEX_CLAMP 1
+#define A3D_TEX_ZERO 2
+#define A3D_TEX_CUBE 3
+typedef struct a3d_tex_desc {
+    uint32_t size;      /* sizeof(a3d_tex_desc) of the caller's header (fields are only ever appended) */
+    int32_t C;          /* channels (any count) */
+    int32_t tex_batch;  /* 1 (shared) or B */
+    int32_t filter;     /* A3D_TEX_NEAREST .. A3D_TEX_LINEAR_MIPMAP_LINEAR */
+    int32_t boundary;   /* A3D_TEX_WRAP / CLAMP / ZERO, or A3D_TEX_CUBE */
+    int32_t levels;     /* 1 .. A3D_TEX_MAX_LEVELS */
+    int32_t height[A3D_TEX_MAX_LEVELS]; /* rows of level l (cube: the face size S_l, = width[l]) */
+    int32_t width[A3D_TEX_MAX_LEVELS];
+    float* level[A3D_TEX_MAX_LEVELS];   /* read by fwd / bwd; levels 1.. written by mip_fwd */
+    float* grad[A3D_TEX_MAX_LEVELS];    /* the level gradients (bwd, mip_bwd), or NULL */
+} a3d_tex_desc;
+int a3d_texture_fwd(const a3d_tex_desc* desc, const float* uv, const float* uv_da_or_null, const float* bias_or_null, int B, int H, int W,
+                    float* out, a3d_stream_t stream);
+int a3d_texture_bwd(const a3d_tex_desc* desc, const float* g_out, const float* uv, const float* uv_da_or_null, const float* bias_or_null,
+                    int B, int H, int W, float* g_uv_or_null, float* g_uv_da_or_null, float* g_bias_or_null, a3d_stream_t stream);
+int a3d_texture_mip_fwd(const a3d_tex_desc* desc, a3d_stream_t stream);
+int a3d_texture_mip_bwd(const a3d_tex_desc* desc, a3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
