@@ -117,6 +117,16 @@ __device__ __forceinline__ int wrap_index(int i, int n, int boundary, bool& insi
 // floor of a texel coordinate as an int, kept far inside the int range whatever the input (NaN included: fmaxf / fminf drop it)
 __device__ __forceinline__ float safe_floor(float x) { return floorf(fminf(fmaxf(x, -1.0e9f), 1.0e9f)); }
 
+// A 2-D texel coordinate beyond +-2^22 has lost the half of "u * size - 0.5" (and beyond safe_floor's 1e9 its fraction): reduce before
+// the floor.  Wrap: the taps and the fraction of (u - floor(u)) * size - 0.5 are those of u * size - 0.5 (u - floorf(u) is exact in fp32).
+// Clamp / zero: a coordinate below -2 has the taps and the result of -2, one above size + 1 those of size + 1.  Ordinary lookups
+// never come here, so their results stay bit-identical; for every finite uv the weights stay in [0, 1] and sum to 1.
+constexpr float TX_FAR = 4194304.f;  // 2^22
+__device__ __forceinline__ float far_coord(float u, int size, int boundary, float x) {
+    if (boundary == A3D_TEX_WRAP) return (u - floorf(u)) * (float)size - 0.5f;
+    return fminf(fmaxf(x, -2.f), (float)size + 1.f);
+}
+
 // The 4 taps (nearest: 1) of a level: row (-1 = contributes nothing), weight, d weight / d x and d y in texel units
 struct Quad {
     int row[4];
@@ -131,8 +141,11 @@ __device__ __forceinline__ void level_quad(const TexK& k, const Lookup& L, const
         x = (L.s + 1.f) * 0.5f * (float)W - 0.5f;
         y = (L.t + 1.f) * 0.5f * (float)W - 0.5f;
     } else {
-        x = uv[2 * i] * (float)W - 0.5f;
-        y = uv[2 * i + 1] * (float)H - 0.5f;
+        const float u = uv[2 * i], v = uv[2 * i + 1];
+        x = u * (float)W - 0.5f;
+        y = v * (float)H - 0.5f;
+        if (fabsf(x) > TX_FAR) x = far_coord(u, W, k.boundary, x);
+        if (fabsf(y) > TX_FAR) y = far_coord(v, H, k.boundary, y);
     }
     if (nearest) {
         const int ix = (int)safe_floor(x + 0.5f), iy = (int)safe_floor(y + 0.5f);
@@ -197,26 +210,44 @@ __device__ __forceinline__ void lod_of(const TexK& k, const Lookup& L, const flo
     bool lod_ok = true;  // (a zero Jacobian: level -inf, clamped to 0, no gradient)
     float dlam[4] = {0.f, 0.f, 0.f, 0.f}, dlod_dlam = 0.f;
     if (uv_da) {
-        float J00, J01, J10, J11;
-        if (k.cube) {
-            const float* d = uv_da + 6 * i;
-            const float half = 0.5f * (float)k.w[0];
-            const float mX = L.sm * d[2 * L.im], mY = L.sm * d[2 * L.im + 1];
-            J00 = half * (L.sa * d[2 * L.ia] - L.s * mX) * L.inv_m;
-            J01 = half * (L.sa * d[2 * L.ia + 1] - L.s * mY) * L.inv_m;
-            J10 = half * (L.sb * d[2 * L.ib] - L.t * mX) * L.inv_m;
-            J11 = half * (L.sb * d[2 * L.ib + 1] - L.t * mY) * L.inv_m;
-        } else {
-            const float4 d = reinterpret_cast<const float4*>(uv_da)[i];
-            J00 = d.x * (float)k.w[0]; J01 = d.y * (float)k.w[0];
-            J10 = d.z * (float)k.h[0]; J11 = d.w * (float)k.h[0];
+        const float* dq = uv_da + 6 * i;  // (cube)
+        const float4 d4 = k.cube ? make_float4(0.f, 0.f, 0.f, 0.f) : reinterpret_cast<const float4*>(uv_da)[i];
+        float J00, J01, J10, J11, a, c, bb, hd, r, lam;
+        // J of uv_da * 2^-ex (exact: J is linear in uv_da), lambda_max(J J^T) and its parts
+        auto eig = [&](int ex) {
+            auto sc = [ex](float v) { return ex ? ldexpf(v, -ex) : v; };
+            if (k.cube) {
+                const float half = 0.5f * (float)k.w[0];
+                const float mX = L.sm * sc(dq[2 * L.im]), mY = L.sm * sc(dq[2 * L.im + 1]);
+                J00 = half * (L.sa * sc(dq[2 * L.ia]) - L.s * mX) * L.inv_m;
+                J01 = half * (L.sa * sc(dq[2 * L.ia + 1]) - L.s * mY) * L.inv_m;
+                J10 = half * (L.sb * sc(dq[2 * L.ib]) - L.t * mX) * L.inv_m;
+                J11 = half * (L.sb * sc(dq[2 * L.ib + 1]) - L.t * mY) * L.inv_m;
+            } else {
+                J00 = sc(d4.x) * (float)k.w[0]; J01 = sc(d4.y) * (float)k.w[0];
+                J10 = sc(d4.z) * (float)k.h[0]; J11 = sc(d4.w) * (float)k.h[0];
+            }
+            a = J00 * J00 + J01 * J01; c = J10 * J10 + J11 * J11; bb = J00 * J10 + J01 * J11;
+            hd = 0.5f * (a - c); r = sqrtf(hd * hd + bb * bb);
+            lam = 0.5f * (a + c) + r;
+        };
+        eig(0);
+        int ex = 0;
+        if (!(lam > 0.f && lam < INFINITY)) {
+            // lambda over- or underflowed fp32 (|J| beyond ~6e9 or below ~1e-19 texels per pixel) for a finite, non-zero uv_da: redo it on
+            // uv_da * 2^-ex (its largest component into [0.5, 1)); level = 0.5 log2(lambda') + ex, and d level / d J scales by 2^-ex.
+            // A zero J stays a zero J (level 0); a non-finite uv_da is outside the specification (level 0 too).
+            float m = k.cube ? 0.f : fmaxf(fmaxf(fabsf(d4.x), fabsf(d4.y)), fmaxf(fabsf(d4.z), fabsf(d4.w)));
+            if (k.cube)
+                for (int j = 0; j < 6; ++j) m = fmaxf(m, fabsf(dq[j]));
+            if (m > 0.f && m < INFINITY) {
+                frexpf(m, &ex);
+                eig(ex);
+            }
         }
-        const float a = J00 * J00 + J01 * J01, c = J10 * J10 + J11 * J11, bb = J00 * J10 + J01 * J11;
-        const float hd = 0.5f * (a - c), r = sqrtf(hd * hd + bb * bb);
-        const float lam = 0.5f * (a + c) + r;
         if (lam > 0.f && lam < INFINITY) {
-            lod = 0.5f * log2f(lam);
-            dlod_dlam = 0.5f / (lam * 0.69314718055994531f);
+            lod = 0.5f * log2f(lam) + (float)ex;
+            dlod_dlam = ldexpf(0.5f / (lam * 0.69314718055994531f), -ex);
             const float da = r > 0.f ? 0.5f + hd / (2.f * r) : 0.5f, dc = r > 0.f ? 0.5f - hd / (2.f * r) : 0.5f, db = r > 0.f ? bb / r : 0.f;
             dlam[0] = 2.f * J00 * da + J10 * db;
             dlam[1] = 2.f * J01 * da + J11 * db;

@@ -2060,6 +2060,8 @@ class _Texture(torch.autograd.Function):
         require_device(uv, uv_da, bias, *levels, what="texture")
         cube = boundary == _TEX_BOUNDARIES["cube"]
         uv, uv_da, bias = f32c(uv), None if uv_da is None else f32c(uv_da), None if bias is None else f32c(bias)
+        if uv_da is not None and not cube and uv_da.data_ptr() % 16:  # (the kernels read a 2-D uv_da row as one float4)
+            uv_da = uv_da.clone()
         levels = [f32c(t) for t in levels]
         Bt, _, _, C = _tex_hw(levels[0], cube)
         B = uv.shape[0]
@@ -2114,7 +2116,8 @@ def texture(tex, uv, uv_da=None, mip_level_bias=None, mip=None, filter_mode="aut
         the face it is fetched from (clamped into range); a tap outside in both (a cube corner) is the mean of the quad's other three.
     Level of detail: 2-D, J = rows (du/dX, du/dY) * Tw and (dv/dX, dv/dY) * Th; cube, the face-coordinate derivatives of uv_da by the
     quotient rule at S/2 texels per unit.  level = 0.5 log2(lambda_max(J J^T)) + bias (without uv_da: level = bias), clamped to
-    [0, L-1]; a zero J gives level 0.  'linear-mipmap-nearest' takes level floor(level + 0.5), 'linear-mipmap-linear' blends the two
+    [0, L-1]; a zero J gives level 0.  The level follows this for every finite uv_da, also where J J^T lies beyond the fp32 range
+    (|J| above ~6e9 or below ~1e-19 texels per pixel).  'linear-mipmap-nearest' takes level floor(level + 0.5), 'linear-mipmap-linear' blends the two
     neighbouring levels by the fraction.
     Mip stack: mip=None (mipmap modes) builds it on the device (texture_mip_sizes: halve every dimension > 1 with a box mean, stop at
     1 x 1, at max_mip_level or at an odd dimension > 1), differentiably back to ``tex``; mip=[tensors] is a custom stack whose level i
@@ -2122,7 +2125,9 @@ def texture(tex, uv, uv_da=None, mip_level_bias=None, mip=None, filter_mode="aut
     (texture_construct_mip) holds constants.
     Gradients: tex and every mip tensor always; uv except under 'nearest' (zeros there), with the level treated as a constant (so in
     cube mode g_uv is orthogonal to uv); uv_da and mip_level_bias only under 'linear-mipmap-linear' and where the level is not clamped.
-    A zero cube direction samples 0."""
+    A zero cube direction samples 0.  A 2-D uv of any finite size samples as specified: under wrap it is taken modulo 1, and under
+    clamp / zero a uv far outside the texture reads the edge texels, or nothing.  Non-finite uv or uv_da values are outside this
+    specification: they give NaN or level-0 results, never an access outside the texture."""
     filter_mode = texture_filter_mode(filter_mode, uv_da, mip_level_bias)
     if boundary_mode not in _TEX_BOUNDARIES:
         raise ValueError(f"texture: unknown boundary_mode {boundary_mode!r}")

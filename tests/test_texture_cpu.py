@@ -147,3 +147,83 @@ def test_restatement_closed_forms():
     for k, want in ((1.0, chain[1]), (1.25, 0.75 * chain[1] + 0.25 * R.texture(chain[2], uv, filter_mode="linear", boundary_mode="clamp"))):
         got = R.texture(tex2, uv, mip_level_bias=torch.full((1, 4, 4), k, dtype=torch.float64), boundary_mode="clamp")
         assert torch.allclose(got, want), k
+
+
+# ------------------------------------------------------------------------------------------------ premises of test_texture_backward_gpu.py
+def _all_grads(dtype, f, mode, boundary, uv=None):
+    to = lambda t: None if t is None else t.to(dtype).clone().requires_grad_(True)
+    tex, u, b = to(f["tex"]), to(f["uv"] if uv is None else uv), to(f["bias"])
+    mip = None if f["mip"] is None else [to(m) for m in f["mip"]]
+    out = R.texture(tex, u, None, b, mip=mip, filter_mode=mode, boundary_mode=boundary)
+    out.backward(f["g"].to(dtype))
+    return [out.detach()] + [t.grad if t.grad is not None else torch.zeros_like(t) for t in [tex, u] + (mip or []) + ([b] if b is not None else [])]
+
+
+@pytest.mark.parametrize("mode", ["nearest", "linear", "linear-mipmap-nearest", "linear-mipmap-linear"])
+def test_exact_fields_are_exact_in_fp32(mode):
+    """The generator's fields (R.exact_field) give bit-identical outputs and gradients from the restatement in float32 and float64: no
+    fp32 operation rounds, so the GPU tests may compare with torch.equal whatever order the kernel's float atomics add in."""
+    shapes = [(3, 31, 31), (1, 17, 9), (3, 23, 3)]
+    for i, pattern in enumerate(R.PATTERNS):
+        B, H, W = shapes[i % 3]
+        for size in ((32, 16), (1, 16), (1, 1)):
+            for k in (0, 1, 2):
+                f = R.exact_field(pattern, B, H, W, size, (1, 3, 5, 8)[i % 4], mode, seed=10 * i + k, k=k, tex_batch=B if i % 2 else 1)
+                for boundary in ("wrap", "clamp", "zero"):
+                    a, b = _all_grads(torch.float32, f, mode, boundary), _all_grads(torch.float64, f, mode, boundary)
+                    for j, (x, y) in enumerate(zip(a, b)):
+                        assert torch.equal(x.double(), y), (pattern, size, k, boundary, j, float((x.double() - y).abs().max()))
+
+
+def _drop_one_families():
+    g = R._gen(7)
+    f = R.exact_field("mag33", 2, 16, 16, (16, 16), 3, "linear-mipmap-linear", seed=1, k=1)
+    yield "exact mag33, custom stack", f["tex"], f["uv"], f["g"], None, f["bias"], f["mip"], dict(filter_mode="linear-mipmap-linear", boundary_mode="wrap")
+    f = R.exact_field("run3", 1, 17, 5, (16, 16), 4, "linear", seed=2)
+    yield "exact run3, narrow", f["tex"], f["uv"], f["g"], None, None, None, dict(filter_mode="linear", boundary_mode="zero")
+    tex = torch.rand(1, 32, 16, 4, generator=g, dtype=torch.float64)
+    uv = torch.rand(2, 12, 20, 2, generator=g, dtype=torch.float64) * 1.4 - 0.2
+    da = torch.randn(2, 12, 20, 4, generator=g, dtype=torch.float64) * 0.03
+    bias = torch.rand(2, 12, 20, generator=g, dtype=torch.float64) * 2 - 0.5
+    gg = R.small_ints((2, 12, 20, 4), 3)
+    yield "random trilinear, internal stack", tex, uv, gg, da, bias, None, dict(filter_mode="linear-mipmap-linear", boundary_mode="clamp")
+    d = torch.randn(1, 16, 16, 3, generator=g, dtype=torch.float64)
+    d[0, 0, :8] = torch.tensor([[x, y, z] for x in (-1, 1) for y in (-1, 1) for z in (-1, 1)], dtype=torch.float64)
+    yield "cube corners", torch.rand(1, 6, 8, 8, 3, generator=g, dtype=torch.float64), d, R.small_ints((1, 16, 16, 3), 4), None, None, None, \
+        dict(filter_mode="linear", boundary_mode="cube")
+    yy, xx = torch.meshgrid(torch.arange(64.0, dtype=torch.float64), torch.arange(64.0, dtype=torch.float64), indexing="ij")
+    uv = torch.stack([(xx + 0.5) / 64 + 0.03 * torch.sin(yy / 23), (yy + 0.5) / 64 + 0.03 * torch.cos(xx / 31)], -1)[None]
+    yield "smooth field", torch.rand(1, 24, 32, 4, generator=g, dtype=torch.float64), uv, R.small_ints((1, 64, 64, 4), 5), None, None, None, \
+        dict(filter_mode="linear", boundary_mode="wrap")
+
+
+def test_g_tex_bound_catches_one_dropped_lookup():
+    """On each pattern family of the GPU tests, the per-texel bound R.g_tex_bounds is tight enough that a g_tex missing any one
+    lookup's contribution breaks it at some texel (checked for every 7th lookup)."""
+    for name, tex, uv, g, da, bias, mip, kw in _drop_one_families():
+        levels = [tex] + list(mip or [])
+        leaves = lambda: [t.clone().requires_grad_(True) for t in levels]
+
+        def g_tex(gg):
+            ls = leaves()
+            out = R.texture(ls[0], uv, da, bias, mip=ls[1:] if mip else None, **kw)
+            return torch.autograd.grad(out, ls, gg, allow_unused=True)
+
+        full = g_tex(g)
+        bounds = R.g_tex_bounds(tex, uv, g, da, bias, mip, **kw)
+        n = g[..., 0].numel()
+        checked = 0
+        for i in range(0, n, 7):
+            gi = g.reshape(n, -1)
+            if float(gi[i].abs().sum()) == 0 or (kw["boundary_mode"] == "cube" and float(uv.reshape(n, 3)[i].abs().sum()) == 0):
+                continue
+            dropped = gi.clone()
+            dropped[i] = 0
+            part = g_tex(dropped.reshape(g.shape))
+            broke = any(bool(((a - b).abs() > bd).any()) for a, b, bd in zip(full, part, bounds) if a is not None)
+            lost = max(float((a - b).abs().max()) for a, b in zip(full, part) if a is not None)
+            if lost == 0:  # (a lookup whose taps all fall outside a zero-boundary texture contributes nothing)
+                continue
+            assert broke, (name, i, lost)
+            checked += 1
+        assert checked > 10, name
