@@ -104,6 +104,11 @@ SIGNATURES = {
     "a3d_texture_bwd": (_c_int, [_p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _p, _p, _p, _p]),
     "a3d_texture_mip_fwd": (_c_int, [_p, _p]),
     "a3d_texture_mip_bwd": (_c_int, [_p, _p]),
+    "a3d_cubemap_diffuse_fwd": (_c_int, [_p, _p]),
+    "a3d_cubemap_diffuse_bwd": (_c_int, [_p, _p]),
+    "a3d_cubemap_specular_bounds": (_c_int, [_p, _p]),
+    "a3d_cubemap_specular_fwd": (_c_int, [_p, _p]),
+    "a3d_cubemap_specular_bwd": (_c_int, [_p, _p]),
 }
 
 
@@ -183,6 +188,13 @@ class TexDesc(ctypes.Structure):
 
     _fields_ = [("size", ctypes.c_uint32), ("C", ctypes.c_int32), ("tex_batch", ctypes.c_int32), ("filter", ctypes.c_int32), ("boundary", ctypes.c_int32),
                 ("levels", ctypes.c_int32), ("height", ctypes.c_int32 * 16), ("width", ctypes.c_int32 * 16), ("level", _p * 16), ("grad", _p * 16)]
+
+
+class EnvDesc(ctypes.Structure):
+    """a3d_env_desc of include/a3d.h."""
+
+    _fields_ = [("size", ctypes.c_uint32), ("N", ctypes.c_int32), ("roughness", ctypes.c_float), ("costheta_cutoff", ctypes.c_float), ("src", _p),
+                ("dst", _p), ("bounds", _p), ("area", _p)]
 
 
 ABI_VERSION = 404  # a3d_version() of the library these signatures belong to (include/a3d.h)

@@ -3,7 +3,7 @@
     python 3danimals_amd/csrc/build.py [--force] [--profile | --exp]
 
 One object per .hip file, linked into 3danimals_amd/lib/liba3d_hip.so (in-tree, git-ignored, travels to the
-GPU box with the snapshot).  raster/dmtet/antialias/normals are compiled with -ffp-contract=off: their arithmetic is
+GPU box with the snapshot).  raster/dmtet/antialias/normals (and shade, embed, xfm, texture, envlight) are compiled with -ffp-contract=off: their arithmetic is
 specified operation by operation (oracle/raster_ref.c, reference dmtet.py:124-131, mesh.py:276-304).
 """
 import os
@@ -36,6 +36,7 @@ SOURCES = {
     "topology.hip": [],
     "xfm.hip": ["-ffp-contract=off"],
     "texture.hip": ["-ffp-contract=off"],
+    "envlight.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wall",
           "-Wno-unused-function"]

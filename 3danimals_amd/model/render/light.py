@@ -1,19 +1,22 @@
-"""Directional light of the hot path -- /root/reference/model/render/light.py:169-193.
-
-The environment-light / split-sum machinery of the reference file has no caller in any config (SURVEY.md
-section 2 row 16) and needs dr.texture; it is out of scope and not provided.
+"""Light sources -- reference model/render/light.py: the directional light of the hot path (:169-193) and the split-sum environment
+light (:27-162), whose prefilters run as HIP kernels (renderutils.diffuse_cubemap / specular_cubemap, csrc/envlight.hip) and whose
+lookups go through ops.texture.  load_env / save_env_map stay the reference's (they need its image I/O).
 """
+import math
+import os
+
+import numpy as np
 import torch
 import torch.nn.functional as F
 
+from ... import ops
+from . import renderutils as ru
 from . import util
 
 try:
     from model.networks import MLP  # type: ignore  (overlaid on the reference tree)
 except ImportError:  # stand-alone
     from ...hostnets import MLP
-
-_STANDALONE_ONLY = ("EnvironmentLight",)  # placeholders for stand-alone use: never overlaid on the reference's real definitions
 
 
 class DirectionalLight(torch.nn.Module):
@@ -44,6 +47,167 @@ class DirectionalLight(torch.nn.Module):
         return shading * kd, shading
 
 
-class EnvironmentLight:  # pragma: no cover - placeholder so isinstance checks in callers keep working
-    def __init__(self, *a, **k):
-        raise NotImplementedError("EnvironmentLight (split-sum, needs dr.texture) is outside the hot path; no config uses it")
+class cubemap_mip(torch.autograd.Function):
+    """One mip step of a cube map [6,S,S,C] -> [6,S/2,S/2,C]: the 2 x 2 box mean (ops.texture_construct_mip's filter).  The gradient
+    is the box filter's own adjoint, a quarter of the parent's gradient to each of its four texels -- not the reference's
+    0.25 * bilinear cube lookup of dout at the fine texel centres (light.py:32-42), which smooths the gradient across texel and face
+    borders and is not the derivative of its forward."""
+
+    @staticmethod
+    def forward(ctx, cubemap):
+        return ops.cube_box_down(cubemap)
+
+    @staticmethod
+    def backward(ctx, dout):
+        return ops.cube_box_down_adjoint(dout)
+
+
+FG_RES = 256
+FG_PHI, FG_XI = 16, 64  # quadrature of fg_table: azimuths over the half circle x radial samples
+FG_FILE = "data/irrmaps/bsdf_256_256.bin"  # the reference's table (light.py:117), taken when it exists; like there, relative to the working directory
+_fg_cache = {}
+
+
+def fg_table(device, dtype=torch.float32, rows=16):
+    """The split-sum environment BRDF [1,256,256,2]: texel (j, i) holds scale A and bias B of F0 at N.V = u = (i + 0.5) / 256 and
+    roughness r = (j + 0.5) / 256 (so dr.texture(table, (N.V, roughness)) reads it as the reference does).  This project's
+    specification, unpinned against the reference's missing data/irrmaps/bsdf_256_256.bin:
+
+        V = (sqrt(1 - u^2), 0, u), N = (0, 0, 1), alpha = r^2; GGX importance samples H on the fixed midpoint grid
+        phi_m = pi (m + 0.5) / 16, m = 0..15 (half circle: the integrand is even in phi), xi_n = (n + 0.5) / 64, n = 0..63,
+        cos(theta) = sqrt((1 - xi) / (1 + (alpha^2 - 1) xi)), H = (sin(theta) cos(phi), sin(theta) sin(phi), cos(theta)),
+        L = 2 (V.H) H - V; with k = alpha / 2, G1(x) = x / (x (1 - k) + k), G = G1(N.V) G1(N.L),
+        Gv = G (V.H) / ((N.H) (N.V)), Fc = (1 - V.H)^5, samples with N.L <= 0 or V.H <= 0 contribute 0:
+        A = mean((1 - Fc) Gv), B = mean(Fc Gv) over the 1024 samples.
+    The light evaluates it in float64 and rounds the table to float32 once."""
+    u = ((torch.arange(FG_RES, dtype=dtype, device=device) + 0.5) / FG_RES)[None, :, None, None]
+    phi = (math.pi * (torch.arange(FG_PHI, dtype=dtype, device=device) + 0.5) / FG_PHI)[None, None, :, None]
+    xi = ((torch.arange(FG_XI, dtype=dtype, device=device) + 0.5) / FG_XI)[None, None, None, :]
+    vx, vz = torch.sqrt(1 - u * u), u
+    out = []
+    for j0 in range(0, FG_RES, rows):  # (a few rows of roughness at a time: [rows,256,16,64] temporaries)
+        r = ((torch.arange(j0, j0 + rows, dtype=dtype, device=device) + 0.5) / FG_RES)[:, None, None, None]
+        alpha = r * r
+        cos_t = torch.sqrt((1 - xi) / (1 + (alpha * alpha - 1) * xi))
+        sin_t = torch.sqrt(torch.clamp(1 - cos_t * cos_t, min=0))
+        hx, hz = sin_t * torch.cos(phi), cos_t
+        vh = vx * hx + vz * hz
+        nl = 2 * vh * hz - vz
+        k = alpha / 2
+        g = (vz / (vz * (1 - k) + k)) * (nl / (nl * (1 - k) + k))
+        ok = (nl > 0) & (vh > 0)
+        gv = torch.where(ok, g * vh / (hz * vz), torch.zeros_like(g))
+        fc = (1 - torch.clamp(vh, 0, 1)) ** 5
+        out.append(torch.stack((((1 - fc) * gv).mean(dim=(2, 3)), (fc * gv).mean(dim=(2, 3))), dim=-1))
+    return torch.cat(out, dim=0)[None].contiguous()
+
+
+def _fg_lut(device):
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:  # ('cuda' and 'cuda:0' are one table)
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = str(device)
+    if key not in _fg_cache:
+        if os.path.exists(FG_FILE):
+            table = torch.as_tensor(np.fromfile(FG_FILE, dtype=np.float32).reshape(1, FG_RES, FG_RES, 2), dtype=torch.float32, device=device)
+        else:
+            table = fg_table(device, torch.float64).float()  # (in float64: the sine of a narrow lobe is a difference of near-equal numbers)
+        _fg_cache[key] = table
+    return _fg_cache[key]
+
+
+class EnvironmentLight(torch.nn.Module):
+    """Split-sum environment map light with automatic mip generation (reference light.py:48-128): ``env_base`` [6,N,N,3] is the
+    trainable map, build_mips() prefilters it -- differentiably -- into a roughness-indexed specular stack and a diffuse
+    irradiance map, shade() looks both up."""
+
+    LIGHT_MIN_RES = 16
+
+    MIN_ROUGHNESS = 0.08
+    MAX_ROUGHNESS = 0.5
+
+    def __init__(self, base):
+        super().__init__()
+        self.mtx = None
+        self.base = torch.nn.Parameter(base.clone().detach(), requires_grad=True)
+        self.register_parameter("env_base", self.base)
+
+    def xfm(self, mtx):
+        """Rotate the lookups by ``mtx`` [1,4,4] or [B,4,4] (B = the batch of the G-buffers handed to shade)."""
+        self.mtx = mtx
+
+    def clone(self):
+        return EnvironmentLight(self.base.clone().detach())
+
+    def clamp_(self, min=None, max=None):
+        self.base.clamp_(min, max)
+
+    def get_mip(self, roughness):
+        n = len(self.specular)
+        lo, hi = self.MIN_ROUGHNESS, self.MAX_ROUGHNESS
+        return torch.where(roughness < hi,
+                           (torch.clamp(roughness, lo, hi) - lo) / (hi - lo) * (n - 2),
+                           (torch.clamp(roughness, hi, 1.0) - hi) / (1.0 - hi) + n - 2)
+
+    def build_mips(self, cutoff=0.99):
+        self.specular = [self.base]
+        while self.specular[-1].shape[1] > self.LIGHT_MIN_RES:
+            self.specular += [cubemap_mip.apply(self.specular[-1])]
+
+        self.diffuse = ru.diffuse_cubemap(self.specular[-1])
+
+        n = len(self.specular)
+        for idx in range(n - 1):
+            roughness = (idx / (n - 2)) * (self.MAX_ROUGHNESS - self.MIN_ROUGHNESS) + self.MIN_ROUGHNESS
+            self.specular[idx] = ru.specular_cubemap(self.specular[idx], roughness, cutoff)
+        self.specular[-1] = ru.specular_cubemap(self.specular[-1], 1.0, cutoff)
+
+    def regularizer(self):
+        white = (self.base[..., 0:1] + self.base[..., 1:2] + self.base[..., 2:3]) / 3.0
+        return torch.mean(torch.abs(self.base - white))
+
+    def shade(self, gb_pos, gb_normal, kd, ks, view_pos, specular=True):
+        wo = util.safe_normalize(view_pos - gb_pos)
+
+        if specular:
+            roughness = ks[..., 1:2]  # y component
+            metallic = ks[..., 2:3]  # z component
+            spec_col = (1.0 - metallic) * 0.04 + kd * metallic
+            diff_col = kd * (1.0 - metallic)
+        else:
+            diff_col = kd
+
+        reflvec = util.safe_normalize(util.reflect(wo, gb_normal))
+        nrmvec = gb_normal
+        if self.mtx is not None:  # rotate the lookups
+            mtx = torch.as_tensor(self.mtx, dtype=torch.float32, device=gb_pos.device)
+            b, h, w, _ = reflvec.shape
+            if mtx.dim() != 3 or mtx.shape[0] not in (1, b):
+                raise ValueError(f"EnvironmentLight.shade: the lookup transform must be [1,4,4] or [{b},4,4], got {list(mtx.shape)}")
+            reflvec = ru.xfm_vectors(reflvec.reshape(b, h * w, 3), mtx).view(b, h, w, 3)
+            nrmvec = ru.xfm_vectors(nrmvec.reshape(b, h * w, 3), mtx).view(b, h, w, 3)
+
+        diffuse = ops.texture(self.diffuse[None, ...], nrmvec.contiguous(), filter_mode="linear", boundary_mode="cube")
+        shaded_col = diffuse * diff_col
+
+        if specular:
+            # FG term of the split sum
+            n_dot_v = torch.clamp(util.dot(wo, gb_normal), min=1e-4)
+            fg_uv = torch.cat((n_dot_v, roughness), dim=-1)
+            fg_lookup = ops.texture(_fg_lut(gb_pos.device), fg_uv, filter_mode="linear", boundary_mode="clamp")
+
+            # roughness-adjusted specular lookup
+            miplevel = self.get_mip(roughness)
+            spec = ops.texture(self.specular[0][None, ...], reflvec.contiguous(), mip=list(m[None, ...] for m in self.specular[1:]),
+                               mip_level_bias=miplevel[..., 0], filter_mode="linear-mipmap-linear", boundary_mode="cube")
+
+            reflectance = spec_col * fg_lookup[..., 0:1] + fg_lookup[..., 1:2]
+            shaded_col = shaded_col + spec * reflectance
+
+        return shaded_col * (1.0 - ks[..., 0:1])  # modulate by hemisphere visibility
+
+
+def create_trainable_env_rnd(base_res, scale=0.5, bias=0.25):
+    """A trainable environment light with a random base map (reference light.py:160-162)."""
+    base = torch.rand(6, base_res, base_res, 3, dtype=torch.float32, device="cuda") * scale + bias
+    return EnvironmentLight(base)

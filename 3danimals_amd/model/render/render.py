@@ -144,10 +144,13 @@ def shade(gb_pos, gb_geometric_normal, gb_normal, gb_tangent, gb_tex_pos, w2c, v
 
     bsdf = _resolve_bsdf(bsdf, material)
     shading = None
-    if lgt is None:
+    if bsdf == "pbr":  # reference render.py:83-87
+        assert isinstance(lgt, light.EnvironmentLight), "Invalid light type"
+        shaded_col = lgt.shade(gb_pos, gb_normal, kd, ks, view_pos, specular=True)
+    elif lgt is None:
         shaded_col = kd
-    elif isinstance(lgt, light.EnvironmentLight):
-        raise NotImplementedError("EnvironmentLight is outside the hot path")
+    elif isinstance(lgt, light.EnvironmentLight):  # reference render.py:91-92
+        shaded_col = lgt.shade(gb_pos, gb_normal, kd, ks, view_pos, specular=False)
     else:
         shaded_col, shading = lgt.shade(feat, kd, cam_normal)
 
@@ -167,9 +170,7 @@ def shade(gb_pos, gb_geometric_normal, gb_normal, gb_tangent, gb_tex_pos, w2c, v
 def _resolve_bsdf(bsdf, material):
     assert bsdf is not None or material.bsdf is not None, "Material must specify a BSDF type"
     bsdf = bsdf if bsdf is not None else material.bsdf
-    if bsdf == "pbr":
-        raise NotImplementedError("bsdf='pbr' needs an EnvironmentLight (reference render.py:83-87); no config uses it")
-    assert bsdf == "diffuse", "Invalid BSDF '%s'" % bsdf
+    assert bsdf in ("diffuse", "pbr"), "Invalid BSDF '%s'" % bsdf
     return bsdf
 
 
@@ -277,16 +278,16 @@ def _shade_points(pos, geo, nrm, tng, tex_pos, flow, pix, bhw, w2c, view_pos, lg
     all_tex = field(material, tex_rows, feat) if material is not None else torch.ones(n_pts, 9, device=dev)
     dino_rows = field(dino_net, tex_rows, class_vector) if dino_net is not None else None
 
-    _resolve_bsdf(bsdf, material)
-    if lgt is not None and isinstance(lgt, light.EnvironmentLight):
-        raise NotImplementedError("EnvironmentLight is outside the hot path")
+    bsdf = _resolve_bsdf(bsdf, material)
+    env = isinstance(lgt, light.EnvironmentLight)  # image-based lighting: the general path below, never the fused compositor
+    assert env or bsdf != "pbr", "Invalid light type"  # (reference render.py:83-87)
     modes = render_modes if render_modes is not None else ["shaded"]
     view = view_pos.reshape(-1, 3)
-    light_rows = lgt(feat) if lgt is not None else None  # DirectionalLight.forward: [B,5] = direction(3), ambient, diffuse (light.py:176-184)
+    light_rows = lgt(feat) if lgt is not None and not env else None  # DirectionalLight.forward: [B,5] = direction(3), ambient, diffuse (light.py:176-184)
 
     # ---- the fused training path: nothing is computed here.  The compositor computes the colour on the fly and its backward node runs
     # the shading adjoint (ops.ShadeRecipe / ops.shade_composite_antialias): no [B,17] table, no kd / ks / row slices, no launch.
-    if (gb is not None and FUSED_SHADING and SHADE_IN_COMPOSITOR and sparse and inv is not None and lgt is not None and material is not None
+    if (gb is not None and FUSED_SHADING and SHADE_IN_COMPOSITOR and sparse and inv is not None and lgt is not None and not env and material is not None
             and w2c.dim() == 3 and all(m in ("shaded", "dino_pred", "flow", "kd", "ks") for m in modes)):
         recipe = ops.ShadeRecipe(gb, w2c, view, light_rows, all_tex, two_sided_shading, img_rows)
         LAST_POINTS[0] = dict(pix=pix, gb=gb.detach(), all_tex=all_tex.detach(), dino=None if dino_rows is None else dino_rows.detach(),
@@ -308,11 +309,18 @@ def _shade_points(pos, geo, nrm, tng, tex_pos, flow, pix, bhw, w2c, view_pos, lg
     dino_pred = None if dino_rows is None else (dino_rows[:n_pts] if n_pad else dino_rows)
     # the narrow per-image quantities (camera rotation 9, view position 3, light parameters 5) travel to the points as ONE gather
     cols = [w2c[:, :3, :3].reshape(-1, 9).expand(b, 9), view.expand(b, 3)]
-    if lgt is not None:
+    if light_rows is not None:
         cols.append(light_rows)
     per_image = torch.cat(cols, dim=-1)  # [B, 12 | 17]
     shading = None
-    if gb is not None and FUSED_SHADING:  # one HIP kernel each way for the ~30 (+~70 backward) elementwise launches below; the kernels
+    if env:  # reference render.py:83-92 on the point list: the shading normal, then the environment lookups ([1,1,P,.] images)
+        # (the point list is ONE image: a lookup transform lgt.xfm(mtx) must be [1,4,4] here; lgt.shade refuses a per-image [B,4,4], B > 1)
+        view_p = _rows_per_point(per_image, img, b)[:, 9:12]
+        nrm = ru.prepare_shading_normal(pos, view_p, None, nrm, tng, geo, two_sided_shading=two_sided_shading, opengl=True, use_python=True)
+        as_image = lambda t: t.reshape(1, 1, n_pts, t.shape[-1])
+        shaded_col = lgt.shade(as_image(pos), as_image(nrm), as_image(kd), as_image(ks), as_image(view_p),
+                               specular=bsdf == "pbr").reshape(n_pts, 3)
+    elif gb is not None and FUSED_SHADING:  # one HIP kernel each way for the ~30 (+~70 backward) elementwise launches below; the kernels
         # read the image's row through the point -> image index (no [P,17] copy) and reduce its gradient per image themselves
         if lgt is None:
             nrm, shaded_col = ops.shade_points(gb, per_image, None, two_sided_shading, img=img), kd

@@ -2164,6 +2164,176 @@ def texture(tex, uv, uv_da=None, mip_level_bias=None, mip=None, filter_mode="aut
     return _Texture.apply(_TEX_FILTERS[filter_mode], _TEX_BOUNDARIES[boundary_mode], uv, uv_da, mip_level_bias, *levels)
 
 
+def cube_box_down(cubemap):
+    """[6,S,S,C] -> [6,S/2,S/2,C]: the 2 x 2 box mean of every face (a3d_texture_mip_fwd on a one-step cube stack); no autograd."""
+    require_device(cubemap, what="cube_box_down")
+    if cubemap.dim() != 4 or cubemap.shape[0] != 6 or cubemap.shape[1] != cubemap.shape[2] or cubemap.shape[1] % 2:
+        raise ValueError(f"cube_box_down: the map must have shape [6, S, S, C] with S even, got {list(cubemap.shape)}")
+    fine = f32c(cubemap.detach())[None]
+    S, C = fine.shape[2], fine.shape[4]
+    coarse = torch.empty((1, 6, S // 2, S // 2, C), dtype=torch.float32, device=fine.device)
+    call("a3d_texture_mip_fwd", ctypes.byref(_tex_desc([fine, coarse], C, 1, 1, 3)), stream())
+    return coarse[0]
+
+
+def cube_box_down_adjoint(g_coarse):
+    """The adjoint of cube_box_down: [6,S,S,C] -> [6,2S,2S,C], every fine texel gets a quarter of its parent (a3d_texture_mip_bwd)."""
+    require_device(g_coarse, what="cube_box_down_adjoint")
+    coarse = f32c(g_coarse.detach())[None].clone()
+    S, C = coarse.shape[2], coarse.shape[4]
+    fine = torch.zeros((1, 6, 2 * S, 2 * S, C), dtype=torch.float32, device=coarse.device)
+    call("a3d_texture_mip_bwd", ctypes.byref(_tex_desc([fine, coarse], C, 1, 1, 3, [fine, coarse])), stream())
+    return fine[0]
+
+
+# ---------------------------------------------------------------------------------------------- environment light
+ENV_MAX_RES = 4096  # ENV_MAX_N of csrc/envlight.hip
+ENV_MAX_DIFFUSE_RES = 256  # ENV_MAX_DIFFUSE_N: the diffuse filter is all pairs, 36 N^4 (the light runs it at 16)
+_env_area_cache = {}
+
+
+def cubemap_axis_area(res, device=None, dtype=torch.float32):
+    """The N per-axis factors of the texel solid angle, area(x, y) = axis[x] * axis[y]: with H = N // 2 and x' = |x - H|,
+    axis[x] = atan((x' + 1) / H) - atan(x' / H), and 1 when N == 1.  Computed in float64 (the difference of two fp32 atans loses about
+    log2(N) bits), cached per (N, device) as float32.  This is the formula the reference's environment lights were trained with, kept
+    as it stands: for even N the texels left of the centre get x' = H - x (1..H, not 0..H-1), so the areas are not mirror-symmetric
+    and sum to more than 4 pi (1.08 x at N = 16)."""
+    res = int(res)
+    if res == 1:
+        axis = torch.ones(1, dtype=torch.float64)
+    else:
+        H = res // 2
+        xp = (torch.arange(res, dtype=torch.float64) - H).abs()
+        axis = torch.atan((xp + 1) / H) - torch.atan(xp / H)
+    if device is None:
+        return axis.to(dtype)
+    key = (res, str(torch.device(device)))
+    if key not in _env_area_cache:
+        _env_area_cache[key] = axis.to(torch.float32).to(device)
+    return _env_area_cache[key]
+
+
+def _env_check_map(t, channels, what, max_res=ENV_MAX_RES):
+    if t.dim() != 4 or t.shape[0] != 6 or t.shape[1] != t.shape[2] or t.shape[3] != channels or t.shape[1] < 1:
+        raise ValueError(f"{what}: expected a cube map of shape [6, N, N, {channels}], got {list(t.shape)}")
+    if t.shape[1] > max_res:
+        raise ValueError(f"{what}: face size {t.shape[1]} is above the supported {max_res}")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{what}: expected a float32 tensor, got {t.dtype}")
+
+
+def _env_desc(N, src, dst, area, bounds=None, roughness=1.0, cutoff=0.0):
+    return _lib.EnvDesc(size=ctypes.sizeof(_lib.EnvDesc), N=N, roughness=roughness, costheta_cutoff=cutoff, src=ptr(src), dst=ptr(dst),
+                        bounds=ptr(bounds), area=ptr(area))
+
+
+class _DiffuseCubemap(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cubemap):
+        cubemap = f32c(cubemap)
+        N = cubemap.shape[1]
+        out = torch.empty_like(cubemap)
+        call("a3d_cubemap_diffuse_fwd", ctypes.byref(_env_desc(N, cubemap, out, cubemap_axis_area(N, cubemap.device))), stream())
+        ctx.N = N
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out):
+        g_out = f32c(g_out)
+        g_in = torch.empty_like(g_out)
+        call("a3d_cubemap_diffuse_bwd", ctypes.byref(_env_desc(ctx.N, g_out, g_in, cubemap_axis_area(ctx.N, g_out.device))), stream())
+        return g_in
+
+
+def diffuse_cubemap(cubemap):
+    """The cosine-lobe irradiance filter of a cube map (csrc/envlight.hip), [6,N,N,3] float32 on the GPU -> the same shape; the
+    arithmetic of the reference plugin's diffuse_cubemap (renderutils/ops.py:404-411), restated:
+
+    Texel (x, y) of face f points along d = normalize(cube_to_dir(f, fx, fy)), fx = 2 (x + 0.5) / N - 1, fy = 2 (y + 0.5) / N - 1:
+    face 0 (1,-fy,-fx), 1 (-1,-fy,fx), 2 (fx,1,fy), 3 (fx,-1,-fy), 4 (fx,-fy,1), 5 (-fx,-fy,-1) -- the cube convention of
+    texture(boundary_mode='cube').  area(q) is the texel solid angle of cubemap_axis_area().
+
+        out[p] = sum over ALL 6 N^2 texels q of in[q] * clamp(dot(d_p, d_q), 0, 0.999) * area(q) / pi
+
+    Gradient to the map: g_in[q] = area(q) / pi * sum_p g_out[p] * clamp(dot(d_p, d_q), 0, 0.999), computed as a gather (one lane per
+    q, no atomics): two calls on the same input return the same bits.
+    Every texel is filtered against every texel (36 N^4 pairs), so N <= 256 (ValueError above: mip the map down first, as
+    EnvironmentLight.build_mips does to 16)."""
+    _env_check_map(cubemap, 3, "diffuse_cubemap", ENV_MAX_DIFFUSE_RES)
+    require_device(cubemap, what="diffuse_cubemap")
+    return _DiffuseCubemap.apply(cubemap)
+
+
+def specular_bounds(res, costheta_cutoff, device):
+    """int16 [6,N,N,6,4]: for every output texel p and source face s, (xmin, xmax, ymin, ymax) over the texels q of face s with
+    dot(d_q, d_p) >= costheta_cutoff, and (N-1, 0, N-1, 0) where there is none.  Found by the exhaustive test on the device (a one-off
+    per (N, cutoff)); the directions and the dot are the filter's own, so the table is exact for it."""
+    res = int(res)
+    if not 1 <= res <= 32767:
+        raise ValueError(f"specular_bounds: res must be 1 .. 32767 (the table is int16), got {res}")
+    if not -1.0 <= float(costheta_cutoff) <= 1.0:
+        raise ValueError(f"specular_bounds: costheta_cutoff must be a cosine, got {costheta_cutoff}")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.A3DError(f"specular_bounds: device {device}; the HIP hot path only runs on a ROCm device (no CPU fallback)")
+    with torch.cuda.device(device):
+        bounds = torch.empty((6, res, res, 6, 4), dtype=torch.int16, device=device)
+        call("a3d_cubemap_specular_bounds", ctypes.byref(_env_desc(res, None, None, None, bounds, 1.0, float(costheta_cutoff))), stream())
+    return bounds
+
+
+class _SpecularCubemap(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cubemap, roughness, costheta_cutoff, bounds):
+        cubemap = f32c(cubemap)
+        N = cubemap.shape[1]
+        out = torch.empty((6, N, N, 4), dtype=torch.float32, device=cubemap.device)
+        call("a3d_cubemap_specular_fwd", ctypes.byref(_env_desc(N, cubemap, out, cubemap_axis_area(N, cubemap.device), bounds, roughness,
+                                                                costheta_cutoff)), stream(), tag=f"[N{N}]")
+        ctx.cfg = (N, roughness, costheta_cutoff)
+        ctx.save_for_backward(bounds)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out):
+        N, roughness, costheta_cutoff = ctx.cfg
+        bounds, = ctx.saved_tensors
+        g_out = f32c(g_out)
+        g_in = torch.empty((6, N, N, 3), dtype=torch.float32, device=g_out.device)
+        call("a3d_cubemap_specular_bwd", ctypes.byref(_env_desc(N, g_out, g_in, cubemap_axis_area(N, g_out.device), bounds, roughness,
+                                                                costheta_cutoff)), stream(), tag=f"[N{N}]")
+        return g_in, None, None, None
+
+
+def specular_cubemap_raw(cubemap, roughness, costheta_cutoff, bounds):
+    """The GGX-lobe filter of a cube map (csrc/envlight.hip): [6,N,N,3] float32 on the GPU -> [6,N,N,4] = (weighted colour sum, weight
+    sum); the arithmetic of the reference plugin's specular_cubemap_fwd (renderutils/ops.py:413-425), restated.  Directions and area(q)
+    as in diffuse_cubemap().  With a2 = roughness^4 and c = costheta_cutoff, over all q with dot(d_q, d_p) >= c:
+
+        h = normalize(d_q + d_p),  t = clamp(dot(d_p, h), 0, 1),  D = a2 / (pi * ((t * a2 - t) * t + 1)^2)
+        w = max(dot(d_q, d_p), 0) * D * area(q) / 4,              out[p] = (sum w * in[q], sum w)
+
+    ``bounds`` = specular_bounds(N, c, device): the filter visits the texels inside those rectangles and applies the cone test itself.
+    Gradient to the map only: g_in[q] = sum_p g_out[p][0:3] * w(p, q); channel 3 of g_out is ignored (the weight sum does not depend
+    on the map).  w(p, q) = f(p, q) * area(q) with f and the cone test symmetric in p and q, so the backward is a gather through the
+    same table (one lane per q, no atomics): two calls on the same input return the same bits.
+    fp32 note: at t near 1 the denominator is about a2, so D carries the rounding of t magnified by up to 4 / a2 (1e5 at roughness
+    0.08): a raw value agrees with exact arithmetic to about 1e-2 there.  The magnification is common to both components of a texel,
+    so it cancels in colour / weight, which is what specular_cubemap returns."""
+    _env_check_map(cubemap, 3, "specular_cubemap_raw")
+    N = cubemap.shape[1]
+    if not float(roughness) > 0.0:
+        raise ValueError(f"specular_cubemap_raw: roughness must be positive, got {roughness}")
+    if not -1.0 <= float(costheta_cutoff) <= 1.0:
+        raise ValueError(f"specular_cubemap_raw: costheta_cutoff must be a cosine, got {costheta_cutoff}")
+    if not torch.is_tensor(bounds) or bounds.dtype != torch.int16 or tuple(bounds.shape) != (6, N, N, 6, 4) or not bounds.is_contiguous():
+        raise ValueError(f"specular_cubemap_raw: bounds must be a contiguous int16 tensor of shape [6, {N}, {N}, 6, 4] (specular_bounds)")
+    require_device(cubemap, bounds, what="specular_cubemap_raw")
+    return _SpecularCubemap.apply(cubemap, float(roughness), float(costheta_cutoff), bounds)
+
+
 # ---------------------------------------------------------------------------------------------- mixed precision
 def _amp_wrap_functions():
     """Every autograd.Function of this module runs its forward with autocast OFF on float32 copies of half-precision inputs, and its

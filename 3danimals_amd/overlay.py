@@ -6,7 +6,7 @@ Each replaced reference module keeps its own source and gets ONE line appended a
 
 ``apply`` puts the public names of the mirror module (``3danimals_amd.model...``) on top of the reference module's own: functions
 and classes this package implements replace the reference's, everything it does not implement (``util.save_image``,
-``light.EnvironmentLight``, ``obj.load_obj``, the texture helpers ...) stays the reference's -- the reference's remaining
+``light.load_env``, ``obj.load_obj``, the texture helpers ...) stays the reference's -- the reference's remaining
 ``texture.py`` / ``material.py`` / light-loading code keeps working.  Names the mirror only defines as stand-alone placeholders
 (``_STANDALONE_ONLY`` in the mirror module) are never exported.
 """

@@ -766,6 +766,40 @@ int a3d_texture_bwd(const a3d_tex_desc* desc, const float* g_out, const float* u
 int a3d_texture_mip_fwd(const a3d_tex_desc* desc, a3d_stream_t stream);
 int a3d_texture_mip_bwd(const a3d_tex_desc* desc, a3d_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Environment light -- the split-sum cube-map prefilters behind EnvironmentLight.build_mips (reference model/render/light.py:74-84),
+ * which the reference only has inside its CUDA plugin (renderutils/ops.py:404-458: diffuse_cubemap, specular_cubemap, specular_bounds).
+ * 3danimals_amd/ops.py diffuse_cubemap() / specular_cubemap_raw() state the arithmetic in full.  Maps are [6, N, N, 3]; texel (x, y) of
+ * face f points along normalize(cube_to_dir(f, 2(x+0.5)/N - 1, 2(y+0.5)/N - 1)), the cube convention of the texture sampler above.
+ * area(x, y) = axis(x) * axis(y) is the plugin's texel solid angle; the caller passes the N per-axis factors (`area`, computed in double).
+ *   a3d_cubemap_diffuse_fwd     : dst[p] = sum over ALL q of src[q] * clamp(dot(d_p, d_q), 0, 0.999) * area(q) / pi          ([6,N,N,3])
+ *   a3d_cubemap_diffuse_bwd     : src = g_out [6,N,N,3] -> dst = g_in [6,N,N,3] (its adjoint, as a gather)
+ *   a3d_cubemap_specular_bounds : bounds[p][s] = (xmin, xmax, ymin, ymax) over the texels q of face s with dot(d_q, d_p) >= costheta_cutoff,
+ *                                 (N-1, 0, N-1, 0) when there is none; int16 [6,N,N,6,4]; the exhaustive test (N <= 32767)
+ *   a3d_cubemap_specular_fwd    : dst [6,N,N,4] = (sum w src[q], sum w) over the q inside `bounds` with dot >= costheta_cutoff;
+ *                                 w = max(dot, 0) * D * area(q) / 4, D = a2 / (pi ((t a2 - t) t + 1)^2), a2 = roughness^4,
+ *                                 t = clamp(dot(d_p, normalize(d_q + d_p)), 0, 1)
+ *   a3d_cubemap_specular_bwd    : src = g_out [6,N,N,4] (channel 3 ignored) -> dst = g_in [6,N,N,3], a gather through the same table
+ * Every element of dst / bounds is written; nothing is accumulated and no atomics are used: results are reproducible run to run.
+ * The specular filter needs N <= 4096 (its per-axis tables live in LDS), the diffuse filter N <= 256 (it is all pairs, 36 N^4: larger
+ * maps are refused instead of running for minutes).
+ */
+typedef struct a3d_env_desc {
+    uint32_t size;          /* sizeof(a3d_env_desc) of the caller's header (fields are only ever appended) */
+    int32_t N;              /* face size */
+    float roughness;        /* specular: > 0 */
+    float costheta_cutoff;  /* specular, bounds: cosine of the cone that is kept, -1 .. 1 */
+    const float* src;       /* fwd: the map; bwd: g_out */
+    float* dst;             /* fwd: the filtered map; bwd: g_in */
+    int16_t* bounds;        /* specular: read; bounds: written */
+    const float* area;      /* [N] per-axis solid-angle factors (all but bounds) */
+} a3d_env_desc;
+int a3d_cubemap_diffuse_fwd(const a3d_env_desc* desc, a3d_stream_t stream);
+int a3d_cubemap_diffuse_bwd(const a3d_env_desc* desc, a3d_stream_t stream);
+int a3d_cubemap_specular_bounds(const a3d_env_desc* desc, a3d_stream_t stream);
+int a3d_cubemap_specular_fwd(const a3d_env_desc* desc, a3d_stream_t stream);
+int a3d_cubemap_specular_bwd(const a3d_env_desc* desc, a3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,165 @@
+"""Environment light without a GPU: the ABI surface of csrc/envlight.hip, the descriptor's size check, self-checks of the float64
+restatement (tests/envlight_ref.py) and of its error bound, and the host side of the public API."""
+import ctypes
+import importlib
+import os
+import re
+import sys
+
+import pytest
+import torch
+
+from conftest import ROOT
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import envlight_ref as R  # noqa: E402
+
+ENTRIES = ("a3d_cubemap_diffuse_fwd", "a3d_cubemap_diffuse_bwd", "a3d_cubemap_specular_bounds", "a3d_cubemap_specular_fwd",
+           "a3d_cubemap_specular_bwd")
+CUTOFFS = {0.08: 0.999767, 0.22: 0.986168, 0.36: 0.877280, 0.5: 0.446214, 1.0: 0.015706}  # roughness -> cosine at cutoff 0.99
+
+
+def test_envlight_prototypes_are_declared_bound_and_exported():
+    L = importlib.import_module("3danimals_amd._lib")
+    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "a3d.h")).read(), flags=re.S)
+    for name in ENTRIES:
+        assert re.search(r"\bint\s+%s\s*\(\s*const a3d_env_desc\*\s*desc,\s*a3d_stream_t\s+stream\)" % name, header), name
+        assert L.SIGNATURES[name] == (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]), name
+        assert hasattr(L.lib(), name), name
+    assert L.ABI_VERSION == 404 and len(L.SIGNATURES) == 92
+    body = re.sub(r"/\*.*?\*/", "", re.search(r"typedef struct a3d_env_desc \{(.*?)\} a3d_env_desc;", open(os.path.join(ROOT, "include", "a3d.h")).read(),
+                                             flags=re.S).group(1), flags=re.S)
+    names = [d.strip().split()[-1].lstrip("*") for d in body.split(";") if d.strip()]
+    assert names == [n for n, _ in L.EnvDesc._fields_] and names[0] == "size"
+    assert ctypes.sizeof(L.EnvDesc) == 16 + 4 * 8
+
+
+def test_a_short_env_desc_is_refused_before_anything_is_launched():
+    """A descriptor shorter than the library's is refused with A3D_EINVAL by all five entry points before a pointer is touched (none of
+    the pointers below is ever dereferenced; no GPU needed)."""
+    L = importlib.import_module("3danimals_amd._lib")
+    lib = L.lib()
+    fake = 0x1000
+    d = L.EnvDesc(size=ctypes.sizeof(L.EnvDesc) - 4, N=4, roughness=0.5, costheta_cutoff=0.5, src=fake, dst=fake, bounds=fake, area=fake)
+    for name in ENTRIES:
+        assert getattr(lib, name)(ctypes.byref(d), None) == -1, name
+        msg = lib.a3d_last_error().decode()
+        assert "size" in msg and "invalid argument" in msg and name in msg, (name, msg)
+    # the all-pairs diffuse filter refuses a size it would run for minutes on
+    d.size, d.N = ctypes.sizeof(L.EnvDesc), 257
+    for name in ENTRIES[:2]:
+        assert getattr(lib, name)(ctypes.byref(d), None) == -1 and "N = 257, must be 1 .. 256" in lib.a3d_last_error().decode(), name
+    # a full-size descriptor with a face size outside the range is refused too
+    d.size, d.N = ctypes.sizeof(L.EnvDesc), 40000
+    for name in ENTRIES:
+        assert getattr(lib, name)(ctypes.byref(d), None) == -1 and "N = 40000" in lib.a3d_last_error().decode(), name
+
+
+def test_cutoff_rule_reproduces_the_recorded_cosines():
+    ru_ops = importlib.import_module("3danimals_amd.model.render.renderutils.ops")
+    for r, want in CUTOFFS.items():
+        assert R.cutoff_cosine(r) == pytest.approx(want, abs=1e-6), r
+        assert ru_ops.ndf_cutoff_cosine(r, 0.99) == pytest.approx(R.cutoff_cosine(r), abs=1e-12), r
+
+
+def test_axis_area_matches_the_restatement():
+    ops = importlib.import_module("3danimals_amd.ops")
+    for N in (1, 2, 5, 16, 512):
+        assert torch.equal(ops.cubemap_axis_area(N, dtype=torch.float64), R.axis_area(N)), N
+
+
+def test_constant_map_diffuse_is_k_times_S_and_S_is_not_one():
+    """The texel solid angles of the specification do not sum to 4 pi: a constant map k comes out as k * S[p] with S in these ranges."""
+    for N, lo, hi in ((8, 0.923, 1.045), (16, 1.046, 1.116), (32, 1.109, 1.151)):
+        S = R.diffuse(torch.ones(6, N, N, 3, dtype=torch.float64))
+        assert float(S.min()) == pytest.approx(lo, abs=1e-3) and float(S.max()) == pytest.approx(hi, abs=1e-3), (N, float(S.min()), float(S.max()))
+        assert torch.allclose(R.diffuse(torch.full((6, N, N, 3), 2.5, dtype=torch.float64)), 2.5 * S, rtol=1e-13, atol=0)
+
+
+def test_constant_map_specular_colour_over_weight_is_the_constant():
+    for r in (0.08, 0.36, 1.0):
+        raw = R.specular_raw(torch.full((6, 8, 8, 3), 1.75, dtype=torch.float64), r, R.cutoff_cosine(r))
+        assert float(raw[..., 3].min()) > 0
+        assert torch.allclose(raw[..., :3] / raw[..., 3:], torch.full((6, 8, 8, 3), 1.75, dtype=torch.float64), rtol=1e-13, atol=0)
+
+
+def test_restatement_gradient_is_the_transposed_filter():
+    g = torch.Generator().manual_seed(3)
+    x = (torch.rand(6, 8, 8, 3, generator=g, dtype=torch.float64) * 4).requires_grad_(True)
+    go = torch.randn(6, 8, 8, 4, generator=g, dtype=torch.float64)
+    c = R.cutoff_cosine(0.36)
+    gx, = torch.autograd.grad(R.specular_raw(x, 0.36, c), x, go)
+    assert torch.allclose(gx, R.specular_terms(go[..., :3], 0.36, c, transpose=True)[0], rtol=1e-12, atol=1e-14)
+    gd, = torch.autograd.grad(R.diffuse(x), x, go[..., :3])
+    assert torch.allclose(gd, R.diffuse_terms(go[..., :3], transpose=True)[0], rtol=1e-12, atol=1e-14)
+
+
+@pytest.mark.parametrize("roughness", [0.08, 0.22, 0.36, 0.5, 1.0])
+def test_bound_catches_one_dropped_pair_of_median_weight(roughness):
+    """The fp32 bound of R.specular_terms / R.diffuse_terms is tight enough that an output missing ONE in-cone pair of median weight
+    breaks it (N = 16, one output at a face centre, an edge and a corner each)."""
+    N = 16
+    g = torch.Generator().manual_seed(11)
+    x = torch.rand(6, N, N, 3, generator=g, dtype=torch.float64) * 4 + 0.5
+    c = R.cutoff_cosine(roughness)
+    _, bound, _, _ = R.specular_terms(x, roughness, c)
+    _, dbound = R.diffuse_terms(x)
+    flat = x.reshape(-1, 3)
+    for p in (8 * N + 8, 0, 2 * N * N + 15):
+        dot, w = R.specular_pairs(N, roughness, c, slice(p, p + 1))[:2]
+        inside = torch.nonzero((dot[0] >= c) & (w[0] > 0))[:, 0]
+        q = inside[w[0, inside].argsort()[len(inside) // 2]]
+        assert bool((w[0, q] * flat[q] > bound.reshape(-1, 3)[p]).all()), (roughness, p, float(w[0, q]), bound.reshape(-1, 3)[p])
+        wd = R.diffuse_weights(N, slice(p, p + 1))[0]
+        pos = torch.nonzero(wd > 0)[:, 0]
+        qd = pos[wd[pos].argsort()[len(pos) // 2]]
+        assert bool((wd[qd] * flat[qd] > dbound.reshape(-1, 3)[p]).all()), (p, float(wd[qd]))
+
+
+def test_cpu_tensors_raise_and_the_light_constructs_on_the_cpu():
+    L = importlib.import_module("3danimals_amd._lib")
+    ops = importlib.import_module("3danimals_amd.ops")
+    ru = importlib.import_module("3danimals_amd.model.render.renderutils")
+    light = importlib.import_module("3danimals_amd.model.render.light")
+    with pytest.raises(L.A3DError, match="no CPU fallback"):
+        ru.diffuse_cubemap(torch.zeros(6, 4, 4, 3))
+    with pytest.raises(L.A3DError, match="no CPU fallback"):
+        ru.specular_cubemap(torch.zeros(6, 4, 4, 3), 0.5)
+    with pytest.raises(L.A3DError, match="no CPU fallback"):
+        ops.specular_bounds(4, 0.5, "cpu")
+    for bad in (torch.zeros(6, 4, 3, 3), torch.zeros(5, 4, 4, 3), torch.zeros(6, 4, 4, 4), torch.zeros(6, 4, 4, 3, dtype=torch.float64)):
+        with pytest.raises(ValueError):
+            ops.diffuse_cubemap(bad)
+        with pytest.raises(ValueError):
+            ops.specular_cubemap_raw(bad, 0.5, 0.5, torch.zeros(6, 4, 4, 6, 4, dtype=torch.int16))
+    with pytest.raises(ValueError):
+        ops.specular_cubemap_raw(torch.zeros(6, 4, 4, 3), 0.5, 0.5, torch.zeros(6, 4, 4, 24, dtype=torch.float32))
+    with pytest.raises(ValueError, match="above the supported 256"):
+        ops.diffuse_cubemap(torch.zeros(6, 257, 257, 3))
+    ru_ops = importlib.import_module("3danimals_amd.model.render.renderutils.ops")
+    ru_ops.clear_specular_cache()
+    for i in range(ru_ops.NDF_CACHE_SIZE + 5):  # the caches keep the most recently used entries only
+        ru_ops._lru(ru_ops._ndf_cutoff_cache, (0.1 + i, 0.99), lambda: 0.5)
+    assert len(ru_ops._ndf_cutoff_cache) == ru_ops.NDF_CACHE_SIZE and (0.1, 0.99) not in ru_ops._ndf_cutoff_cache
+    ru_ops.clear_specular_cache()
+    assert "EnvironmentLight" not in getattr(light, "_STANDALONE_ONLY", ())
+    base = torch.rand(6, 8, 8, 3)
+    lgt = light.EnvironmentLight(base)
+    assert isinstance(lgt, torch.nn.Module) and lgt.env_base is lgt.base and set(lgt.state_dict()) == {"base", "env_base"}  # (as in the reference)
+    assert len(list(lgt.parameters())) == 1 and lgt.base.requires_grad
+    white = base.mean(-1, keepdim=True)
+    assert float(lgt.regularizer()) == pytest.approx(float((base - white).abs().mean()), rel=1e-6)
+    assert torch.equal(lgt.clone().base, lgt.base) and lgt.clone().base is not lgt.base
+    lgt.specular = [None] * 4
+    assert torch.allclose(lgt.get_mip(torch.tensor([0.0, 0.08, 0.29, 0.5, 0.75, 1.0])), torch.tensor([0.0, 0.0, 1.0, 2.0, 2.5, 3.0]))
+
+
+def test_fg_table_is_a_split_sum_table():
+    """light.fg_table in float64 on the CPU against the restatement's sample-by-sample evaluation; 0 <= A, B and A + B <= 1."""
+    light = importlib.import_module("3danimals_amd.model.render.light")
+    want = R.fg_table()
+    got = light.fg_table("cpu", torch.float64)
+    assert got.shape == (1, 256, 256, 2) and torch.allclose(got, want, rtol=1e-12, atol=1e-14)
+    assert float(want.min()) >= 0 and float(want.sum(-1).max()) <= 1 + 1e-9
+    assert float(want[0, 0, -1].sum()) == pytest.approx(1.0, abs=1e-3)  # smooth surface seen head-on reflects everything
+    assert float(want[0, -1, 0, 1]) < 0.5 and float(want[0, 0, 0, 1]) > float(want[0, 0, -1, 1])  # the Fresnel bias grows towards grazing angles
