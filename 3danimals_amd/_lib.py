@@ -1,4 +1,4 @@
-"""ctypes binding of liba3d_hip.so (include/a3d.h).  No fallback: if the library is missing we say so and stop."""
+"""ctypes binding of liba3d_hip.so (include/a3d.h, include/a3d_bsdf.h).  No fallback: if the library is missing we say so and stop."""
 from __future__ import annotations
 
 import ctypes
@@ -197,6 +197,26 @@ class EnvDesc(ctypes.Structure):
                 ("dst", _p), ("bounds", _p), ("area", _p)]
 
 
+class BsdfDesc(ctypes.Structure):
+    """a3d_bsdf_desc of include/a3d_bsdf.h (field for field; tests/test_bsdf_cpu.py compares the two)."""
+
+    _fields_ = [("size", ctypes.c_uint32), ("op", ctypes.c_int32), ("variant", ctypes.c_int32), ("min_roughness", ctypes.c_float),
+                ("ndim", ctypes.c_int32), ("reserved", ctypes.c_int32), ("shape", ctypes.c_int64 * 4), ("seg", ctypes.c_int64), ("in", _p * 6),
+                ("stride", ctypes.c_int64 * 24), ("cstride", ctypes.c_int64 * 6), ("out", _p), ("scratch", _p), ("g_out", _p),
+                ("g_mode", ctypes.c_int32 * 6), ("seg_div", ctypes.c_int64 * 6), ("g_in", _p * 6), ("g_final", _p * 6)]
+
+
+# the entry points of include/a3d_bsdf.h (same library, same a3d_version(); tests/test_bsdf_cpu.py checks this table against that header)
+BSDF_SIGNATURES = {
+    "a3d_bsdf_rows": (ctypes.c_int64, [_p]),
+    "a3d_bsdf_fwd": (_c_int, [_p, _p]),
+    "a3d_bsdf_bwd": (_c_int, [_p, _p]),
+    "a3d_image_loss_fwd": (_c_int, [_p, _p]),
+    "a3d_image_loss_bwd": (_c_int, [_p, _p]),
+}
+BSDF_TILE = 1024  # A3D_BSDF_TILE
+BSDF_MAX_DIMS = 4  # A3D_BSDF_MAX_DIMS
+
 ABI_VERSION = 404  # a3d_version() of the library these signatures belong to (include/a3d.h)
 _lib = None
 
@@ -215,7 +235,7 @@ def lib():
                 "(or __graft_entry__.build()).  There is no CPU fallback for the HIP hot path."
             )
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(BSDF_SIGNATURES.items()):
             fn = getattr(handle, name)  # AttributeError here == ABI drift
             fn.restype, fn.argtypes = res, args
         if handle.a3d_version() != ABI_VERSION:  # same symbols, other argument lists: a stale build must not be called

@@ -2334,6 +2334,253 @@ def specular_cubemap_raw(cubemap, roughness, costheta_cutoff, bounds):
     return _SpecularCubemap.apply(cubemap, float(roughness), float(costheta_cutoff), bounds)
 
 
+# ---------------------------------------------------------------------------------------------- shading BSDFs, HDR image loss
+BSDF_OPS = {"lambert": (0, (3, 3), 1), "frostbite_diffuse": (1, (3, 3, 3, 1), 1), "pbr_specular": (2, (3, 3, 3, 3, 1), 3),
+            "pbr_bsdf": (3, (3, 3, 3, 3, 3, 3), 3), "image_loss": (4, (1, 1), 1)}  # name -> (A3D_BSDF_* code, channels per input, of the result)
+IMAGE_LOSSES = {"l1": 0, "mse": 1, "smape": 2, "relmse": 3}
+BSDF_MIN_RUN = 256  # a gradient is reduced inside the launch when its input is constant over runs of at least this many pixels
+
+
+class _BsdfPlan:
+    """How a broadcast element-wise call is handed to the library: the leading shape of the result with neighbouring dimensions merged
+    where every input allows it, per input the element strides along those dimensions (0 = broadcast) and the channel stride, and the
+    segment length: the shortest run of pixels over which an outer-broadcast input ([B,1,1,3], [1,1,1,3]) is constant."""
+
+    _geometry = {}  # (name, shapes, strides) -> the plan's geometry: a training loop calls with the same few layouts every step
+
+    def __init__(self, name, inputs):
+        self.code, chans, self.c_out = BSDF_OPS[name]
+        self.inputs, self.chans = inputs, chans
+        key = (name, tuple((t.shape, t.stride()) for t in inputs))
+        geo = self._geometry.get(key)
+        if geo is None:
+            if len(self._geometry) > 256:
+                self._geometry.clear()
+            geo = self._geometry[key] = self._plan(name, inputs, chans)
+        self.lead, self.shape, self.strides, self.cstrides, self.n, self.run, self.seg = geo
+
+    @staticmethod
+    def _plan(name, inputs, chans):
+        assert len(inputs) == len(chans)
+        for t, c in zip(inputs, chans):
+            if t.dim() < 1 or t.shape[-1] not in (1, c):
+                raise ValueError(f"{name}: the last dimension of an input must be {c} (or 1), got shape {list(t.shape)}")
+        lead = tuple(torch.broadcast_shapes(*[t.shape[:-1] for t in inputs]))
+        nd = len(lead)
+        strides, bcast = [], []  # per input and leading dimension: element stride (0 where the input has size 1), and "has size 1 there"
+        for t in inputs:
+            pad = nd - (t.dim() - 1)
+            one = [d < pad or t.shape[d - pad] == 1 for d in range(nd)]
+            bcast.append(one)
+            strides.append([0 if one[d] else t.stride(d - pad) for d in range(nd)])
+        # drop dimensions of size 1; merge dimension d into d - 1 where, for every input, stride[d - 1] == stride[d] * size[d] AND the
+        # input is broadcast (size 1) along both or along neither: the gradient of an input follows its SHAPE, not its strides -- a
+        # light.expand(B, 1, 1, 3) has stride 0 along B too, but wants B rows of gradient
+        shape, st, bc = [], [[] for _ in inputs], [[] for _ in inputs]
+        for d in range(nd):
+            n = lead[d]
+            if n == 1:
+                continue
+            if shape and all(s[-1] == strides[i][d] * n and bc[i][-1] == bcast[i][d] for i, s in enumerate(st)):
+                shape[-1] *= n
+                for i, s in enumerate(st):
+                    s[-1] = strides[i][d]
+            else:
+                shape.append(n)
+                for i, s in enumerate(st):
+                    s.append(strides[i][d])
+                    bc[i].append(bcast[i][d])
+        if not shape:
+            shape, st, bc = [1], [[0] for _ in inputs], [[False] for _ in inputs]
+        if len(shape) > _lib.BSDF_MAX_DIMS:
+            raise _lib.A3DError(f"{name}: the inputs' strides leave {len(shape)} leading dimensions that cannot be merged; at most "
+                                f"{_lib.BSDF_MAX_DIMS} are supported (make the most irregular input contiguous)")
+        cstrides = [0 if t.shape[-1] == 1 else t.stride(-1) for t in inputs]
+        n = math.prod(shape)
+        # run[i]: pixels over which input i is constant because it has SIZE 1 along a trailing block of dimensions (and only there), else None
+        run = []
+        for b in bc:
+            k = len(shape)
+            while k > 0 and b[k - 1]:
+                k -= 1
+            r = math.prod(shape[k:])
+            run.append(r if (k < len(shape) and not any(b[:k]) and r >= BSDF_MIN_RUN) else None)
+        runs = [r for r in run if r]
+        return lead, shape, st, cstrides, n, run, (min(runs) if runs else max(n, 1))
+
+    def desc(self):
+        d = _lib.BsdfDesc(size=ctypes.sizeof(_lib.BsdfDesc), op=self.code, ndim=len(self.shape), seg=self.seg)
+        for j, n in enumerate(self.shape):
+            d.shape[j] = n
+        for i, t in enumerate(self.inputs):
+            getattr(d, "in")[i] = t.data_ptr()
+            d.cstride[i] = self.cstrides[i]
+            for j, s in enumerate(self.strides[i]):
+                d.stride[4 * i + j] = s
+        return d
+
+    def rows(self):
+        return (self.n // self.seg) * (-(-self.seg // _lib.BSDF_TILE))
+
+    def grads(self, d, needs, device):
+        """Gradient buffers for the inputs that want one, set into the descriptor -> a function that turns them into the tensors autograd
+        expects once the call has been enqueued."""
+        finish = []
+        for i, (t, c) in enumerate(zip(self.inputs, self.chans)):
+            if not needs[i]:
+                finish.append(None)
+                continue
+            if self.run[i]:  # constant over runs: partial rows + the finishing launch
+                rows = torch.empty((self.rows(), c), dtype=torch.float64, device=device)  # (the sums are carried in double)
+                final = torch.empty((self.n // self.run[i], c), dtype=torch.float32, device=device)
+                d.g_mode[i], d.seg_div[i], d.g_in[i], d.g_final[i] = 2, self.run[i] // self.seg, rows.data_ptr(), final.data_ptr()
+                finish.append((final, rows))
+            else:  # one row per pixel; any other broadcast pattern (inner dimensions, [1,H,W,3]) is summed by torch afterwards
+                g = torch.empty((self.n, c), dtype=torch.float32, device=device)
+                d.g_mode[i], d.g_in[i] = 1, g.data_ptr()
+                finish.append((g, None))
+
+        def collect():
+            out = []
+            for i, (t, c) in enumerate(zip(self.inputs, self.chans)):
+                if finish[i] is None:
+                    out.append(None)
+                    continue
+                g, rows = finish[i]
+                if rows is None:
+                    pad = (1,) * (len(self.lead) - (t.dim() - 1))
+                    g = g.view(*self.lead, c).sum_to_size(*pad, *t.shape[:-1], t.shape[-1])
+                elif t.shape[-1] != c:
+                    g = g.sum(-1, keepdim=True)
+                out.append(g.reshape(t.shape))
+            return out
+
+        return collect
+
+
+class _Bsdf(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, name, min_roughness, lobe, *inputs):
+        plan = _BsdfPlan(name, inputs)
+        out = torch.empty((*plan.lead, plan.c_out), dtype=torch.float32, device=inputs[0].device)
+        if plan.n:
+            d = plan.desc()
+            d.variant, d.min_roughness, d.out = lobe, min_roughness, out.data_ptr()
+            call("a3d_bsdf_fwd", ctypes.byref(d), stream(), tag=f"[{name}]")
+        ctx.cfg = (name, min_roughness, lobe)
+        ctx.save_for_backward(*inputs)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out):
+        name, min_roughness, lobe = ctx.cfg
+        inputs = ctx.saved_tensors
+        plan = _BsdfPlan(name, inputs)
+        needs = ctx.needs_input_grad[3:]
+        if not plan.n:
+            return (None, None, None) + tuple(torch.zeros_like(t) if n else None for t, n in zip(inputs, needs))
+        g_out = f32c(g_out)
+        d = plan.desc()
+        d.variant, d.min_roughness, d.g_out = lobe, min_roughness, g_out.data_ptr()
+        collect = plan.grads(d, needs, g_out.device)
+        call("a3d_bsdf_bwd", ctypes.byref(d), stream(), tag=f"[{name}]")
+        return (None, None, None) + tuple(collect())
+
+
+def bsdf(name, inputs, min_roughness=0.08, lobe=0):
+    """lambert / frostbite_diffuse / pbr_specular / pbr_bsdf of renderutils as ONE launch forward and one backward (csrc/bsdf.hip,
+    include/a3d_bsdf.h); the arithmetic is the torch twin's of model/render/renderutils/ops.py, operation by operation.
+
+    ``inputs``: float32 tensors on the GPU in the reference's argument order, [..., 3] (or [..., 1] for linearRoughness / alpha),
+    broadcastable against each other in every leading dimension; any strides.  Nothing is expanded: the kernels read through strides.
+    Returns [..., 1] (lambert, frostbite_diffuse) or [..., 3] in the broadcast leading shape.
+    Gradients: every input that requires one gets it, in its own shape (zeros included).  An input that is broadcast along trailing
+    leading dimensions only ([B,1,1,3], [1,1,1,3]: camera, light, a constant colour) has its gradient summed inside the launch
+    (registers -> wave -> work-group -> one partial row per work-group, then a finishing launch over the rows; no atomics, bit-identical
+    run to run); any other broadcast pattern gets one row per pixel from the launch and a torch sum afterwards."""
+    inputs = tuple(inputs)
+    for t in inputs:
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name}: expected float32 tensors, got {t.dtype}")
+    require_device(*inputs, what=name)
+    return _Bsdf.apply(name, float(min_roughness), int(lobe), *inputs)
+
+
+def _flat_loss_desc(img, target):
+    """The descriptor of image_loss for two contiguous images of one shape, written down directly (one dimension of n elements, unit
+    strides): the common call, and one whose kernels take tens of microseconds -- the general plan would cost as much again."""
+    n = img.numel()
+    d = _lib.BsdfDesc(size=ctypes.sizeof(_lib.BsdfDesc), op=4, ndim=1, seg=n)
+    d.shape[0] = n
+    ins = getattr(d, "in")
+    ins[0], ins[1] = img.data_ptr(), target.data_ptr()
+    d.stride[0] = d.stride[4] = d.cstride[0] = d.cstride[1] = 1
+    return d, n
+
+
+class _ImageLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, img, target, variant):
+        flat = img.shape == target.shape and img.is_contiguous() and target.is_contiguous()
+        if flat:
+            d, n = _flat_loss_desc(img, target)
+            rows = -(-n // _lib.BSDF_TILE)
+        else:
+            plan = _BsdfPlan("image_loss", (img.unsqueeze(-1), target.unsqueeze(-1)))
+            d, rows = plan.desc(), plan.rows()
+        out = torch.empty((), dtype=torch.float32, device=img.device)
+        scratch = torch.empty((rows,), dtype=torch.float64, device=img.device)
+        d.variant, d.out, d.scratch = variant, out.data_ptr(), scratch.data_ptr()
+        call("a3d_image_loss_fwd", ctypes.byref(d), stream(), tag=_LOSS_TAGS[variant])
+        ctx.variant, ctx.flat = variant, flat
+        ctx.save_for_backward(img, target)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out):
+        img, target = ctx.saved_tensors
+        g_out = f32c(g_out)
+        if ctx.flat:
+            d, _ = _flat_loss_desc(img, target)
+            d.variant, d.g_out = ctx.variant, g_out.data_ptr()
+            gi = gt = None
+            if ctx.needs_input_grad[0]:
+                gi = torch.empty_like(img)
+                d.g_mode[0], d.g_in[0] = 1, gi.data_ptr()
+            if ctx.needs_input_grad[1]:
+                gt = torch.empty_like(target)
+                d.g_mode[1], d.g_in[1] = 1, gt.data_ptr()
+            call("a3d_image_loss_bwd", ctypes.byref(d), stream(), tag=_LOSS_TAGS[ctx.variant])
+            return gi, gt, None
+        plan = _BsdfPlan("image_loss", (img.unsqueeze(-1), target.unsqueeze(-1)))
+        d = plan.desc()
+        d.variant, d.g_out = ctx.variant, g_out.data_ptr()
+        collect = plan.grads(d, ctx.needs_input_grad[:2], g_out.device)
+        call("a3d_image_loss_bwd", ctypes.byref(d), stream(), tag=_LOSS_TAGS[ctx.variant])
+        gi, gt = collect()
+        return (None if gi is None else gi.squeeze(-1)), (None if gt is None else gt.squeeze(-1)), None
+
+
+_LOSS_TAGS = [f"[{v}]" for v in range(8)]
+
+
+def image_loss(img, target, loss="l1", tonemapper="none"):
+    """The HDR image loss of renderutils as a scalar (the mean over all elements), csrc/bsdf.hip: 'l1' | 'mse' | 'smape' | 'relmse'
+    (any other name is l1, as in the reference), after the optional tone map 'log_srgb' = srgb(log(clamp(x, 0, 65535) + 1)).  The forward
+    sums per work-group and finishes over the partial sums in a fixed order (no atomics); the backward is element-wise.  img and target
+    are float32 on the GPU, broadcastable against each other, any strides."""
+    if img.dtype != torch.float32 or target.dtype != torch.float32:
+        raise ValueError(f"image_loss: expected float32 tensors, got {img.dtype} and {target.dtype}")
+    require_device(img, target, what="image_loss")
+    if img.dim() == 0 or target.dim() == 0:
+        img, target = img.reshape(-1) if img.dim() == 0 else img, target.reshape(-1) if target.dim() == 0 else target
+    if img.numel() == 0 or target.numel() == 0:
+        return (img * target).mean()  # (the mean of nothing: nan, as torch's)
+    return _ImageLoss.apply(img, target, IMAGE_LOSSES.get(loss, 0) + 4 * (tonemapper == "log_srgb"))
+
+
 # ---------------------------------------------------------------------------------------------- mixed precision
 def _amp_wrap_functions():
     """Every autograd.Function of this module runs its forward with autocast OFF on float32 copies of half-precision inputs, and its
