@@ -1,4 +1,4 @@
-"""ctypes binding of liba3d_hip.so (include/a3d.h, include/a3d_bsdf.h).  No fallback: if the library is missing we say so and stop."""
+"""ctypes binding of liba3d_hip.so (include/a3d.h, include/a3d_bsdf.h, include/a3d_deriv.h).  No fallback: if the library is missing we say so and stop."""
 from __future__ import annotations
 
 import ctypes
@@ -217,6 +217,15 @@ BSDF_SIGNATURES = {
 BSDF_TILE = 1024  # A3D_BSDF_TILE
 BSDF_MAX_DIMS = 4  # A3D_BSDF_MAX_DIMS
 
+# the entry points of include/a3d_deriv.h (same library, same a3d_version(); tests/test_deriv_cpu.py checks this table against that header)
+DERIV_SIGNATURES = {
+    "a3d_rast_db_fwd": (_c_int, [_p, _c_int, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p]),
+    "a3d_rast_db_bwd": (_c_int, [_p, _p, _c_int, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p]),
+    "a3d_interp_da_fwd": (_c_int, [_p, _c_int, _c_int, _p, _c_int, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p]),
+    "a3d_interp_da_bwd": (_c_int, [_p, _p, _c_int, _c_int, _p, _c_int, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _p]),
+}
+DERIV_MAX_SELECTED = 64  # A3D_DERIV_MAX_SELECTED
+
 ABI_VERSION = 404  # a3d_version() of the library these signatures belong to (include/a3d.h)
 _lib = None
 
@@ -235,7 +244,7 @@ def lib():
                 "(or __graft_entry__.build()).  There is no CPU fallback for the HIP hot path."
             )
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(BSDF_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(BSDF_SIGNATURES.items()) + list(DERIV_SIGNATURES.items()):
             fn = getattr(handle, name)  # AttributeError here == ABI drift
             fn.restype, fn.argtypes = res, args
         if handle.a3d_version() != ABI_VERSION:  # same symbols, other argument lists: a stale build must not be called

@@ -101,9 +101,10 @@ struct TileScatter {
     __device__ __forceinline__ void link(int e, int s) const { e_next[e] = atomicExch(&head[s], e); }
     // after a barrier: G lanes per claimed slot (lane = column) walk the slot's list and add the row's sum to g[row * stride + c] as
     // adjacent atomics; two lists in flight per group so that the hops (one LDS round trip each) overlap.  ``skip`` = a column never
-    // written.  Contains a barrier.
+    // written.  ``col_map`` (optional): staged column c is added to column col_map[c] of the row (a3d_interp_da_bwd stages the SELECTED
+    // channels only).  Contains a barrier.
     template <int G>
-    __device__ __forceinline__ void flush(float* __restrict__ g, int stride, int skip) const {
+    __device__ __forceinline__ void flush(float* __restrict__ g, int stride, int skip, const int* __restrict__ col_map = nullptr) const {
         // the claimed slots, compacted (ballot + one counter update per wave): ~50 of the 512 at the bench mesh -- walking all of them
         // was 6 of a work-group's 11 us
         for (int s = threadIdx.x; s < TS_SLOTS; s += blockDim.x) {
@@ -117,6 +118,7 @@ struct TileScatter {
         __syncthreads();
         const int n_used = n[1], c = threadIdx.x & (G - 1), groups = blockDim.x / G;
         const bool on = c < C && c != skip;
+        const int col = (col_map && c < C) ? col_map[c] : c;
         for (int j = threadIdx.x / G; j < n_used; j += 2 * groups) {
             const int sa = used[j], sb = j + groups < n_used ? used[j + groups] : -1;
             int ea = head[sa], eb = sb >= 0 ? head[sb] : -1;
@@ -125,8 +127,8 @@ struct TileScatter {
                 if (ea >= 0) { const float v = c < C ? e_val[ea * C + c] : 0.f; ea = e_next[ea]; sum_a += v; }
                 if (eb >= 0) { const float v = c < C ? e_val[eb * C + c] : 0.f; eb = e_next[eb]; sum_b += v; }
             }
-            if (on && sum_a != 0.f) atomicAdd(g + (long long)key[sa] * stride + c, sum_a);
-            if (on && sb >= 0 && sum_b != 0.f) atomicAdd(g + (long long)key[sb] * stride + c, sum_b);
+            if (on && sum_a != 0.f) atomicAdd(g + (long long)key[sa] * stride + col, sum_a);
+            if (on && sb >= 0 && sum_b != 0.f) atomicAdd(g + (long long)key[sb] * stride + col, sum_b);
         }
     }
     static size_t lds_bytes(int C) { return sizeof(int) * (3 * TS_SLOTS + 4 + TS_ENTRIES) + sizeof(float) * TS_ENTRIES * (size_t)C; }

@@ -1086,10 +1086,59 @@ def rasterize(clip, tri, resolution, batch=None, prev=None, normals_job=None, de
     return _Rasterize.apply(clip, tri_int32(tri), B, int(resolution[0]), int(resolution[1]), prev, normals_job, defer_resolve)
 
 
+def _deriv_on_gpu(*tensors):
+    """The derivative kernels take CUDA float32 tensors; anything else (CPU, float64 ...) goes to the torch statement."""
+    return all(t.is_cuda and t.dtype == torch.float32 for t in tensors)
+
+
+class _RasterizeDb(torch.autograd.Function):
+    """a3d_rast_db_fwd / a3d_rast_db_bwd (csrc/deriv.hip): one launch each way.  ``rast`` receives no gradient (it only names the
+    triangle).  A backward under create_graph=True (double backward) differentiates the torch statement instead."""
+
+    @staticmethod
+    def forward(ctx, clip, tri32, rast):
+        require_device(clip, tri32, rast, what="rasterize_db")
+        ensure_resolved(rast)
+        clip_c, rast_c = f32c(clip), f32c(rast)
+        B, H, W = rast_c.shape[:3]
+        assert clip_c.dim() == 3 and clip_c.shape[0] in (1, B) and clip_c.shape[2] == 4 and rast_c.shape[3] == 4
+        db = torch.empty((B, H, W, 4), dtype=torch.float32, device=rast_c.device)
+        call("a3d_rast_db_fwd", ptr(clip_c), clip_c.shape[0], ptr(tri32), ptr(rast_c), B, clip_c.shape[1], tri32.shape[0], H, W, ptr(db), stream())
+        ctx.save_for_backward(clip, tri32, rast_c)
+        return db
+
+    @staticmethod
+    def backward(ctx, g_db):
+        clip, tri32, rast = ctx.saved_tensors
+        if torch.is_grad_enabled():  # double backward: the torch statement, differentiated by autograd
+            with torch.enable_grad():
+                (g_clip,) = torch.autograd.grad(_rasterize_db_torch(clip, tri32, rast), clip, g_db, create_graph=True)
+            return g_clip, None, None
+        clip_c = f32c(clip)
+        B, H, W = rast.shape[:3]
+        g_clip = torch.empty_like(clip_c)
+        call("a3d_rast_db_bwd", ptr(f32h(g_db)), ptr(clip_c), clip_c.shape[0], ptr(tri32), ptr(rast), B, clip_c.shape[1], tri32.shape[0], H, W,
+             ptr(g_clip), stream())
+        return g_clip, None, None
+
+
 def rasterize_db(clip, tri, rast):
     """rast_db [B,H,W,4] = (du/dX, du/dY, dv/dX, dv/dY) per pixel: the image-space derivatives of the perspective-correct
-    barycentrics of the stored triangle, from the definition u = a0/s, a_i = q_j x q_k, q_i = p_i.xy - f p_i.w (torch ops, so they are
-    differentiable w.r.t. clip like nvdiffrast's; nothing on the training path consumes them: render.py:24 passes rast_db=None)."""
+    barycentrics of the stored triangle, from the definition u = a0/s, a_i = q_j x q_k, q_i = p_i.xy - f p_i.w; differentiable w.r.t.
+    clip like nvdiffrast's (grad_db).  CUDA float32 tensors: one HIP launch each way (a3d_rast_db_fwd / _bwd, csrc/deriv.hip; a pixel
+    whose triangle is exactly edge-on at the pixel centre, s == 0, which the rasteriser never stores, gets zeros); anything else --
+    CPU tensors, float64, a double backward -- evaluates the torch statement _rasterize_db_torch, which is also the specification.
+    Nothing on the training path consumes it (render.py:24 passes rast_db=None)."""
+    if clip.dim() == 2:
+        clip = clip[None]
+    if _deriv_on_gpu(clip, rast) and tri.is_cuda:
+        return _RasterizeDb.apply(clip, tri_int32(tri), rast)
+    return _rasterize_db_torch(clip, tri, rast)
+
+
+def _rasterize_db_torch(clip, tri, rast):
+    """rasterize_db as torch operations (about 30 launches over [B,H,W,3,4] gathers): the statement the kernels follow operation by
+    operation, the path of CPU / float64 tensors and of a double backward, and what tests and tools/bench_deriv.py compare against."""
     B, H, W, _ = rast.shape
     ensure_resolved(rast)
     ids = rast[..., 3].long() - 1
@@ -1147,9 +1196,79 @@ def interpolate(attr, rast, tri):
     return _Interpolate.apply(attr, rast, tri_int32(tri))
 
 
+def _selected(diff_attrs, C):
+    """'all' -> None; a list of attribute indices (repeats allowed, negative = from the end) -> tuple of channels in [0, C)."""
+    if isinstance(diff_attrs, str):
+        if diff_attrs != "all":
+            raise ValueError(f"diff_attrs must be 'all' or a list of attribute indices, not {diff_attrs!r}")
+        return None
+    sel = tuple(int(i) for i in (diff_attrs.tolist() if torch.is_tensor(diff_attrs) else diff_attrs))
+    if any(i < -C or i >= C for i in sel):
+        raise IndexError(f"diff_attrs {list(sel)} out of range for {C} attributes")
+    return tuple(i % C for i in sel)
+
+
+class _InterpolateDa(torch.autograd.Function):
+    """a3d_interp_da_fwd / a3d_interp_da_bwd (csrc/deriv.hip): one launch each way; gradients to attr (tile scatter, zero on unselected
+    channels) and rast_db.  The gradient w.r.t. rast is identically zero.  Double backward: the torch statement."""
+
+    @staticmethod
+    def forward(ctx, attr, rast, tri32, rast_db, sel):
+        require_device(attr, rast, tri32, rast_db, what="interpolate_da")
+        ensure_resolved(rast)
+        attr_c, rast_c, db_c = f32c(attr), f32c(rast), f32c(rast_db)
+        B, H, W = rast_c.shape[:3]
+        V, C = attr_c.shape[1], attr_c.shape[2]
+        assert attr_c.shape[0] in (1, B) and db_c.shape == (B, H, W, 4)
+        S = C if sel is None else len(sel)
+        sel_d = None if sel is None else torch.tensor(sel, dtype=torch.int32, device=rast_c.device)  # (kept for the backward)
+        out = torch.empty((B, H, W, 2 * S), dtype=torch.float32, device=rast_c.device)
+        call("a3d_interp_da_fwd", ptr(attr_c), attr_c.shape[0], C, ptr(sel_d), S, ptr(rast_c), ptr(db_c), ptr(tri32), B, V, tri32.shape[0], H, W,
+             ptr(out), stream(), tag=f"[S{S}]")
+        ctx.save_for_backward(attr, rast_c, tri32, rast_db, sel_d)
+        ctx.sel = sel
+        return out
+
+    @staticmethod
+    def backward(ctx, g_da):
+        attr, rast, tri32, rast_db, sel_d = ctx.saved_tensors
+        want_attr, want_db = ctx.needs_input_grad[0], ctx.needs_input_grad[3]
+        if torch.is_grad_enabled():  # double backward: the torch statement, differentiated by autograd
+            with torch.enable_grad():
+                ins = [t for t, w in ((attr, want_attr), (rast_db, want_db)) if w]
+                out = _interpolate_da_torch(attr, rast, tri32, rast_db, "all" if ctx.sel is None else list(ctx.sel))
+                gs = list(torch.autograd.grad(out, ins, g_da, create_graph=True))
+            return (gs.pop(0) if want_attr else None), None, None, (gs.pop(0) if want_db else None), None
+        attr_c, db_c = f32c(attr), f32c(rast_db)
+        B, H, W = rast.shape[:3]
+        V, C = attr_c.shape[1], attr_c.shape[2]
+        S = C if ctx.sel is None else len(ctx.sel)
+        g_attr = torch.empty_like(attr_c) if want_attr else None
+        g_db = torch.empty_like(db_c) if want_db else None
+        call("a3d_interp_da_bwd", ptr(f32h(g_da)), ptr(attr_c), attr_c.shape[0], C, ptr(sel_d), S, ptr(rast), ptr(db_c), ptr(tri32), B, V,
+             tri32.shape[0], H, W, ptr(g_attr), ptr(g_db), stream(), tag=f"[S{S}]")
+        return g_attr, None, None, g_db, None
+
+
 def interpolate_da(attr, rast, tri, rast_db, diff_attrs="all"):
     """out_da [B,H,W,2*S] = (dA/dX, dA/dY) per selected attribute (dr.interpolate's second output with ``rast_db`` / ``diff_attrs``):
-    dA/dX = du/dX (A0 - A2) + dv/dX (A1 - A2).  torch ops (differentiable); nothing on the training path consumes it (render.py:24)."""
+    dA/dX = du/dX (A0 - A2) + dv/dX (A1 - A2), differentiable w.r.t. attr and rast_db.  CUDA float32 tensors: one HIP launch each way
+    (a3d_interp_da_fwd / _bwd, csrc/deriv.hip; up to 64 attributes and 64 selected ones); anything else -- CPU tensors, float64, wider
+    rows, a double backward -- evaluates the torch statement _interpolate_da_torch.  Nothing on the training path consumes it
+    (render.py:24)."""
+    a = attr if attr.dim() == 3 else attr[None]
+    C = a.shape[-1]
+    if _deriv_on_gpu(a, rast, rast_db) and tri.is_cuda and 0 < C <= _lib.DERIV_MAX_SELECTED:
+        sel = _selected(diff_attrs, C)
+        if sel is None or 0 < len(sel) <= _lib.DERIV_MAX_SELECTED:
+            return _InterpolateDa.apply(a, rast, tri_int32(tri), rast_db, sel)
+    return _interpolate_da_torch(attr, rast, tri, rast_db, diff_attrs)
+
+
+def _interpolate_da_torch(attr, rast, tri, rast_db, diff_attrs="all"):
+    """interpolate_da as torch operations (a [B,H,W,3,S] gather and a dozen element-wise launches; backward = autograd's index_put): the
+    statement the kernels follow, the path of CPU / float64 tensors and of a double backward, and what tests and tools/bench_deriv.py
+    compare against."""
     a = attr if attr.dim() == 3 else attr[None]
     sel = list(range(a.shape[-1])) if isinstance(diff_attrs, str) and diff_attrs == "all" else list(diff_attrs)
     B = rast.shape[0]

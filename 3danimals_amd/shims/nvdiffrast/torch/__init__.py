@@ -3,7 +3,8 @@
 Put ``3danimals_amd/shims`` on ``sys.path`` and the reference's unchanged callers --
 ``dr.RasterizeGLContext()`` (AnimalModel.py:235-236), ``dr.DepthPeeler`` / ``dr.interpolate`` / ``dr.antialias``
 (render.py:24,264-267,292-294), ``dr.rasterize`` (render.py:351, visualize_results.py:225-229) -- run on MI355X
-without OpenGL or CUDA.  Instanced and range mode, ``grad_db``, ``diff_attrs`` and ``pos_gradient_boost`` are covered.  ``dr.texture``
+without OpenGL or CUDA.  Instanced and range mode, ``grad_db``, ``diff_attrs`` (HIP kernels of their own, csrc/deriv.hip) and
+``pos_gradient_boost`` are covered.  ``dr.texture``
 (Texture2D.sample, EnvironmentLight.shade, cubemap_mip, cubemap_to_latlong, the 2-D bilinear taps) runs every mode on the GPU --
 mip-mapped, uv_da, mip_level_bias, custom mip stacks, cube maps -- and ``dr.texture_construct_mip`` builds a stack there; on CPU
 tensors only the 2-D bilinear / nearest tap exists (torch).
@@ -40,8 +41,8 @@ class RasterizeCudaContext(_Context):
 
 class _LazyRastDb:
     """rast_db computed on first use.  The reference's render.py receives it from every rasterize call and discards it (render.py:24
-    passes rast_db=None), so the ~30 torch launches over [B,H,W,3,4] gathers are only paid by a caller that actually looks at it:
-    any torch function applied to the object, an attribute (.shape, .dtype ...) or an index materialises the tensor."""
+    passes rast_db=None), so its launch (a3d_rast_db_fwd, csrc/deriv.hip) is only paid by a caller that actually looks at it: any
+    torch function applied to the object, an attribute (.shape, .dtype ...) or an index materialises the tensor."""
 
     def __init__(self, make):
         self._make, self._value = make, None
@@ -148,8 +149,8 @@ def _rasterize_ranges(pos, tri, resolution, ranges, prev=None):
 
 def rasterize(glctx, pos, tri, resolution, ranges=None, grad_db=True):
     """-> (rast [B,H,W,4] = (u, v, z/w, triangle_id+1), rast_db [B,H,W,4] = (du/dX, du/dY, dv/dX, dv/dY)).  The image-space
-    derivatives are analytic (ops.rasterize_db, torch ops) and computed on first use: no caller on the training path consumes them
-    (render.py:24)."""
+    derivatives are analytic (ops.rasterize_db: one HIP launch, a3d_rast_db_fwd; with grad_db its backward a3d_rast_db_bwd reaches pos)
+    and computed on first use: no caller on the training path consumes them (render.py:24)."""
     _check(pos, tri, resolution, ranges)
     if ranges is not None:
         rast = _rasterize_ranges(pos, tri, resolution, ranges)
@@ -190,7 +191,8 @@ class DepthPeeler:
 
 def interpolate(attr, rast, tri, rast_db=None, diff_attrs=None):
     """-> (out [B,H,W,C], out_da).  With ``rast_db`` and ``diff_attrs`` ('all' or a list of attribute indices) out_da
-    [B,H,W,2*len(diff_attrs)] holds (dA/dX, dA/dY) per selected attribute: dA/dX = du/dX (A0 - A2) + dv/dX (A1 - A2) (torch ops)."""
+    [B,H,W,2*len(diff_attrs)] holds (dA/dX, dA/dY) per selected attribute: dA/dX = du/dX (A0 - A2) + dv/dX (A1 - A2)
+    (ops.interpolate_da: one more HIP launch, a3d_interp_da_fwd; gradients reach attr and rast_db through a3d_interp_da_bwd)."""
     if attr.dim() == 2:  # range mode: one shared attribute array
         attr = attr[None]
     out = _ops.interpolate(attr, rast, tri)
