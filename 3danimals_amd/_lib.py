@@ -1,4 +1,4 @@
-"""ctypes binding of liba3d_hip.so (include/a3d.h, include/a3d_bsdf.h, include/a3d_deriv.h).  No fallback: if the library is missing we say so and stop."""
+"""ctypes binding of liba3d_hip.so (include/a3d.h, include/a3d_bsdf.h, include/a3d_deriv.h, include/a3d_tangent.h).  No fallback: if the library is missing we say so and stop."""
 from __future__ import annotations
 
 import ctypes
@@ -226,6 +226,16 @@ DERIV_SIGNATURES = {
 }
 DERIV_MAX_SELECTED = 64  # A3D_DERIV_MAX_SELECTED
 
+# the entry points of include/a3d_tangent.h (same library, same a3d_version(); tests/test_tangent_cpu.py checks this table against that header)
+TANGENT_SIGNATURES = {
+    "a3d_shading_normal_rows": (ctypes.c_int64, [_p]),
+    "a3d_shading_normal_fwd": (_c_int, [_p, _p]),
+    "a3d_shading_normal_bwd": (_c_int, [_p, _p]),
+    "a3d_tangents_fwd": (_c_int, [_p, _p, ctypes.c_int64, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p]),
+    "a3d_tangents_bwd": (_c_int, [_p, _p, _p, ctypes.c_int64, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p]),
+}
+SHADING_NORMAL_OP = 5  # A3D_SHADING_NORMAL
+
 ABI_VERSION = 404  # a3d_version() of the library these signatures belong to (include/a3d.h)
 _lib = None
 
@@ -244,7 +254,7 @@ def lib():
                 "(or __graft_entry__.build()).  There is no CPU fallback for the HIP hot path."
             )
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(BSDF_SIGNATURES.items()) + list(DERIV_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(BSDF_SIGNATURES.items()) + list(DERIV_SIGNATURES.items()) + list(TANGENT_SIGNATURES.items()):
             fn = getattr(handle, name)  # AttributeError here == ABI drift
             fn.restype, fn.argtypes = res, args
         if handle.a3d_version() != ABI_VERSION:  # same symbols, other argument lists: a stale build must not be called

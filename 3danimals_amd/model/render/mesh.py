@@ -3,8 +3,9 @@
 Differences that do not change results on the hot path:
 * vertex normals (auto_normals, reference :276-304) come from csrc/normals.hip (forward + backward);
 * tangents (compute_tangents, reference :310-350) are LAZY: ``shade`` forces perturbed_nrm=None (render.py:71), for
-  which value and gradient are independent of the tangent field, so ``v_tng`` is only built
-  -- with the reference's torch expressions -- when something actually reads it ('tangent' render mode, export);
+  which value and gradient are independent of the tangent field, so ``v_tng`` is only built when something
+  actually reads it ('tangent' render mode, export, a normal-mapped shade) -- by csrc/tangent.hip (ops.vertex_tangents) for a CUDA
+  float32 mesh, with the reference's torch expressions otherwise;
 * ``v_tex`` is not copied B times: batch expansion uses views.
 """
 from __future__ import annotations
@@ -18,6 +19,7 @@ from ... import ops
 from . import util
 
 
+HIP_TANGENTS = True  # Mesh.v_tng of a CUDA float32 mesh from a3d_tangents_fwd / _bwd (False: always the torch statements of _tangents)
 LAZY_NORMALS = True  # auto_normals defers the kernel to the first read of Mesh.v_nrm (same values; False = at make_mesh time)
 PAIR_NORMALS = True  # ... and a pending small mesh (<= PAIR_MAX_BATCH images: the canonical one) over the SAME triangle list rides in that launch
 PAIR_MAX_BATCH = 2
@@ -266,8 +268,31 @@ def auto_normals(imesh):
     return Mesh(v_nrm=v_nrm, t_nrm_idx=imesh.t_pos_idx, base=imesh)
 
 
+def _hip_tangents_ok(imesh):
+    """The kernels' scope: CUDA float32, normals indexed like positions (make_mesh always produces that), a static atlas."""
+    if not HIP_TANGENTS or imesh.t_pos_idx is None or imesh.t_tex_idx is None or imesh.t_nrm_idx is None:
+        return False
+    floats = (imesh.v_pos, imesh.v_tex, imesh.v_nrm)
+    if not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 for t in floats):
+        return False
+    if imesh.v_tex.requires_grad or imesh.v_nrm.shape != imesh.v_pos.shape or imesh.v_tex.shape[0] not in (1, imesh.v_pos.shape[0]):
+        return False
+    if not (imesh.t_pos_idx.is_cuda and imesh.t_tex_idx.is_cuda and imesh.t_pos_idx.shape == imesh.t_tex_idx.shape):
+        return False
+    same = imesh.t_nrm_idx is imesh.t_pos_idx or (imesh.t_nrm_idx.shape == imesh.t_pos_idx.shape
+                                                  and imesh.t_nrm_idx.data_ptr() == imesh.t_pos_idx.data_ptr()
+                                                  and imesh.t_nrm_idx.stride() == imesh.t_pos_idx.stride())
+    return same or (imesh.t_nrm_idx.shape == imesh.t_pos_idx.shape and bool(torch.equal(imesh.t_nrm_idx, imesh.t_pos_idx)))
+
+
 def _tangents(imesh):
-    """Per-vertex tangents from the uv atlas, reference :310-350 (torch; off the training path)."""
+    """Per-vertex tangents from the uv atlas, reference :310-350: csrc/tangent.hip where it applies, else the torch statements below
+    (CPU, float64, an atlas that wants a gradient, normals with an index list of their own) -- they are the kernel's specification."""
+    if _hip_tangents_ok(imesh):
+        t = ops.vertex_tangents(imesh.v_pos, imesh.v_tex, imesh.v_nrm, imesh.t_pos_idx, imesh.t_tex_idx)
+        if torch.is_anomaly_enabled():
+            assert torch.all(torch.isfinite(t))
+        return t
     faces, uv_idx = imesh.t_pos_idx[0], imesh.t_tex_idx[0]
     pos = [imesh.v_pos[:, faces[:, i]] for i in range(3)]
     tex = [imesh.v_tex[:, uv_idx[:, i]] for i in range(3)]

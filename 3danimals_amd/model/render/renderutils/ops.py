@@ -15,6 +15,7 @@ from ...._lib import fp32_region
 
 NORMAL_THRESHOLD = 0.1  # reference renderutils/bsdf.py:13
 HIP_XFM_POINTS = True  # xfm_points on the GPU as a3d_xfm_points_fwd / _bwd (False: the padded torch matmul, e.g. for double precision)
+HIP_SHADING_NORMAL = True  # prepare_shading_normal WITH a perturbed normal as a3d_shading_normal_fwd / _bwd (False: always the torch statements)
 
 
 def _dot(x, y):
@@ -62,8 +63,18 @@ def prepare_shading_normal(pos, view_pos, perturbed_nrm, smooth_nrm, smooth_tng,
     two-sided flip by the geometric normal, bend toward the geometric normal at grazing view angles.
 
     The hot path passes perturbed_nrm=None (render.py:71), for which the tangent frame cancels exactly and
-    ``smooth_tng`` is not touched (so it may be None).
+    ``smooth_tng`` is not touched (so it may be None).  With a perturbed normal, ``use_python=False`` and CUDA float32 tensors the
+    statements below run as one launch each way (ops.shading_normal, csrc/tangent.hip); they are its specification.
     """
+    if (not use_python and perturbed_nrm is not None and HIP_SHADING_NORMAL
+            and all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() >= 1 and t.shape[-1] == 3
+                    for t in (pos, view_pos, perturbed_nrm, smooth_nrm, smooth_tng, geom_nrm))):
+        from .... import ops
+
+        out = ops.shading_normal(pos, view_pos, perturbed_nrm, smooth_nrm, smooth_tng, geom_nrm, two_sided_shading, opengl)
+        if torch.is_anomaly_enabled():
+            assert torch.all(torch.isfinite(out)), "Output of prepare_shading_normal contains inf or NaN"
+        return out
     n = F.normalize(smooth_nrm, dim=-1)
     view = F.normalize(view_pos - pos, dim=-1)
     if perturbed_nrm is not None:

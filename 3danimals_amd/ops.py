@@ -2468,7 +2468,7 @@ class _BsdfPlan:
     _geometry = {}  # (name, shapes, strides) -> the plan's geometry: a training loop calls with the same few layouts every step
 
     def __init__(self, name, inputs):
-        self.code, chans, self.c_out = BSDF_OPS[name]
+        self.code, chans, self.c_out = BSDF_OPS.get(name) or TANGENT_OPS[name]
         self.inputs, self.chans = inputs, chans
         key = (name, tuple((t.shape, t.stride()) for t in inputs))
         geo = self._geometry.get(key)
@@ -2698,6 +2698,111 @@ def image_loss(img, target, loss="l1", tonemapper="none"):
     if img.numel() == 0 or target.numel() == 0:
         return (img * target).mean()  # (the mean of nothing: nan, as torch's)
     return _ImageLoss.apply(img, target, IMAGE_LOSSES.get(loss, 0) + 4 * (tonemapper == "log_srgb"))
+
+
+# ---------------------------------------------------------------------------------------------- tangent frame (include/a3d_tangent.h)
+TANGENT_OPS = {"shading_normal": (_lib.SHADING_NORMAL_OP, (3, 3, 3, 3, 3, 3), 3)}  # the call plan is _BsdfPlan's, the op code a3d_tangent.h's
+
+
+class _ShadingNormal(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, variant, *inputs):
+        plan = _BsdfPlan("shading_normal", inputs)
+        out = torch.empty((*plan.lead, 3), dtype=torch.float32, device=inputs[0].device)
+        if plan.n:
+            d = plan.desc()
+            d.variant, d.out = variant, out.data_ptr()
+            call("a3d_shading_normal_fwd", ctypes.byref(d), stream())
+        ctx.variant = variant
+        ctx.save_for_backward(*inputs)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out):
+        inputs = ctx.saved_tensors
+        plan = _BsdfPlan("shading_normal", inputs)
+        needs = ctx.needs_input_grad[1:]
+        if not plan.n:
+            return (None,) + tuple(torch.zeros_like(t) if n else None for t, n in zip(inputs, needs))
+        g_out = f32c(g_out)
+        d = plan.desc()
+        d.variant, d.g_out = ctx.variant, g_out.data_ptr()
+        collect = plan.grads(d, needs, g_out.device)
+        call("a3d_shading_normal_bwd", ctypes.byref(d), stream())
+        return (None,) + tuple(collect())
+
+
+def shading_normal(pos, view_pos, perturbed_nrm, smooth_nrm, smooth_tng, geom_nrm, two_sided_shading=True, opengl=True):
+    """prepare_shading_normal of renderutils WITH a tangent-space perturbation as one launch forward and one backward (csrc/tangent.hip,
+    include/a3d_tangent.h); the arithmetic is the torch statements of model/render/renderutils/ops.py, operation by operation.
+
+    Six float32 tensors on the GPU, [..., 3], broadcastable against each other in every leading dimension, any strides (a channel slice
+    ``all_tex[..., 6:9]`` is read in place).  Returns [..., 3] in the broadcast leading shape.  Gradients as ops.bsdf's: an input that is
+    broadcast along trailing leading dimensions only (view_pos [B,1,1,3], a constant perturbation [1,1,1,3]) is summed inside the launch
+    in double, without atomics, bit-identical run to run.  The forward is float32; the backward carries its arithmetic in double."""
+    inputs = (pos, view_pos, perturbed_nrm, smooth_nrm, smooth_tng, geom_nrm)
+    for t in inputs:
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise ValueError(f"shading_normal: expected float32 tensors, got {getattr(t, 'dtype', type(t))}")
+    require_device(*inputs, what="shading_normal")
+    return _ShadingNormal.apply(int(bool(two_sided_shading)) + 2 * int(bool(opengl)), *inputs)
+
+
+def _tangent_atlas(v_tex, B):
+    """(v_tex as the kernel reads it, elements between the images' atlases): [1,Nuv,2] and stride-0 views of it are passed on as they
+    are (batch stride 0), never expanded in memory."""
+    if v_tex.shape[0] not in (1, B):
+        raise ValueError(f"vertex_tangents: v_tex has {v_tex.shape[0]} atlases for {B} meshes")
+    if v_tex.shape[0] == 1 or v_tex.stride(0) == 0:
+        return f32c(v_tex[0:1]), 0
+    v_tex = f32c(v_tex)
+    return v_tex, v_tex.stride(0)
+
+
+class _Tangents(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, v_pos, v_nrm, v_tex, tri32, tex32, adjacency):
+        v_pos, v_nrm = f32c(v_pos), f32c(v_nrm)
+        B, V, F = v_pos.shape[0], v_pos.shape[1], tri32.shape[0]
+        v_tex, tex_stride = _tangent_atlas(v_tex, B)
+        v_tng = torch.empty_like(v_pos)
+        call("a3d_tangents_fwd", ptr(v_pos), ptr(v_tex), tex_stride, ptr(v_nrm), ptr(tri32), ptr(tex32), ptr(adjacency.off), ptr(adjacency.adj),
+             adjacency.stride, B, V, F, ptr(v_tng), stream(), tag=f"[B{B}]")
+        ctx.save_for_backward(v_pos, v_nrm, v_tex, tri32, tex32)
+        ctx.adjacency, ctx.tex_stride = adjacency, tex_stride
+        return v_tng
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_tng):
+        v_pos, v_nrm, v_tex, tri32, tex32 = ctx.saved_tensors
+        B, V, F = v_pos.shape[0], v_pos.shape[1], tri32.shape[0]
+        g_tng = f32c(g_tng)
+        scratch = torch.empty((B, V, 3), dtype=torch.float64, device=v_pos.device)
+        g_pos, g_nrm = torch.empty_like(v_pos), torch.empty_like(v_pos)
+        call("a3d_tangents_bwd", ptr(g_tng), ptr(v_pos), ptr(v_tex), ctx.tex_stride, ptr(v_nrm), ptr(tri32), ptr(tex32), ptr(ctx.adjacency.off),
+             ptr(ctx.adjacency.adj), ctx.adjacency.stride, B, V, F, ptr(scratch), ptr(g_pos), ptr(g_nrm), stream(), tag=f"[B{B}]")
+        return g_pos, g_nrm, None, None, None, None
+
+
+def vertex_tangents(v_pos, v_tex, v_nrm, t_pos_idx, t_tex_idx):
+    """Per-vertex tangents [B,V,3] of compute_tangents (reference mesh.py:310-350) for a mesh whose normals are indexed by t_pos_idx:
+    one launch forward, two backward (csrc/tangent.hip), gradients to v_pos and v_nrm, none to the static atlas v_tex ([1,Nuv,2], a
+    stride-0 expansion of it, or [B,Nuv,2]).  The vertex -> face lists are vertex_face_adjacency's, built once per triangle list."""
+    for t in (v_pos, v_tex, v_nrm):
+        if t.dtype != torch.float32:
+            raise ValueError(f"vertex_tangents: expected float32 tensors, got {t.dtype}")
+    if v_tex.requires_grad and torch.is_grad_enabled():
+        raise ValueError("vertex_tangents: v_tex receives no gradient from the kernels (the atlas is static); detach it or use the torch statements")
+    tri32, tex32 = tri_int32(t_pos_idx), tri_int32(t_tex_idx)
+    require_device(v_pos, v_tex, v_nrm, tri32, tex32, what="vertex_tangents")
+    if v_pos.dim() != 3 or v_pos.shape != v_nrm.shape or v_pos.shape[2] != 3 or tex32.shape != tri32.shape or v_tex.dim() != 3 or v_tex.shape[2] != 2:
+        raise ValueError(f"vertex_tangents: v_pos {list(v_pos.shape)}, v_nrm {list(v_nrm.shape)}, v_tex {list(v_tex.shape)}, "
+                         f"t_pos_idx {list(tri32.shape)}, t_tex_idx {list(tex32.shape)}")
+    if tri32.shape[0] == 0 or v_pos.shape[0] == 0 or v_pos.shape[1] == 0:
+        return torch.full_like(v_pos, float("nan")) + 0 * (v_pos + v_nrm)  # (no face anywhere: 0 / 0 at every vertex, as the torch statements)
+    return _Tangents.apply(v_pos, v_nrm, v_tex, tri32, tex32, vertex_face_adjacency(tri32, v_pos.shape[1]))
 
 
 # ---------------------------------------------------------------------------------------------- mixed precision
