@@ -375,7 +375,9 @@ def test_skinning_matches_reference_golden(tag, dev, mods):
     wgt, wgt_b = seeded(out.shape, 77, -1, 1).to(dev), seeded(aux["posed_bones"].shape, 78, -1, 1).to(dev)
     gv, ga = torch.autograd.grad((out * wgt).sum() + (aux["posed_bones"] * wgt_b).sum(), [v, ang])
     np.testing.assert_allclose(gv.cpu().numpy(), g["grad_v"], rtol=1e-3, atol=2e-5)
-    np.testing.assert_allclose(ga.cpu().numpy(), g["grad_angles"], rtol=1e-3, atol=1e-3)
+    # atol: 4 x what the torch float32 path errs by against float64 on these inputs (8.7e-6) plus the golden's own distance from float64
+    # (1.1e-5): tests/test_skin_cpu.py::test_golden_gradient_figures measures both
+    np.testing.assert_allclose(ga.cpu().numpy(), g["grad_angles"], rtol=1e-3, atol=4 * 8.7e-6 + 1.1e-5)
 
 
 def test_skinning_identity_and_oracle_larger(dev, mods):
@@ -1828,7 +1830,9 @@ def test_bone_transforms_kernel_vs_torch_chain(tag, dev, mods):
     wgt = seeded(ref.shape, 17, -1, 1).to(dev)
     (g1,) = torch.autograd.grad((ref * wgt).sum(), a1)
     (g2,) = torch.autograd.grad((out * wgt).sum(), a2)
-    np.testing.assert_allclose(g2.cpu().numpy(), g1.cpu().numpy(), rtol=1e-4, atol=1e-4)
+    # atol: the torch chain errs by 3.3e-6 against float64 on these inputs (tests/test_skin_cpu.py::test_golden_gradient_figures); the
+    # kernel is allowed 4 x that, and the two float32 results may lie on opposite sides of the float64 one
+    np.testing.assert_allclose(g2.cpu().numpy(), g1.cpu().numpy(), rtol=1e-4, atol=5 * 3.3e-6)
 
 
 def test_max_size_grid_and_raster_properties(dev, mods, ops):
