@@ -1,29 +1,19 @@
 // Shading BSDFs and the HDR image loss on gfx950 (include/a3d_bsdf.h): lambert, frostbite_diffuse, pbr_specular, pbr_bsdf and image_loss
 // of the reference's renderutils (ops.py:244-386, 476-498), one fused launch forward and one backward per call.  The per-pixel arithmetic
-// and its hand-written derivatives are bsdf_math.h; this file is the memory side.
-//
-// One lane per pixel, A3D_BSDF_TILE = 4 x 256 pixels per work-group: in round `it` lane t takes pixel tile + 256 it + t, so a wave reads 64
-// consecutive pixels = 768 contiguous bytes of every contiguous 3-channel input.  The forward keeps everything in registers and stores
-// the colour once; the backward recomputes the forward's intermediates from the inputs (nothing is saved but the inputs) and writes
-// every gradient from the same launch.
-// Inputs are base pointer + per-dimension element strides (0 = broadcast), resolved per input to one of three address modes on the host:
-// ROWS (contiguous [pixels, C]: offset = pixel * C, no index arithmetic), UNIFORM (constant over the work-group's segment: one offset
-// per work-group) or STRIDED (the pixel index is decomposed into the leading dimensions; 32-bit divisions when the pixel count allows).
-// Gradients of inputs that are constant over runs of pixels (camera / light position, a constant albedo) are reduced without atomics:
-// lane registers over the 4 rounds -> wave (xor butterfly) -> work-group (LDS, fixed order) -> ONE partial row per work-group; a second
-// small launch adds the rows of each run in a fixed order.  The sums are carried in DOUBLE (partial rows are doubles).  Bit-identical run to run.  image_loss forward sums its scalar the same way.
-#include <limits.h>
-
+// and its hand-written derivatives are bsdf_math.h; the memory side (address modes, reduced gradients, the descriptor check, the finishing
+// launch) is pixel_desc.h, shared with tangent.hip.  This file holds the operators' policies, their op / variant rule, the rule that picks
+// float or double, and the image loss's fast form for contiguous images.
 #include "../../include/a3d_bsdf.h"
 #include "a3d_common.h"
 #include "bsdf_math.h"
+#include "pixel_desc.h"
 
 namespace {
 
 using bsdf::V3T;
-
-constexpr int NI = A3D_BSDF_MAX_INPUTS, ND = A3D_BSDF_MAX_DIMS, TILE = A3D_BSDF_TILE, THREADS = 256, ROUNDS = TILE / THREADS;
-enum { MODE_ROWS = 0, MODE_UNIFORM = 1, MODE_STRIDED = 2 };
+using px::ROUNDS;
+using px::THREADS;
+using px::TILE;
 
 constexpr int op_nin(int op) { return op == A3D_BSDF_LAMBERT ? 2 : op == A3D_BSDF_FROSTBITE ? 4 : op == A3D_BSDF_PBR_SPECULAR ? 5 : op == A3D_BSDF_PBR ? 6 : 2; }
 constexpr int op_cin(int op, int i) {
@@ -31,135 +21,15 @@ constexpr int op_cin(int op, int i) {
 }
 constexpr int op_cout(int op) { return (op == A3D_BSDF_PBR_SPECULAR || op == A3D_BSDF_PBR) ? 3 : 1; }
 
-struct BsdfIn {
-    const float* p;
-    long long st[ND];
-    long long cs;
-    float* g;
-    int mode, gmode;
-};
+// px::kernel's policy for one A3D_BSDF_* code
+template <int OP>
+struct BsdfOp {
+    static constexpr int NIN = op_nin(OP), CO = op_cout(OP);
+    static constexpr bool SUM = OP == A3D_BSDF_IMAGE_LOSS;
+    static constexpr int cin(int i) { return op_cin(OP, i); }
 
-struct BsdfK {
-    int variant, ndim, small, any_uniform, any_strided;
-    float min_a;
-    long long n, seg, bps;
-    long long shape[ND];
-    BsdfIn in[NI];
-    float* out;
-    const float* g_out;
-    float* scratch;
-};
-
-struct BsdfFin {  // the finishing launch: final[e][c] = sum over rows [e R, (e + 1) R) of rows[.][c], optionally / div
-    const double* rows[NI];
-    float* final_[NI];
-    long long R[NI], ne[NI];
-    int C[NI];
-    double div;
-};
-
-// offset of pixel p in an input, from its leading-dimension strides
-__device__ __forceinline__ void bsdf_index(const BsdfK& k, long long p, long long* idx) {
-    if (k.small) {
-        unsigned r = (unsigned)p;
-        for (int d = k.ndim - 1; d > 0; --d) {
-            const unsigned s = (unsigned)k.shape[d];
-            idx[d] = r % s;
-            r /= s;
-        }
-        idx[0] = r;
-    } else {
-        long long r = p;
-        for (int d = k.ndim - 1; d > 0; --d) {
-            idx[d] = r % k.shape[d];
-            r /= k.shape[d];
-        }
-        idx[0] = r;
-    }
-}
-
-__device__ __forceinline__ long long bsdf_offset(const BsdfK& k, const BsdfIn& in, const long long* idx) {
-    long long o = 0;
-    for (int d = 0; d < k.ndim; ++d) o += idx[d] * in.st[d];
-    return o;
-}
-
-template <typename T>
-__device__ __forceinline__ T comp(V3T<T> v, int c) { return c == 0 ? v.x : c == 1 ? v.y : v.z; }
-
-// sum of v over the work-group, in a fixed order (red: 4 doubles of LDS).  Sums are carried in double from the lane to the finishing
-// launch: what is left in a reduced gradient is the rounding of the per-pixel terms, not of the summation
-__device__ __forceinline__ double bsdf_block_sum(double v, double* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
-// T: the scalar the per-pixel arithmetic is carried in.  float, except in the backward of a call that reduces a gradient over pixels
-// (a [B,1,1,3] camera): there it is double, so that the few numbers such a gradient consists of carry the rounding of the float32
-// INPUTS only -- two float32 evaluations of a sum of thousands of ill-conditioned terms otherwise differ by a factor either way.
-template <int OP, bool BWD, typename T>
-__global__ __launch_bounds__(THREADS) void bsdf_kernel(const BsdfK k) {
-    constexpr int NIN = op_nin(OP), CO = op_cout(OP);
-    __shared__ double red[4];
-    const unsigned bps = (unsigned)k.bps;  // (the grid fits 31 bits, so does this: 32-bit division, once per lane)
-    const long long sg = blockIdx.x / bps, blk = blockIdx.x % bps;
-    const long long p0 = sg * k.seg;
-    long long idx[ND] = {0, 0, 0, 0};
-    long long uoff[NIN];
-    if (k.any_uniform) {
-        bsdf_index(k, p0, idx);
-#pragma unroll
-        for (int i = 0; i < NIN; ++i) uoff[i] = bsdf_offset(k, k.in[i], idx);
-    } else {
-#pragma unroll
-        for (int i = 0; i < NIN; ++i) uoff[i] = 0;
-    }
-    // (accumulators only where a gradient can be reduced: the double instantiation -- bsdf_launch picks it exactly then -- and the image
-    // loss; the float BSDF backward carries none)
-    constexpr bool ACC = BWD && (sizeof(T) == 8 || OP == A3D_BSDF_IMAGE_LOSS);
-    double acc[ACC ? NIN : 1][3];
-#pragma unroll
-    for (int i = 0; i < (ACC ? NIN : 1); ++i) acc[i][0] = acc[i][1] = acc[i][2] = 0.0;
-    double lsum = 0.0;
-    const T g_scalar = (OP == A3D_BSDF_IMAGE_LOSS && BWD) ? (T)(k.g_out[0] / (float)k.n) : T(0);
-
-    // (the BSDF backwards keep the rounds rolled: unrolled, four rounds of live state do not fit the register file; the forwards and the
-    // image loss have little state and want their four rounds of loads in flight together)
-    constexpr int UNROLL = (OP == A3D_BSDF_IMAGE_LOSS || !BWD) ? ROUNDS : 1;
-#pragma unroll UNROLL
-    for (int it = 0; it < ROUNDS; ++it) {
-        const long long q = blk * TILE + it * THREADS + threadIdx.x;
-        if (q >= k.seg) break;
-        const long long p = p0 + q;
-        if (k.any_strided) bsdf_index(k, p, idx);
-        T x[NIN][3];
-#pragma unroll
-        for (int i = 0; i < NIN; ++i) {
-            const int C = op_cin(OP, i);
-            const BsdfIn& in = k.in[i];
-            if (in.mode == MODE_ROWS) {
-                const float* s = in.p + p * C;
-#pragma unroll
-                for (int c = 0; c < C; ++c) x[i][c] = s[c];
-            } else {
-                const float* s = in.p + (in.mode == MODE_UNIFORM ? uoff[i] : bsdf_offset(k, in, idx));
-#pragma unroll
-                for (int c = 0; c < C; ++c) x[i][c] = s[c * in.cs];
-            }
-        }
-        V3T<T> g[NIN];
-#pragma unroll
-        for (int i = 0; i < NIN; ++i) g[i] = V3T<T>{T(0), T(0), T(0)};
-        T go[3] = {T(0), T(0), T(0)};
-        if (BWD && OP != A3D_BSDF_IMAGE_LOSS) {
-#pragma unroll
-            for (int c = 0; c < CO; ++c) go[c] = k.g_out[p * CO + c];
-        }
-        T o[3] = {T(0), T(0), T(0)};
+    template <bool BWD, typename T>
+    static __device__ __forceinline__ void pixel(const px::K& k, const T (&x)[NIN][3], const T* go, T* o, V3T<T>* g) {
         auto V = [&](int i) { return V3T<T>{x[i][0], x[i][1], x[i][2]}; };
         const T min_a = (T)k.min_a;
         if constexpr (OP == A3D_BSDF_LAMBERT) {
@@ -176,81 +46,12 @@ __global__ __launch_bounds__(THREADS) void bsdf_kernel(const BsdfK k) {
             o[0] = r.x; o[1] = r.y; o[2] = r.z;
         } else {
             T da, db;
-            lsum += bsdf::image_loss(x[0][0], x[1][0], k.variant & 3, k.variant >> 2, da, db);
-            g[0].x = g_scalar * da;
-            g[1].x = g_scalar * db;
-        }
-        if (!BWD) {
-            if (OP != A3D_BSDF_IMAGE_LOSS) {
-#pragma unroll
-                for (int c = 0; c < CO; ++c) k.out[p * CO + c] = (float)o[c];
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < NIN; ++i) {
-                const int C = op_cin(OP, i);
-                const BsdfIn& in = k.in[i];
-                if (in.gmode == A3D_BSDF_GRAD_DIRECT) {
-#pragma unroll
-                    for (int c = 0; c < C; ++c) in.g[p * C + c] = (float)comp(g[i], c);
-                } else if (ACC && in.gmode == A3D_BSDF_GRAD_REDUCE) {
-#pragma unroll
-                    for (int c = 0; c < C; ++c) acc[ACC ? i : 0][c] += comp(g[i], c);
-                }
-            }
+            o[0] = bsdf::image_loss(x[0][0], x[1][0], k.variant & 3, k.variant >> 2, da, db);
+            g[0].x = go[0] * da;
+            g[1].x = go[0] * db;
         }
     }
-    if (ACC) {
-#pragma unroll
-        for (int i = 0; i < NIN; ++i) {
-            const int C = op_cin(OP, i);
-            if (k.in[i].gmode != A3D_BSDF_GRAD_REDUCE) continue;  // (the same in every lane)
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                const double s = bsdf_block_sum(acc[ACC ? i : 0][c], red);
-                if (threadIdx.x == 0) reinterpret_cast<double*>(k.in[i].g)[(long long)blockIdx.x * C + c] = s;
-            }
-        }
-    } else if (OP == A3D_BSDF_IMAGE_LOSS) {
-        const double s = bsdf_block_sum(lsum, red);
-        if (threadIdx.x == 0) reinterpret_cast<double*>(k.scratch)[blockIdx.x] = s;
-    }
-}
-
-__global__ __launch_bounds__(THREADS) void bsdf_finish_kernel(const BsdfFin f) {
-    __shared__ double red[4];
-    const int i = blockIdx.y;
-    const long long e = blockIdx.x;
-    if (!f.rows[i] || e >= f.ne[i]) return;  // (the same in every lane of the work-group)
-    const int C = f.C[i];
-    const long long R = f.R[i];
-    const double* rows = f.rows[i] + e * R * C;
-    for (int c = 0; c < C; ++c) {
-        double s = 0.0;
-        for (long long r = threadIdx.x; r < R; r += THREADS) s += rows[r * C + c];
-        s = bsdf_block_sum(s, red);
-        if (threadIdx.x == 0) f.final_[i][e * C + c] = (float)(f.div > 0.0 ? s / f.div : s);
-    }
-}
-
-// ---- host side
-// d >= the returned k are the dimensions inside a run of `run` consecutive pixels; -1 when no boundary between dimensions gives that run
-int bsdf_run_dim(const int64_t* shape, int ndim, long long run) {
-    long long prod = 1;
-    if (run == 1) return ndim;
-    for (int d = ndim - 1; d >= 0; --d) {
-        prod *= shape[d];
-        if (prod == run) return d;
-        if (prod > run) return -1;
-    }
-    return -1;
-}
-
-bool bsdf_const_from(const a3d_bsdf_desc* d, int i, int from) {
-    for (int j = from; j < d->ndim; ++j)
-        if (d->shape[j] > 1 && d->stride[ND * i + j] != 0) return false;
-    return true;
-}
+};
 
 // image_loss over two contiguous, 16-byte aligned images of n = 4 m elements, no gradient reduced: 16 bytes per lane and load, four
 // loads per input in flight (the generic kernel's one float per lane and load reaches a quarter of the probe's bandwidth; the torch
@@ -276,14 +77,14 @@ __global__ __launch_bounds__(THREADS) void loss_rows_kernel(const float* __restr
         }
     }
     if (!BWD) {
-        const double s = bsdf_block_sum(lsum, red);
+        const double s = px::block_sum(lsum, red);
         if (threadIdx.x == 0) scratch[blockIdx.x] = s;
     }
 }
 
 // the fast form applies: both inputs ROWS, everything 16-byte aligned, n a multiple of 4, no reduced gradient
-bool loss_rows_ok(const a3d_bsdf_desc* d, const BsdfK& k, bool bwd) {
-    if (k.n % 4 || k.in[0].mode != MODE_ROWS || k.in[1].mode != MODE_ROWS) return false;
+bool loss_rows_ok(const a3d_bsdf_desc* d, const px::K& k, bool bwd) {
+    if (k.n % 4 || k.in[0].mode != px::MODE_ROWS || k.in[1].mode != px::MODE_ROWS) return false;
     uintptr_t bits = (uintptr_t)d->in[0] | (uintptr_t)d->in[1];
     if (bwd)
         for (int i = 0; i < 2; ++i) {
@@ -293,24 +94,9 @@ bool loss_rows_ok(const a3d_bsdf_desc* d, const BsdfK& k, bool bwd) {
     return (bits & 15) == 0;
 }
 
-// validates everything that can be validated without touching a pointer; fills k (n == 0: nothing to launch)
-int bsdf_check(const a3d_bsdf_desc* d, BsdfK& k, const char* fn, bool loss, bool bwd, long long* rows) {
-    if (!d) {
-        a3d_set_error("%s: invalid argument: desc", fn);
-        return A3D_EINVAL;
-    }
-    if (d->size < sizeof(a3d_bsdf_desc)) {  // (before any other field is read: a shorter struct does not have them)
-        a3d_set_error("%s: invalid argument: desc->size %u < sizeof(a3d_bsdf_desc) %zu (a caller built against an older header)", fn, d->size,
-                      sizeof(a3d_bsdf_desc));
-        return A3D_EINVAL;
-    }
-#define BSDF_REQUIRE(cond)                                              \
-    do {                                                                \
-        if (!(cond)) {                                                  \
-            a3d_set_error("%s: invalid argument: %s", fn, #cond);       \
-            return A3D_EINVAL;                                          \
-        }                                                               \
-    } while (0)
+// the op / variant rule of this file's entry points between the two halves of the shared check; fills k (n == 0: nothing to launch)
+int bsdf_check(const a3d_bsdf_desc* d, px::K& k, const char* fn, bool loss, bool bwd, long long* rows) {
+    if (const int rc = px::check_size(d, fn)) return rc;
     if (loss) {
         if (d->op != A3D_BSDF_IMAGE_LOSS || d->variant < 0 || d->variant > 7) {
             a3d_set_error("%s: invalid argument: op %d / variant %d: op must be A3D_BSDF_IMAGE_LOSS, variant loss + 4 * tonemap in 0 .. 7", fn,
@@ -321,96 +107,35 @@ int bsdf_check(const a3d_bsdf_desc* d, BsdfK& k, const char* fn, bool loss, bool
         a3d_set_error("%s: invalid argument: unknown op %d / variant %d", fn, d->op, d->variant);
         return A3D_EINVAL;
     }
-    BSDF_REQUIRE(d->ndim >= 1 && d->ndim <= A3D_BSDF_MAX_DIMS);
-    long long n = 1;
-    for (int j = 0; j < d->ndim; ++j) {
-        if (d->shape[j] < 0 || d->shape[j] > (1ll << 40)) {
-            a3d_set_error("%s: invalid argument: shape[%d] = %lld", fn, j, (long long)d->shape[j]);
-            return A3D_EINVAL;
-        }
-        n *= d->shape[j];
-        BSDF_REQUIRE(n <= (1ll << 40));
+    if (const int rc = px::check(d, k, fn, op_nin(d->op), op_cin, bwd, rows)) return rc;
+    if (loss && !bwd && k.n && !d->scratch) {
+        a3d_set_error("%s: invalid argument: d->scratch != nullptr", fn);
+        return A3D_EINVAL;
     }
-    k.n = n;
-    *rows = 0;
-    if (n == 0) return A3D_OK;
-    BSDF_REQUIRE(d->seg >= 1 && n % d->seg == 0);
-    const int kseg = bsdf_run_dim(d->shape, d->ndim, d->seg);
-    BSDF_REQUIRE(kseg >= 0 /* seg must be the product of trailing dimensions */);
-    k.seg = d->seg;
-    k.bps = (d->seg + TILE - 1) / TILE;
-    BSDF_REQUIRE((n / d->seg) <= INT_MAX / k.bps);
-    *rows = (n / d->seg) * k.bps;
-    k.variant = d->variant;
-    k.ndim = d->ndim;
-    k.small = n < (1ll << 31);
-    k.min_a = d->min_roughness * d->min_roughness;
-    k.any_uniform = k.any_strided = 0;
-    for (int j = 0; j < ND; ++j) k.shape[j] = j < d->ndim ? d->shape[j] : 1;
-    const int nin = op_nin(d->op);
-    for (int i = 0; i < nin; ++i) {
-        BsdfIn& in = k.in[i];
-        const int C = d->op == A3D_BSDF_IMAGE_LOSS ? 1 : op_cin(d->op, i);
-        long long rowstride = C;
-        bool rows_mode = d->cstride[i] == 1 || C == 1;
-        for (int j = ND - 1; j >= 0; --j) {
-            in.st[j] = j < d->ndim ? d->stride[ND * i + j] : 0;
-            if (j < d->ndim) {
-                if (in.st[j] < 0) {
-                    a3d_set_error("%s: invalid argument: stride[%d][%d] = %lld is negative", fn, i, j, (long long)in.st[j]);
-                    return A3D_EINVAL;
-                }
-                if (d->shape[j] > 1 && in.st[j] != rowstride) rows_mode = false;
-                rowstride *= d->shape[j];
-            }
-        }
-        BSDF_REQUIRE(d->cstride[i] >= 0);
-        in.p = d->in[i];
-        in.cs = d->cstride[i];
-        in.mode = rows_mode ? MODE_ROWS : bsdf_const_from(d, i, kseg) ? MODE_UNIFORM : MODE_STRIDED;
-        k.any_uniform |= in.mode == MODE_UNIFORM;
-        k.any_strided |= in.mode == MODE_STRIDED;
-        in.g = nullptr;
-        in.gmode = A3D_BSDF_GRAD_NONE;
-        if (!in.p) {
-            a3d_set_error("%s: invalid argument: in[%d] is NULL", fn, i);
-            return A3D_EINVAL;
-        }
-        if (bwd) {
-            in.gmode = d->g_mode[i];
-            in.g = d->g_in[i];
-            BSDF_REQUIRE(in.gmode >= A3D_BSDF_GRAD_NONE && in.gmode <= A3D_BSDF_GRAD_REDUCE);
-            if (in.gmode != A3D_BSDF_GRAD_NONE) BSDF_REQUIRE(d->g_in[i] != nullptr);
-            if (in.gmode == A3D_BSDF_GRAD_REDUCE) {
-                BSDF_REQUIRE(d->g_final[i] != nullptr && d->seg_div[i] >= 1 && (n / d->seg) % d->seg_div[i] == 0);
-                const int kr = bsdf_run_dim(d->shape, d->ndim, d->seg * d->seg_div[i]);
-                BSDF_REQUIRE(kr >= 0 && bsdf_const_from(d, i, kr) /* a reduced input must be constant over its runs */);
-            }
-        }
-    }
-    k.out = d->out;
-    k.g_out = d->g_out;
-    k.scratch = d->scratch;
-    if (bwd) BSDF_REQUIRE(d->g_out != nullptr);
-    else BSDF_REQUIRE(d->out != nullptr);
-    if (loss && !bwd) BSDF_REQUIRE(d->scratch != nullptr);
-#undef BSDF_REQUIRE
     return A3D_OK;
 }
 
+int bsdf_finish_grads(const a3d_bsdf_desc* d, const px::K& k, hipStream_t s) { return px::finish_grads(d, k, op_nin(d->op), op_cin, s); }
+
+// T, the scalar the per-pixel arithmetic is carried in: float, except in the backward of a BSDF call that reduces a gradient over pixels
+// (a [B,1,1,3] camera): there it is double, so that the few numbers such a gradient consists of carry the rounding of the float32
+// INPUTS only -- two float32 evaluations of a sum of thousands of ill-conditioned terms otherwise differ by a factor either way.
+// (Chosen at compile time where it can be: no forward and no image loss has a double instantiation.)
 template <int OP, bool BWD>
-void bsdf_launch(const BsdfK& k, long long rows, hipStream_t stream) {
-    bool reduce = false;
-    for (int i = 0; i < op_nin(OP); ++i) reduce |= k.in[i].gmode == A3D_BSDF_GRAD_REDUCE;
-    if (BWD && OP != A3D_BSDF_IMAGE_LOSS && reduce) {
-        hipLaunchKernelGGL((bsdf_kernel<OP, BWD, double>), dim3((unsigned)rows), dim3(THREADS), 0, stream, k);
-        return;
+void bsdf_launch(const px::K& k, long long rows, hipStream_t stream) {
+    if constexpr (BWD && OP != A3D_BSDF_IMAGE_LOSS) {
+        bool reduce = false;
+        for (int i = 0; i < op_nin(OP); ++i) reduce |= k.in[i].gmode == A3D_BSDF_GRAD_REDUCE;
+        if (reduce) {
+            hipLaunchKernelGGL((px::kernel<BsdfOp<OP>, BWD, double>), dim3((unsigned)rows), dim3(THREADS), 0, stream, k);
+            return;
+        }
     }
-    hipLaunchKernelGGL((bsdf_kernel<OP, BWD, float>), dim3((unsigned)rows), dim3(THREADS), 0, stream, k);
+    hipLaunchKernelGGL((px::kernel<BsdfOp<OP>, BWD, float>), dim3((unsigned)rows), dim3(THREADS), 0, stream, k);
 }
 
 template <bool BWD>
-int bsdf_run(const a3d_bsdf_desc* d, a3d_stream_t stream, const char* fn, BsdfK& k) {
+int bsdf_run(const a3d_bsdf_desc* d, a3d_stream_t stream, const char* fn, px::K& k) {
     long long rows;
     const int rc = bsdf_check(d, k, fn, false, BWD, &rows);
     if (rc || k.n == 0) return rc;
@@ -425,55 +150,24 @@ int bsdf_run(const a3d_bsdf_desc* d, a3d_stream_t stream, const char* fn, BsdfK&
     return A3D_OK;
 }
 
-// the finishing launch of a backward: every reduced input in one grid (y = input)
-int bsdf_finish_grads(const a3d_bsdf_desc* d, const BsdfK& k, hipStream_t s) {
-    BsdfFin f = {};
-    long long max_e = 0;
-    const int nin = op_nin(d->op);
-    for (int i = 0; i < nin; ++i) {
-        if (k.in[i].gmode != A3D_BSDF_GRAD_REDUCE) continue;
-        f.rows[i] = reinterpret_cast<const double*>(d->g_in[i]);
-        f.final_[i] = d->g_final[i];
-        f.R[i] = d->seg_div[i] * k.bps;
-        f.ne[i] = (k.n / k.seg) / d->seg_div[i];
-        f.C[i] = d->op == A3D_BSDF_IMAGE_LOSS ? 1 : op_cin(d->op, i);
-        if (f.ne[i] > max_e) max_e = f.ne[i];
-    }
-    if (max_e == 0) return A3D_OK;
-    hipLaunchKernelGGL(bsdf_finish_kernel, dim3((unsigned)max_e, nin), dim3(THREADS), 0, s, f);
-    A3D_LAUNCH_CHECK();
-    return A3D_OK;
-}
-
 }  // namespace
 
-extern "C" int64_t a3d_bsdf_rows(const a3d_bsdf_desc* desc) {
-    if (!desc || desc->size < sizeof(a3d_bsdf_desc)) return -1;
-    if (desc->ndim < 1 || desc->ndim > A3D_BSDF_MAX_DIMS || desc->seg < 1) return -1;
-    long long n = 1;
-    for (int j = 0; j < desc->ndim; ++j) {
-        if (desc->shape[j] < 0 || desc->shape[j] > (1ll << 40)) return -1;
-        n *= desc->shape[j];
-        if (n > (1ll << 40)) return -1;
-    }
-    if (n % desc->seg) return -1;
-    return (n / desc->seg) * ((desc->seg + TILE - 1) / TILE);
-}
+extern "C" int64_t a3d_bsdf_rows(const a3d_bsdf_desc* desc) { return px::rows(desc); }
 
 extern "C" int a3d_bsdf_fwd(const a3d_bsdf_desc* desc, a3d_stream_t stream) {
-    BsdfK k;
+    px::K k;
     return bsdf_run<false>(desc, stream, __func__, k);
 }
 
 extern "C" int a3d_bsdf_bwd(const a3d_bsdf_desc* desc, a3d_stream_t stream) {
-    BsdfK k;
+    px::K k;
     const int rc = bsdf_run<true>(desc, stream, __func__, k);
     if (rc || k.n == 0) return rc;
     return bsdf_finish_grads(desc, k, (hipStream_t)stream);
 }
 
 extern "C" int a3d_image_loss_fwd(const a3d_bsdf_desc* desc, a3d_stream_t stream) {
-    BsdfK k;
+    px::K k;
     long long rows;
     const int rc = bsdf_check(desc, k, __func__, true, false, &rows);
     if (rc || k.n == 0) return rc;
@@ -486,20 +180,20 @@ extern "C" int a3d_image_loss_fwd(const a3d_bsdf_desc* desc, a3d_stream_t stream
         bsdf_launch<A3D_BSDF_IMAGE_LOSS, false>(k, rows, s);
     }
     A3D_LAUNCH_CHECK();
-    BsdfFin f = {};
+    px::Fin f = {};
     f.rows[0] = reinterpret_cast<const double*>(desc->scratch);
     f.final_[0] = desc->out;
     f.R[0] = rows;
     f.ne[0] = 1;
     f.C[0] = 1;
     f.div = (double)k.n;
-    hipLaunchKernelGGL(bsdf_finish_kernel, dim3(1, 1), dim3(THREADS), 0, s, f);
+    hipLaunchKernelGGL(px::finish_kernel, dim3(1, 1), dim3(THREADS), 0, s, f);
     A3D_LAUNCH_CHECK();
     return A3D_OK;
 }
 
 extern "C" int a3d_image_loss_bwd(const a3d_bsdf_desc* desc, a3d_stream_t stream) {
-    BsdfK k;
+    px::K k;
     long long rows;
     const int rc = bsdf_check(desc, k, __func__, true, true, &rows);
     if (rc || k.n == 0) return rc;

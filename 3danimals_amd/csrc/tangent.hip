@@ -2,86 +2,24 @@
 // (prepare_shading_normal, reference renderutils/ops.py:194-227, bsdf.py:30-51) and the per-vertex tangents (compute_tangents, reference
 // mesh.py:310-350).
 //
-// Shading normal: the memory side is bsdf.hip's -- one lane per pixel, A3D_BSDF_TILE = 4 x 256 pixels per work-group, inputs read through
-// the descriptor's strides in one of three address modes (ROWS / UNIFORM / STRIDED), reduced gradients as double partial rows per
-// work-group plus a finishing launch in a fixed order.  84 B per pixel forward (six 3-channel inputs, one output), nothing saved for the
-// backward but the inputs.  The arithmetic is the torch statements of model/render/renderutils/ops.py operation by operation
+// Shading normal: a policy for pixel_desc.h's kernel, the memory side shared with bsdf.hip -- one lane per pixel, A3D_BSDF_TILE = 4 x 256
+// pixels per work-group, inputs read through the descriptor's strides in one of three address modes (ROWS / UNIFORM / STRIDED), reduced
+// gradients as double partial rows per work-group plus a finishing launch in a fixed order, the descriptor check.  84 B per pixel
+// forward (six 3-channel inputs, one output), nothing saved for the backward but the inputs.  The arithmetic is the torch statements of model/render/renderutils/ops.py operation by operation
 // (-ffp-contract=off), with bsdf_math.h's normalize and its derivative.
 //
 // Tangents: the gather idiom of normals.hip over the same vertex -> (corner, face) lists, no atomics.  The DMTet atlas gives every face
 // its own uv cell with denom ~ (0.9 / N)^2, so face tangents are huge and unrelated and their sums cancel: the face tangent, the sum
 // and the two normalisations are carried in double (a few dozen operations per vertex next to ~8 x 15 gathers).
-#include <limits.h>
-
 #include "../../include/a3d_tangent.h"
 #include "a3d_common.h"
 #include "bsdf_math.h"
+#include "pixel_desc.h"
 #include "topo_common.h"
 
 namespace {
 
 using bsdf::V3T;
-
-constexpr int NI = A3D_BSDF_MAX_INPUTS, ND = A3D_BSDF_MAX_DIMS, TILE = A3D_BSDF_TILE, THREADS = 256, ROUNDS = TILE / THREADS;
-enum { MODE_ROWS = 0, MODE_UNIFORM = 1, MODE_STRIDED = 2 };
-
-struct SnIn {
-    const float* p;
-    long long st[ND];
-    long long cs;
-    float* g;
-    int mode, gmode;
-};
-
-struct SnK {
-    int variant, ndim, small, any_uniform, any_strided;
-    long long n, seg, bps;
-    long long shape[ND];
-    SnIn in[NI];
-    float* out;
-    const float* g_out;
-};
-
-struct SnFin {  // the finishing launch: final[e][c] = sum over rows [e R, (e + 1) R) of rows[.][c]
-    const double* rows[NI];
-    float* final_[NI];
-    long long R[NI], ne[NI];
-};
-
-__device__ __forceinline__ void sn_index(const SnK& k, long long p, long long* idx) {
-    if (k.small) {
-        unsigned r = (unsigned)p;
-        for (int d = k.ndim - 1; d > 0; --d) {
-            const unsigned s = (unsigned)k.shape[d];
-            idx[d] = r % s;
-            r /= s;
-        }
-        idx[0] = r;
-    } else {
-        long long r = p;
-        for (int d = k.ndim - 1; d > 0; --d) {
-            idx[d] = r % k.shape[d];
-            r /= k.shape[d];
-        }
-        idx[0] = r;
-    }
-}
-
-__device__ __forceinline__ long long sn_offset(const SnK& k, const SnIn& in, const long long* idx) {
-    long long o = 0;
-    for (int d = 0; d < k.ndim; ++d) o += idx[d] * in.st[d];
-    return o;
-}
-
-// sum of v over the work-group, in a fixed order (red: 4 doubles of LDS)
-__device__ __forceinline__ double sn_block_sum(double v, double* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
 
 template <typename T>
 __device__ __forceinline__ V3T<T> cross(V3T<T> a, V3T<T> b) {
@@ -136,214 +74,38 @@ __device__ __forceinline__ V3T<T> shading_normal(const V3T<T>* x, int variant, V
     return out;
 }
 
-template <typename T>
-__device__ __forceinline__ T comp(V3T<T> v, int c) { return c == 0 ? v.x : c == 1 ? v.y : v.z; }
+// px::kernel's policy.  T, the scalar the per-pixel arithmetic is carried in: float forward, double backward.  bsdf.hip goes to double
+// only when a gradient is reduced; here every backward does.  The adjoint of each normalize is a projection g - v (v . g): a component
+// of the result can be 1e-3 of its two terms, and where most of a tensor's gradient is exactly zero (view_pos / pos outside the bend's
+// ramp) nothing but that component's own relative error is left to judge it by.  In double the gradient carries the rounding of the
+// float32 inputs and of the final store only.  view_pos is [B,1,1,3] in every real call, which takes this instantiation in bsdf.hip's
+// rule as well.
+constexpr int sn_cin(int, int) { return 3; }
 
-// T: the scalar the per-pixel arithmetic is carried in: float forward, double backward.  bsdf.hip goes to double only when a gradient
-// is reduced; here every backward does.  The adjoint of each normalize is a projection g - v (v . g): a component of the result can be
-// 1e-3 of its two terms, and where most of a tensor's gradient is exactly zero (view_pos / pos outside the bend's ramp) nothing but that
-// component's own relative error is left to judge it by.  In double the gradient carries the rounding of the float32 inputs and of the
-// final store only.  view_pos is [B,1,1,3] in every real call, which takes this instantiation in bsdf.hip's scheme as well.
-template <bool BWD, typename T>
-__global__ __launch_bounds__(THREADS) void sn_kernel(const SnK k) {
-    __shared__ double red[4];
-    const unsigned bps = (unsigned)k.bps;
-    const long long sg = blockIdx.x / bps, blk = blockIdx.x % bps;
-    const long long p0 = sg * k.seg;
-    long long idx[ND] = {0, 0, 0, 0};
-    long long uoff[NI];
-    if (k.any_uniform) {
-        sn_index(k, p0, idx);
-#pragma unroll
-        for (int i = 0; i < NI; ++i) uoff[i] = sn_offset(k, k.in[i], idx);
-    } else {
-#pragma unroll
-        for (int i = 0; i < NI; ++i) uoff[i] = 0;
-    }
-    constexpr bool ACC = BWD && sizeof(T) == 8;
-    double acc[ACC ? NI : 1][3];
-#pragma unroll
-    for (int i = 0; i < (ACC ? NI : 1); ++i) acc[i][0] = acc[i][1] = acc[i][2] = 0.0;
+struct SnOp {
+    static constexpr int NIN = 6, CO = 3;
+    static constexpr bool SUM = false;
+    static constexpr int cin(int i) { return sn_cin(A3D_SHADING_NORMAL, i); }
 
-    constexpr int UNROLL = BWD ? 1 : ROUNDS;
-#pragma unroll UNROLL
-    for (int it = 0; it < ROUNDS; ++it) {
-        const long long q = blk * TILE + it * THREADS + threadIdx.x;
-        if (q >= k.seg) break;
-        const long long p = p0 + q;
-        if (k.any_strided) sn_index(k, p, idx);
-        V3T<T> x[NI];
+    template <bool BWD, typename T>
+    static __device__ __forceinline__ void pixel(const px::K& k, const T (&x)[NIN][3], const T* go, T* o, V3T<T>* g) {
+        V3T<T> v[NIN];
 #pragma unroll
-        for (int i = 0; i < NI; ++i) {
-            const SnIn& in = k.in[i];
-            if (in.mode == MODE_ROWS) {
-                const float* s = in.p + p * 3;
-                x[i] = V3T<T>{(T)s[0], (T)s[1], (T)s[2]};
-            } else {
-                const float* s = in.p + (in.mode == MODE_UNIFORM ? uoff[i] : sn_offset(k, in, idx));
-                x[i] = V3T<T>{(T)s[0], (T)s[in.cs], (T)s[2 * in.cs]};
-            }
-        }
-        V3T<T> g[NI];
-        V3T<T> go = V3T<T>{T(0), T(0), T(0)};
-        if (BWD) go = V3T<T>{(T)k.g_out[p * 3], (T)k.g_out[p * 3 + 1], (T)k.g_out[p * 3 + 2]};
-        const V3T<T> o = shading_normal<BWD, T>(x, k.variant, go, g);
-        if (!BWD) {
-            k.out[p * 3] = (float)o.x; k.out[p * 3 + 1] = (float)o.y; k.out[p * 3 + 2] = (float)o.z;
-        } else {
-#pragma unroll
-            for (int i = 0; i < NI; ++i) {
-                const SnIn& in = k.in[i];
-                if (in.gmode == A3D_BSDF_GRAD_DIRECT) {
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) in.g[p * 3 + c] = (float)comp(g[i], c);
-                } else if (ACC && in.gmode == A3D_BSDF_GRAD_REDUCE) {
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) acc[ACC ? i : 0][c] += comp(g[i], c);
-                }
-            }
-        }
+        for (int i = 0; i < NIN; ++i) v[i] = V3T<T>{x[i][0], x[i][1], x[i][2]};
+        const V3T<T> r = shading_normal<BWD, T>(v, k.variant, V3T<T>{go[0], go[1], go[2]}, g);
+        o[0] = r.x; o[1] = r.y; o[2] = r.z;
     }
-    if (ACC) {
-#pragma unroll
-        for (int i = 0; i < NI; ++i) {
-            if (k.in[i].gmode != A3D_BSDF_GRAD_REDUCE) continue;  // (the same in every lane)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const double s = sn_block_sum(acc[ACC ? i : 0][c], red);
-                if (threadIdx.x == 0) reinterpret_cast<double*>(k.in[i].g)[(long long)blockIdx.x * 3 + c] = s;
-            }
-        }
-    }
-}
+};
 
-__global__ __launch_bounds__(THREADS) void sn_finish_kernel(const SnFin f) {
-    __shared__ double red[4];
-    const int i = blockIdx.y;
-    const long long e = blockIdx.x;
-    if (!f.rows[i] || e >= f.ne[i]) return;  // (the same in every lane of the work-group)
-    const long long R = f.R[i];
-    const double* rows = f.rows[i] + e * R * 3;
-    for (int c = 0; c < 3; ++c) {
-        double s = 0.0;
-        for (long long r = threadIdx.x; r < R; r += THREADS) s += rows[r * 3 + c];
-        s = sn_block_sum(s, red);
-        if (threadIdx.x == 0) f.final_[i][e * 3 + c] = (float)s;
-    }
-}
-
-// ---- host side (the rules of bsdf.hip's bsdf_check)
-// d >= the returned k are the dimensions inside a run of `run` consecutive pixels; -1 when no boundary between dimensions gives that run
-int sn_run_dim(const int64_t* shape, int ndim, long long run) {
-    long long prod = 1;
-    if (run == 1) return ndim;
-    for (int d = ndim - 1; d >= 0; --d) {
-        prod *= shape[d];
-        if (prod == run) return d;
-        if (prod > run) return -1;
-    }
-    return -1;
-}
-
-bool sn_const_from(const a3d_bsdf_desc* d, int i, int from) {
-    for (int j = from; j < d->ndim; ++j)
-        if (d->shape[j] > 1 && d->stride[ND * i + j] != 0) return false;
-    return true;
-}
-
-// validates everything that can be validated without touching a pointer; fills k (n == 0: nothing to launch)
-int sn_check(const a3d_bsdf_desc* d, SnK& k, const char* fn, bool bwd, long long* rows) {
-    if (!d) {
-        a3d_set_error("%s: invalid argument: desc", fn);
-        return A3D_EINVAL;
-    }
-    if (d->size < sizeof(a3d_bsdf_desc)) {  // (before any other field is read: a shorter struct does not have them)
-        a3d_set_error("%s: invalid argument: desc->size %u < sizeof(a3d_bsdf_desc) %zu (a caller built against an older header)", fn, d->size,
-                      sizeof(a3d_bsdf_desc));
-        return A3D_EINVAL;
-    }
-#define SN_REQUIRE(cond)                                                \
-    do {                                                                \
-        if (!(cond)) {                                                  \
-            a3d_set_error("%s: invalid argument: %s", fn, #cond);       \
-            return A3D_EINVAL;                                          \
-        }                                                               \
-    } while (0)
+// the op / variant rule of a3d_shading_normal_* between the two halves of the shared check; fills k (n == 0: nothing to launch)
+int sn_check(const a3d_bsdf_desc* d, px::K& k, const char* fn, bool bwd, long long* rows) {
+    if (const int rc = px::check_size(d, fn)) return rc;
     if (d->op != A3D_SHADING_NORMAL || d->variant < 0 || d->variant > 3) {
         a3d_set_error("%s: invalid argument: op %d / variant %d: op must be A3D_SHADING_NORMAL, variant two_sided + 2 * opengl in 0 .. 3", fn, d->op,
                       d->variant);
         return A3D_EINVAL;
     }
-    SN_REQUIRE(d->ndim >= 1 && d->ndim <= A3D_BSDF_MAX_DIMS);
-    long long n = 1;
-    for (int j = 0; j < d->ndim; ++j) {
-        if (d->shape[j] < 0 || d->shape[j] > (1ll << 40)) {
-            a3d_set_error("%s: invalid argument: shape[%d] = %lld", fn, j, (long long)d->shape[j]);
-            return A3D_EINVAL;
-        }
-        n *= d->shape[j];
-        SN_REQUIRE(n <= (1ll << 40));
-    }
-    k.n = n;
-    *rows = 0;
-    if (n == 0) return A3D_OK;
-    SN_REQUIRE(d->seg >= 1 && n % d->seg == 0);
-    const int kseg = sn_run_dim(d->shape, d->ndim, d->seg);
-    SN_REQUIRE(kseg >= 0 /* seg must be the product of trailing dimensions */);
-    k.seg = d->seg;
-    k.bps = (d->seg + TILE - 1) / TILE;
-    SN_REQUIRE((n / d->seg) <= INT_MAX / k.bps);
-    *rows = (n / d->seg) * k.bps;
-    k.variant = d->variant;
-    k.ndim = d->ndim;
-    k.small = n < (1ll << 31);
-    k.any_uniform = k.any_strided = 0;
-    for (int j = 0; j < ND; ++j) k.shape[j] = j < d->ndim ? d->shape[j] : 1;
-    for (int i = 0; i < NI; ++i) {
-        SnIn& in = k.in[i];
-        long long rowstride = 3;
-        bool rows_mode = d->cstride[i] == 1;
-        for (int j = ND - 1; j >= 0; --j) {
-            in.st[j] = j < d->ndim ? d->stride[ND * i + j] : 0;
-            if (j < d->ndim) {
-                if (in.st[j] < 0) {
-                    a3d_set_error("%s: invalid argument: stride[%d][%d] = %lld is negative", fn, i, j, (long long)in.st[j]);
-                    return A3D_EINVAL;
-                }
-                if (d->shape[j] > 1 && in.st[j] != rowstride) rows_mode = false;
-                rowstride *= d->shape[j];
-            }
-        }
-        SN_REQUIRE(d->cstride[i] >= 0);
-        in.p = d->in[i];
-        in.cs = d->cstride[i];
-        in.mode = rows_mode ? MODE_ROWS : sn_const_from(d, i, kseg) ? MODE_UNIFORM : MODE_STRIDED;
-        k.any_uniform |= in.mode == MODE_UNIFORM;
-        k.any_strided |= in.mode == MODE_STRIDED;
-        in.g = nullptr;
-        in.gmode = A3D_BSDF_GRAD_NONE;
-        if (!in.p) {
-            a3d_set_error("%s: invalid argument: in[%d] is NULL", fn, i);
-            return A3D_EINVAL;
-        }
-        if (bwd) {
-            in.gmode = d->g_mode[i];
-            in.g = d->g_in[i];
-            SN_REQUIRE(in.gmode >= A3D_BSDF_GRAD_NONE && in.gmode <= A3D_BSDF_GRAD_REDUCE);
-            if (in.gmode != A3D_BSDF_GRAD_NONE) SN_REQUIRE(d->g_in[i] != nullptr);
-            if (in.gmode == A3D_BSDF_GRAD_REDUCE) {
-                SN_REQUIRE(d->g_final[i] != nullptr && d->seg_div[i] >= 1 && (n / d->seg) % d->seg_div[i] == 0);
-                const int kr = sn_run_dim(d->shape, d->ndim, d->seg * d->seg_div[i]);
-                SN_REQUIRE(kr >= 0 && sn_const_from(d, i, kr) /* a reduced input must be constant over its runs */);
-            }
-        }
-    }
-    k.out = d->out;
-    k.g_out = d->g_out;
-    if (bwd) SN_REQUIRE(d->g_out != nullptr);
-    else SN_REQUIRE(d->out != nullptr);
-#undef SN_REQUIRE
-    return A3D_OK;
+    return px::check(d, k, fn, SnOp::NIN, sn_cin, bwd, rows);
 }
 
 // ---------------------------------------------------------------------------------------------- tangents
@@ -505,51 +267,30 @@ __global__ __launch_bounds__(256) void tg_gather_bwd_kernel(const double* __rest
 }  // namespace
 
 extern "C" int64_t a3d_shading_normal_rows(const a3d_bsdf_desc* desc) {
-    if (!desc || desc->size < sizeof(a3d_bsdf_desc) || desc->op != A3D_SHADING_NORMAL) return -1;
-    if (desc->ndim < 1 || desc->ndim > A3D_BSDF_MAX_DIMS || desc->seg < 1) return -1;
-    long long n = 1;
-    for (int j = 0; j < desc->ndim; ++j) {
-        if (desc->shape[j] < 0 || desc->shape[j] > (1ll << 40)) return -1;
-        n *= desc->shape[j];
-        if (n > (1ll << 40)) return -1;
-    }
-    if (n % desc->seg) return -1;
-    return (n / desc->seg) * ((desc->seg + TILE - 1) / TILE);
+    const int64_t rows = px::rows(desc);  // (>= 0: the descriptor is long enough to have an op)
+    return rows < 0 || desc->op != A3D_SHADING_NORMAL ? -1 : rows;
 }
 
 extern "C" int a3d_shading_normal_fwd(const a3d_bsdf_desc* desc, a3d_stream_t stream) {
-    SnK k;
+    px::K k;
     long long rows;
     const int rc = sn_check(desc, k, __func__, false, &rows);
     if (rc || k.n == 0) return rc;
-    hipLaunchKernelGGL((sn_kernel<false, float>), dim3((unsigned)rows), dim3(THREADS), 0, (hipStream_t)stream, k);
+    hipLaunchKernelGGL((px::kernel<SnOp, false, float>), dim3((unsigned)rows), dim3(px::THREADS), 0, (hipStream_t)stream, k);
     A3D_LAUNCH_CHECK();
     return A3D_OK;
 }
 
 extern "C" int a3d_shading_normal_bwd(const a3d_bsdf_desc* desc, a3d_stream_t stream) {
-    SnK k;
+    px::K k;
     long long rows;
     const int rc = sn_check(desc, k, __func__, true, &rows);
     if (rc || k.n == 0) return rc;
     hipStream_t s = (hipStream_t)stream;
-    SnFin f = {};
-    long long max_e = 0;
-    for (int i = 0; i < NI; ++i) {
-        if (k.in[i].gmode != A3D_BSDF_GRAD_REDUCE) continue;
-        f.rows[i] = reinterpret_cast<const double*>(desc->g_in[i]);
-        f.final_[i] = desc->g_final[i];
-        f.R[i] = desc->seg_div[i] * k.bps;
-        f.ne[i] = (k.n / k.seg) / desc->seg_div[i];
-        if (f.ne[i] > max_e) max_e = f.ne[i];
-    }
-    // (always the double instantiation: see sn_kernel)
-    hipLaunchKernelGGL((sn_kernel<true, double>), dim3((unsigned)rows), dim3(THREADS), 0, s, k);
+    // (always the double instantiation: see SnOp)
+    hipLaunchKernelGGL((px::kernel<SnOp, true, double>), dim3((unsigned)rows), dim3(px::THREADS), 0, s, k);
     A3D_LAUNCH_CHECK();
-    if (max_e == 0) return A3D_OK;
-    hipLaunchKernelGGL(sn_finish_kernel, dim3((unsigned)max_e, NI), dim3(THREADS), 0, s, f);
-    A3D_LAUNCH_CHECK();
-    return A3D_OK;
+    return px::finish_grads(desc, k, SnOp::NIN, sn_cin, s);
 }
 
 extern "C" int a3d_tangents_fwd(const float* v_pos, const float* v_tex, int64_t tex_batch_stride, const float* v_nrm, const int32_t* t_pos_idx,

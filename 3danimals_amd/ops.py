@@ -2454,8 +2454,14 @@ def specular_cubemap_raw(cubemap, roughness, costheta_cutoff, bounds):
 
 
 # ---------------------------------------------------------------------------------------------- shading BSDFs, HDR image loss
-BSDF_OPS = {"lambert": (0, (3, 3), 1), "frostbite_diffuse": (1, (3, 3, 3, 1), 1), "pbr_specular": (2, (3, 3, 3, 3, 1), 3),
-            "pbr_bsdf": (3, (3, 3, 3, 3, 3, 3), 3), "image_loss": (4, (1, 1), 1)}  # name -> (A3D_BSDF_* code, channels per input, of the result)
+# name -> (op code, channels per input, channels of the result, stem of the entry points, KernelTimer tag): every element-wise operator
+# over an a3d_bsdf_desc.  BSDF_OPS / TANGENT_OPS: the rows whose codes include/a3d_bsdf.h / include/a3d_tangent.h define
+PIXEL_OPS = {"lambert": (0, (3, 3), 1, "a3d_bsdf", "[lambert]"), "frostbite_diffuse": (1, (3, 3, 3, 1), 1, "a3d_bsdf", "[frostbite_diffuse]"),
+             "pbr_specular": (2, (3, 3, 3, 3, 1), 3, "a3d_bsdf", "[pbr_specular]"), "pbr_bsdf": (3, (3, 3, 3, 3, 3, 3), 3, "a3d_bsdf", "[pbr_bsdf]"),
+             "image_loss": (4, (1, 1), 1, "a3d_image_loss", None),  # (_ImageLoss tags its calls with the variant)
+             "shading_normal": (_lib.SHADING_NORMAL_OP, (3, 3, 3, 3, 3, 3), 3, "a3d_shading_normal", "")}
+BSDF_OPS = {name: row[:3] for name, row in PIXEL_OPS.items() if row[0] != _lib.SHADING_NORMAL_OP}
+TANGENT_OPS = {name: row[:3] for name, row in PIXEL_OPS.items() if row[0] == _lib.SHADING_NORMAL_OP}
 IMAGE_LOSSES = {"l1": 0, "mse": 1, "smape": 2, "relmse": 3}
 BSDF_MIN_RUN = 256  # a gradient is reduced inside the launch when its input is constant over runs of at least this many pixels
 
@@ -2468,7 +2474,7 @@ class _BsdfPlan:
     _geometry = {}  # (name, shapes, strides) -> the plan's geometry: a training loop calls with the same few layouts every step
 
     def __init__(self, name, inputs):
-        self.code, chans, self.c_out = BSDF_OPS.get(name) or TANGENT_OPS[name]
+        self.code, chans, self.c_out, self.entry, self.tag = PIXEL_OPS[name]
         self.inputs, self.chans = inputs, chans
         key = (name, tuple((t.shape, t.stride()) for t in inputs))
         geo = self._geometry.get(key)
@@ -2577,23 +2583,25 @@ class _BsdfPlan:
         return collect
 
 
-class _Bsdf(torch.autograd.Function):
+class _Pixel(torch.autograd.Function):
+    """ops.bsdf and ops.shading_normal: one launch forward, one backward, through the entry points PIXEL_OPS names."""
+
     @staticmethod
-    def forward(ctx, name, min_roughness, lobe, *inputs):
+    def forward(ctx, name, min_roughness, variant, *inputs):
         plan = _BsdfPlan(name, inputs)
         out = torch.empty((*plan.lead, plan.c_out), dtype=torch.float32, device=inputs[0].device)
         if plan.n:
             d = plan.desc()
-            d.variant, d.min_roughness, d.out = lobe, min_roughness, out.data_ptr()
-            call("a3d_bsdf_fwd", ctypes.byref(d), stream(), tag=f"[{name}]")
-        ctx.cfg = (name, min_roughness, lobe)
+            d.variant, d.min_roughness, d.out = variant, min_roughness, out.data_ptr()
+            call(plan.entry + "_fwd", ctypes.byref(d), stream(), tag=plan.tag)
+        ctx.cfg = (name, min_roughness, variant)
         ctx.save_for_backward(*inputs)
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_out):
-        name, min_roughness, lobe = ctx.cfg
+        name, min_roughness, variant = ctx.cfg
         inputs = ctx.saved_tensors
         plan = _BsdfPlan(name, inputs)
         needs = ctx.needs_input_grad[3:]
@@ -2601,9 +2609,9 @@ class _Bsdf(torch.autograd.Function):
             return (None, None, None) + tuple(torch.zeros_like(t) if n else None for t, n in zip(inputs, needs))
         g_out = f32c(g_out)
         d = plan.desc()
-        d.variant, d.min_roughness, d.g_out = lobe, min_roughness, g_out.data_ptr()
+        d.variant, d.min_roughness, d.g_out = variant, min_roughness, g_out.data_ptr()
         collect = plan.grads(d, needs, g_out.device)
-        call("a3d_bsdf_bwd", ctypes.byref(d), stream(), tag=f"[{name}]")
+        call(plan.entry + "_bwd", ctypes.byref(d), stream(), tag=plan.tag)
         return (None, None, None) + tuple(collect())
 
 
@@ -2623,7 +2631,7 @@ def bsdf(name, inputs, min_roughness=0.08, lobe=0):
         if t.dtype != torch.float32:
             raise ValueError(f"{name}: expected float32 tensors, got {t.dtype}")
     require_device(*inputs, what=name)
-    return _Bsdf.apply(name, float(min_roughness), int(lobe), *inputs)
+    return _Pixel.apply(name, float(min_roughness), int(lobe), *inputs)
 
 
 def _flat_loss_desc(img, target):
@@ -2701,38 +2709,6 @@ def image_loss(img, target, loss="l1", tonemapper="none"):
 
 
 # ---------------------------------------------------------------------------------------------- tangent frame (include/a3d_tangent.h)
-TANGENT_OPS = {"shading_normal": (_lib.SHADING_NORMAL_OP, (3, 3, 3, 3, 3, 3), 3)}  # the call plan is _BsdfPlan's, the op code a3d_tangent.h's
-
-
-class _ShadingNormal(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, variant, *inputs):
-        plan = _BsdfPlan("shading_normal", inputs)
-        out = torch.empty((*plan.lead, 3), dtype=torch.float32, device=inputs[0].device)
-        if plan.n:
-            d = plan.desc()
-            d.variant, d.out = variant, out.data_ptr()
-            call("a3d_shading_normal_fwd", ctypes.byref(d), stream())
-        ctx.variant = variant
-        ctx.save_for_backward(*inputs)
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g_out):
-        inputs = ctx.saved_tensors
-        plan = _BsdfPlan("shading_normal", inputs)
-        needs = ctx.needs_input_grad[1:]
-        if not plan.n:
-            return (None,) + tuple(torch.zeros_like(t) if n else None for t, n in zip(inputs, needs))
-        g_out = f32c(g_out)
-        d = plan.desc()
-        d.variant, d.g_out = ctx.variant, g_out.data_ptr()
-        collect = plan.grads(d, needs, g_out.device)
-        call("a3d_shading_normal_bwd", ctypes.byref(d), stream())
-        return (None,) + tuple(collect())
-
-
 def shading_normal(pos, view_pos, perturbed_nrm, smooth_nrm, smooth_tng, geom_nrm, two_sided_shading=True, opengl=True):
     """prepare_shading_normal of renderutils WITH a tangent-space perturbation as one launch forward and one backward (csrc/tangent.hip,
     include/a3d_tangent.h); the arithmetic is the torch statements of model/render/renderutils/ops.py, operation by operation.
@@ -2746,7 +2722,7 @@ def shading_normal(pos, view_pos, perturbed_nrm, smooth_nrm, smooth_tng, geom_nr
         if not torch.is_tensor(t) or t.dtype != torch.float32:
             raise ValueError(f"shading_normal: expected float32 tensors, got {getattr(t, 'dtype', type(t))}")
     require_device(*inputs, what="shading_normal")
-    return _ShadingNormal.apply(int(bool(two_sided_shading)) + 2 * int(bool(opengl)), *inputs)
+    return _Pixel.apply("shading_normal", 0.0, int(bool(two_sided_shading)) + 2 * int(bool(opengl)), *inputs)  # (no min_roughness: the field stays 0)
 
 
 def _tangent_atlas(v_tex, B):

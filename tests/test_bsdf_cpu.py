@@ -196,7 +196,7 @@ def test_a_short_or_invalid_descriptor_is_refused_before_anything_is_launched():
     refused("a3d_bsdf_bwd", d, "g_in")
     d = _desc(L)  # a reduced gradient of an input that is NOT constant over the run
     d.g_mode[0], d.seg_div[0], d.g_in[0], d.g_final[0] = 2, 1, 0x1000, 0x1000
-    refused("a3d_bsdf_bwd", d, "bsdf_const_from")
+    refused("a3d_bsdf_bwd", d, "in[0]", "REDUCE", "constant over")
     assert lib.a3d_bsdf_rows(ctypes.byref(_desc(L, size=8))) == -1 and lib.a3d_bsdf_rows(ctypes.byref(_desc(L, seg=3))) == -1
     d = _desc(L, ndim=2, seg=3000)
     d.shape[0], d.shape[1] = 5, 3000

@@ -104,7 +104,7 @@ def test_shading_normal_refuses_an_invalid_descriptor_before_anything_is_launche
     refused("a3d_shading_normal_bwd", d, "g_in")
     d = _desc(L)  # a reduced gradient of an input that is NOT constant over the run
     d.g_mode[1], d.seg_div[1], d.g_in[1], d.g_final[1] = 2, 1, FAKE, FAKE
-    refused("a3d_shading_normal_bwd", d, "sn_const_from")
+    refused("a3d_shading_normal_bwd", d, "in[1]", "REDUCE", "constant over")
     # the old surface refuses the new code (it was not loosened), the new rows function has a3d_bsdf_rows' rule
     assert lib.a3d_bsdf_fwd(ctypes.byref(_desc(L)), None) == -1 and "op" in lib.a3d_last_error().decode()
     assert lib.a3d_shading_normal_rows(ctypes.byref(_desc(L, size=8))) == -1 and lib.a3d_shading_normal_rows(ctypes.byref(_desc(L, seg=3))) == -1
