@@ -1,4 +1,4 @@
-"""ctypes binding of liba3d_hip.so (include/a3d.h, include/a3d_bsdf.h, include/a3d_deriv.h, include/a3d_tangent.h).  No fallback: if the library is missing we say so and stop."""
+"""ctypes binding of liba3d_hip.so (include/a3d.h, include/a3d_bsdf.h, include/a3d_deriv.h, include/a3d_tangent.h, include/a3d_reg.h).  No fallback: if the library is missing we say so and stop."""
 from __future__ import annotations
 
 import ctypes
@@ -236,6 +236,19 @@ TANGENT_SIGNATURES = {
 }
 SHADING_NORMAL_OP = 5  # A3D_SHADING_NORMAL
 
+# the entry points of include/a3d_reg.h (same library, same a3d_version(); tests/test_regularizer_cpu.py checks this table against that header)
+REG_SIGNATURES = {
+    "a3d_edge_topology": (_c_int, [_p, _c_int, _c_int, _p, _p, _c_int, _p, _p, _p]),
+    "a3d_reg_partials": (_c_size_t, [_c_int, _c_int]),
+    "a3d_laplace_fwd": (_c_int, [_p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p]),
+    "a3d_laplace_bwd": (_c_int, [_p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p]),
+    "a3d_normal_consistency_fwd": (_c_int, [_p, _p, _p, _p, _c_int, _c_int, _c_int, _p, _p, _p, _p]),
+    "a3d_normal_consistency_bwd": (_c_int, [_p, _p, _p, _p, _p, _p, _p, _c_int, _p, _c_int, _c_int, _c_int, _p, _p, _p]),
+    "a3d_edge_length_fwd": (_c_int, [_p, _p, _p, _p, _c_int, _c_int, _c_int, _p, _p, _p]),
+    "a3d_edge_length_bwd": (_c_int, [_p, _p, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p]),
+}
+EDGE_REPRESENTATIVE, EDGE_WINNER, EDGE_STAND_IN = 1, 2, 4  # A3D_EDGE_* bits of an edge-table row
+
 ABI_VERSION = 404  # a3d_version() of the library these signatures belong to (include/a3d.h)
 _lib = None
 
@@ -254,7 +267,7 @@ def lib():
                 "(or __graft_entry__.build()).  There is no CPU fallback for the HIP hot path."
             )
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(BSDF_SIGNATURES.items()) + list(DERIV_SIGNATURES.items()) + list(TANGENT_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(BSDF_SIGNATURES.items()) + list(DERIV_SIGNATURES.items()) + list(TANGENT_SIGNATURES.items()) + list(REG_SIGNATURES.items()):
             fn = getattr(handle, name)  # AttributeError here == ABI drift
             fn.restype, fn.argtypes = res, args
         if handle.a3d_version() != ABI_VERSION:  # same symbols, other argument lists: a stale build must not be called

@@ -2781,6 +2781,156 @@ def vertex_tangents(v_pos, v_tex, v_nrm, t_pos_idx, t_tex_idx):
     return _Tangents.apply(v_pos, v_nrm, v_tex, tri32, tex32, vertex_face_adjacency(tri32, v_pos.shape[1]))
 
 
+# ---------------------------------------------------------------------------------------------- mesh regularisers (include/a3d_reg.h)
+class EdgeTopology:
+    """The per-occurrence edge table of one triangle list (a3d_edge_topology): int32 [3F,2] rows (A3D_EDGE_* bits, partner face) and the
+    number of unique edges as a device int32 that is never read back.  Built from the vertex -> face lists in one launch."""
+
+    def __init__(self, tri32: torch.Tensor, num_vertices: int, adjacency=None):
+        require_device(tri32, what="edge_topology")
+        F, V = tri32.shape[0], int(num_vertices)
+        self.tri, self.num_vertices = tri32, V
+        self.adjacency = adjacency if adjacency is not None else vertex_face_adjacency(tri32, V)
+        self.table = torch.empty((3 * F, 2), dtype=torch.int32, device=tri32.device)
+        self.num_edges = torch.empty(1, dtype=torch.int32, device=tri32.device)
+        call("a3d_edge_topology", ptr(tri32), F, V, ptr(self.adjacency.off), ptr(self.adjacency.adj), self.adjacency.stride, ptr(self.table),
+             ptr(self.num_edges), stream())
+
+
+_edge_cache = _IdentityCache()
+
+
+def edge_topology(tri32: torch.Tensor, num_vertices: int) -> EdgeTopology:
+    """EdgeTopology of a non-empty triangle list, built on first use and cached per list (as the vertex -> face lists it is built from)."""
+    hit = _edge_cache.peek(tri32)
+    if hit is None or hit.num_vertices != num_vertices:
+        hit = _edge_cache.put(tri32, EdgeTopology(tri32, num_vertices))
+    return hit
+
+
+def _reg_partials(v_pos, n):
+    return torch.empty(_lib.lib().a3d_reg_partials(v_pos.shape[0], n), dtype=torch.float64, device=v_pos.device)
+
+
+class _Laplace(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, v_pos, tri32, adjacency):
+        v_pos = f32c(v_pos)
+        B, V, F = v_pos.shape[0], v_pos.shape[1], tri32.shape[0]
+        scaled = torch.empty((B, V, 3), dtype=torch.float64, device=v_pos.device)
+        loss = torch.empty((), dtype=torch.float32, device=v_pos.device)
+        call("a3d_laplace_fwd", ptr(v_pos), ptr(tri32), ptr(adjacency.off), ptr(adjacency.adj), adjacency.stride, B, V, F, ptr(scaled),
+             ptr(_reg_partials(v_pos, V)), ptr(loss), stream(), tag=f"[B{B}]")
+        ctx.save_for_backward(scaled, tri32)
+        ctx.adjacency = adjacency
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss):
+        scaled, tri32 = ctx.saved_tensors
+        B, V, F = scaled.shape[0], scaled.shape[1], tri32.shape[0]
+        g_v = torch.empty((B, V, 3), dtype=torch.float32, device=scaled.device)
+        call("a3d_laplace_bwd", ptr(f32h(g_loss)), ptr(scaled), ptr(tri32), ptr(ctx.adjacency.off), ptr(ctx.adjacency.adj), ctx.adjacency.stride,
+             B, V, F, ptr(g_v), stream(), tag=f"[B{B}]")
+        return g_v, None, None
+
+
+class _NormalConsistency(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, v_pos, tri32, edges):
+        v_pos = f32c(v_pos)
+        B, V, F = v_pos.shape[0], v_pos.shape[1], tri32.shape[0]
+        stand_in = torch.empty((B, 3), dtype=torch.float64, device=v_pos.device)
+        loss = torch.empty((), dtype=torch.float32, device=v_pos.device)
+        call("a3d_normal_consistency_fwd", ptr(v_pos), ptr(tri32), ptr(edges.table), ptr(edges.num_edges), B, V, F, ptr(stand_in),
+             ptr(_reg_partials(v_pos, F)), ptr(loss), stream(), tag=f"[B{B}]")
+        ctx.save_for_backward(v_pos, stand_in, tri32)
+        ctx.edges = edges
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss):
+        v_pos, stand_in, tri32 = ctx.saved_tensors
+        B, V, F = v_pos.shape[0], v_pos.shape[1], tri32.shape[0]
+        edges, adjacency = ctx.edges, ctx.edges.adjacency
+        scratch = torch.empty((B, F, 9), dtype=torch.float64, device=v_pos.device)
+        g_v = torch.empty_like(v_pos)
+        call("a3d_normal_consistency_bwd", ptr(f32h(g_loss)), ptr(v_pos), ptr(tri32), ptr(edges.table), ptr(edges.num_edges), ptr(adjacency.off),
+             ptr(adjacency.adj), adjacency.stride, ptr(stand_in), B, V, F, ptr(scratch), ptr(g_v), stream(), tag=f"[B{B}]")
+        return g_v, None, None
+
+
+class _EdgeLength(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, v_pos, tri32, edges):
+        v_pos = f32c(v_pos)
+        B, V, F = v_pos.shape[0], v_pos.shape[1], tri32.shape[0]
+        loss = torch.empty((), dtype=torch.float32, device=v_pos.device)
+        call("a3d_edge_length_fwd", ptr(v_pos), ptr(tri32), ptr(edges.table), ptr(edges.num_edges), B, V, F, ptr(_reg_partials(v_pos, F)),
+             ptr(loss), stream(), tag=f"[B{B}]")
+        ctx.save_for_backward(v_pos, tri32)
+        ctx.edges = edges
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss):
+        v_pos, tri32 = ctx.saved_tensors
+        B, V, F = v_pos.shape[0], v_pos.shape[1], tri32.shape[0]
+        edges, adjacency = ctx.edges, ctx.edges.adjacency
+        g_v = torch.empty_like(v_pos)
+        call("a3d_edge_length_bwd", ptr(f32h(g_loss)), ptr(v_pos), ptr(tri32), ptr(edges.table), ptr(edges.num_edges), ptr(adjacency.off),
+             ptr(adjacency.adj), adjacency.stride, B, V, F, ptr(g_v), stream(), tag=f"[B{B}]")
+        return g_v, None, None
+
+
+def _reg_args(what, v_pos, t_pos_idx):
+    """(tri32, empty) after the checks the three regularisers share: v_pos float32 [B,V,3], t_pos_idx an integer [1,F,3] or [F,3], both on
+    the current device."""
+    if not torch.is_tensor(v_pos) or v_pos.dtype != torch.float32:
+        raise ValueError(f"{what}: expected a float32 v_pos, got {getattr(v_pos, 'dtype', type(v_pos))}")
+    if not torch.is_tensor(t_pos_idx) or t_pos_idx.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{what}: expected int32 / int64 indices, got {getattr(t_pos_idx, 'dtype', type(t_pos_idx))}")
+    if v_pos.dim() != 3 or v_pos.shape[2] != 3 or t_pos_idx.dim() not in (2, 3) or t_pos_idx.shape[-1] != 3 or (t_pos_idx.dim() == 3 and t_pos_idx.shape[0] != 1):
+        raise ValueError(f"{what}: v_pos {list(v_pos.shape)}, t_pos_idx {list(t_pos_idx.shape)}; expected [B,V,3] and [1,F,3]")
+    tri32 = tri_int32(t_pos_idx)
+    require_device(v_pos, tri32, what=what)
+    return tri32, tri32.shape[0] == 0 or v_pos.shape[0] == 0 or v_pos.shape[1] == 0
+
+
+def laplace_regularizer(v_pos, t_pos_idx):
+    """laplace_regularizer_const (reference regularizer.py:40-61, with the [B,F,1] index its normaliser evidently means): the mean square
+    of the umbrella term, two launches forward and one backward (csrc/regularizer.hip), double sums in a fixed order -> a float32 scalar
+    with the same bits on every run.  v_pos float32 [B,V,3] on the GPU, t_pos_idx [1,F,3]."""
+    tri32, empty = _reg_args("laplace_regularizer", v_pos, t_pos_idx)
+    if v_pos.numel() == 0:
+        return (v_pos ** 2).mean()  # (the mean of nothing: nan, as the torch statements)
+    if empty:
+        return (v_pos * 0).mean()  # (no face: every term is 0 / 1)
+    return _Laplace.apply(v_pos, tri32, vertex_face_adjacency(tri32, v_pos.shape[1]))
+
+
+def normal_consistency(v_pos, t_pos_idx):
+    """normal_consistency (reference regularizer.py:66-84): mean over the unique edges of (1 - n_col0 . n_col1) / 2, with
+    compute_edge_to_face_mapping's columns as the CPU's sequential index put leaves them (face 0 where no face wrote).  Two launches each
+    way plus one a3d_edge_topology launch on first use of a triangle list; the number of edges stays on the device."""
+    tri32, empty = _reg_args("normal_consistency", v_pos, t_pos_idx)
+    if empty:
+        return v_pos.sum() * float("nan")  # (no edge, or no image: the mean of nothing)
+    return _NormalConsistency.apply(v_pos, tri32, edge_topology(tri32, v_pos.shape[1]))
+
+
+def avg_edge_length(v_pos, t_pos_idx):
+    """avg_edge_length (reference regularizer.py:31-34): the mean length of the unique edges over the batch.  Two launches forward, one
+    backward, plus one a3d_edge_topology launch on first use of a triangle list."""
+    tri32, empty = _reg_args("avg_edge_length", v_pos, t_pos_idx)
+    if empty:
+        return v_pos.sum() * float("nan")
+    return _EdgeLength.apply(v_pos, tri32, edge_topology(tri32, v_pos.shape[1]))
+
+
 # ---------------------------------------------------------------------------------------------- mixed precision
 def _amp_wrap_functions():
     """Every autograd.Function of this module runs its forward with autocast OFF on float32 copies of half-precision inputs, and its
