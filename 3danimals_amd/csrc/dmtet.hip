@@ -1034,15 +1034,18 @@ __global__ __launch_bounds__(256) void dm_bwd_kernel(const float* __restrict__ g
     if (v >= V) return;
     int2 e = edges[vert_edge[v]];
     float sa = sdf[e.x], sb = sdf[e.y];
-    float den = sa - sb, inv = 1.f / den, inv2 = inv * inv;
+    float den = sa - sb, inv = 1.f / den;
     float gx = g_verts[3ll * v], gy = g_verts[3ll * v + 1], gz = g_verts[3ll * v + 2];
     const float* pa = pos + 3ll * e.x;
     const float* pb = pos + 3ll * e.y;
     float g_wa = gx * pa[0] + gy * pa[1] + gz * pa[2];
     float g_wb = gx * pb[0] + gy * pb[1] + gz * pb[2];
-    // w_a = -s_b/den, w_b = s_a/den
-    atomicAdd(g_sdf + e.x, (g_wa - g_wb) * sb * inv2);
-    atomicAdd(g_sdf + e.y, (g_wb - g_wa) * sa * inv2);
+    // w_a = -s_b/den, w_b = s_a/den: d w_b / d s_a = -s_b / den^2, d w_b / d s_b = s_a / den^2 -- as (g / den) * (s / den), never through
+    // 1 / den^2: marching tets is scale invariant, and inv * inv overflows for |sdf| < 2.7e-20 (-> inf for a gradient of 7e18) and
+    // underflows for |sdf| > 1e19; |s / den| <= 1 on a crossing edge, so either factor is in range whenever the gradient is
+    const float gd = (g_wa - g_wb) * inv;
+    atomicAdd(g_sdf + e.x, gd * (sb * inv));
+    atomicAdd(g_sdf + e.y, -gd * (sa * inv));
     if (g_pos) {
         float wa = -sb * inv, wb = sa * inv;
         atomicAdd(g_pos + 3ll * e.x + 0, gx * wa); atomicAdd(g_pos + 3ll * e.x + 1, gy * wa); atomicAdd(g_pos + 3ll * e.x + 2, gz * wa);
