@@ -1,4 +1,4 @@
-"""ctypes binding of liba3d_hip.so (include/a3d.h, include/a3d_bsdf.h, include/a3d_deriv.h, include/a3d_tangent.h, include/a3d_reg.h).  No fallback: if the library is missing we say so and stop."""
+"""ctypes binding of liba3d_hip.so (include/a3d.h, include/a3d_bsdf.h, include/a3d_deriv.h, include/a3d_tangent.h, include/a3d_reg.h, include/a3d_envshade.h).  No fallback: if the library is missing we say so and stop."""
 from __future__ import annotations
 
 import ctypes
@@ -249,6 +249,26 @@ REG_SIGNATURES = {
 }
 EDGE_REPRESENTATIVE, EDGE_WINNER, EDGE_STAND_IN = 1, 2, 4  # A3D_EDGE_* bits of an edge-table row
 
+# the entry points of include/a3d_envshade.h (same library, same a3d_version(); tests/test_envshade_cpu.py checks this table against that header)
+ENVSHADE_SIGNATURES = {
+    "a3d_env_shade_fwd": (_c_int, [_p, _p]),
+    "a3d_env_shade_bwd": (_c_int, [_p, _p]),
+}
+ENV_SHADE_INPUTS = 5  # A3D_ENV_SHADE_INPUTS: pos, normal, kd, ks, view_pos
+ENV_SHADE_MIN_LEVELS = 3  # the level rule divides by levels - 2
+
+
+class EnvShadeDesc(ctypes.Structure):
+    """a3d_env_shade_desc of include/a3d_envshade.h (field for field; tests/test_envshade_cpu.py compares the two)."""
+
+    _fields_ = [("size", ctypes.c_uint32), ("levels", ctypes.c_int32), ("diffuse_size", ctypes.c_int32), ("fg_height", ctypes.c_int32),
+                ("fg_width", ctypes.c_int32), ("specular", ctypes.c_int32), ("mtx_batch", ctypes.c_int32), ("B", ctypes.c_int32),
+                ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("min_roughness", ctypes.c_float), ("max_roughness", ctypes.c_float),
+                ("spec_size", ctypes.c_int32 * 16), ("diffuse", _p), ("spec", _p * 16), ("fg", _p), ("mtx", _p), ("g_diffuse", _p),
+                ("g_spec", _p * 16), ("in", _p * 5), ("pixel_stride", ctypes.c_int64 * 5), ("image_stride", ctypes.c_int64 * 5), ("out", _p),
+                ("g_out", _p), ("g_in", _p * 4)]
+
+
 ABI_VERSION = 404  # a3d_version() of the library these signatures belong to (include/a3d.h)
 _lib = None
 
@@ -267,7 +287,7 @@ def lib():
                 "(or __graft_entry__.build()).  There is no CPU fallback for the HIP hot path."
             )
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(BSDF_SIGNATURES.items()) + list(DERIV_SIGNATURES.items()) + list(TANGENT_SIGNATURES.items()) + list(REG_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(BSDF_SIGNATURES.items()) + list(DERIV_SIGNATURES.items()) + list(TANGENT_SIGNATURES.items()) + list(REG_SIGNATURES.items()) + list(ENVSHADE_SIGNATURES.items()):
             fn = getattr(handle, name)  # AttributeError here == ABI drift
             fn.restype, fn.argtypes = res, args
         if handle.a3d_version() != ABI_VERSION:  # same symbols, other argument lists: a stale build must not be called

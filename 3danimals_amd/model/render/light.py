@@ -1,6 +1,8 @@
 """Light sources -- reference model/render/light.py: the directional light of the hot path (:169-193) and the split-sum environment
 light (:27-162), whose prefilters run as HIP kernels (renderutils.diffuse_cubemap / specular_cubemap, csrc/envlight.hip) and whose
-lookups go through ops.texture.  load_env / save_env_map stay the reference's (they need its image I/O).
+shade() is one HIP launch each way (ops.env_shade, csrc/envshade.hip; its torch statements, with the lookups through ops.texture, stay
+as the specification and as the route of everything the kernel does not take).  load_env / save_env_map stay the reference's (they
+need its image I/O).
 """
 import math
 import os
@@ -61,6 +63,8 @@ class cubemap_mip(torch.autograd.Function):
     def backward(ctx, dout):
         return ops.cube_box_down_adjoint(dout)
 
+
+HIP_ENV_SHADE = True  # EnvironmentLight.shade on CUDA float32 tensors: one fused launch each way (False: the torch statements, ~20 launches)
 
 FG_RES = 256
 FG_PHI, FG_XI = 16, 64  # quadrature of fg_table: azimuths over the half circle x radial samples
@@ -167,6 +171,32 @@ class EnvironmentLight(torch.nn.Module):
         return torch.mean(torch.abs(self.base - white))
 
     def shade(self, gb_pos, gb_normal, kd, ks, view_pos, specular=True):
+        """Split-sum shading of the G-buffers [B,H,W,3] (reference light.py:90-128).  CUDA float32 tensors with 3-channel maps and at least
+        three specular levels take ops.env_shade, one launch forward and one backward; everything else -- CPU tensors, float64, other
+        shapes, a lookup transform that requires grad, HIP_ENV_SHADE = False (which a double backward needs) -- takes _shade_torch, the
+        statements the kernel restates."""
+        if HIP_ENV_SHADE and self._fused_ok(gb_pos, gb_normal, kd, ks, view_pos):
+            mtx = None if self.mtx is None else torch.as_tensor(self.mtx, dtype=torch.float32, device=gb_pos.device)
+            return ops.env_shade(self.diffuse, self.specular, _fg_lut(gb_pos.device) if specular else None, gb_pos, gb_normal, kd, ks, view_pos,
+                                 mtx=mtx, specular=bool(specular), min_roughness=self.MIN_ROUGHNESS, max_roughness=self.MAX_ROUGHNESS)
+        return self._shade_torch(gb_pos, gb_normal, kd, ks, view_pos, specular)
+
+    def _fused_ok(self, gb_pos, gb_normal, kd, ks, view_pos):
+        ok = lambda t: torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.shape[-1] == 3
+        if not all(ok(t) for t in (gb_pos, gb_normal, kd, ks, view_pos)):
+            return False
+        if not (gb_pos.shape == gb_normal.shape == kd.shape == ks.shape and all(v in (1, n) for v, n in zip(view_pos.shape, gb_pos.shape))):
+            return False
+        maps = [self.diffuse] + list(self.specular)
+        if len(maps) < 4 or not all(ok(m) and m.shape[0] == 6 and m.shape[1] == m.shape[2] and m.device == gb_pos.device for m in maps):
+            return False
+        if self.mtx is not None:  # (a transform of another shape goes on to the statements, which refuse it)
+            m = self.mtx
+            if not torch.is_tensor(m) or m.requires_grad or m.dim() != 3 or tuple(m.shape[1:]) != (4, 4) or m.shape[0] not in (1, gb_pos.shape[0]):
+                return False
+        return True
+
+    def _shade_torch(self, gb_pos, gb_normal, kd, ks, view_pos, specular=True):
         wo = util.safe_normalize(view_pos - gb_pos)
 
         if specular:

@@ -2931,6 +2931,168 @@ def avg_edge_length(v_pos, t_pos_idx):
     return _EdgeLength.apply(v_pos, tri32, edge_topology(tri32, v_pos.shape[1]))
 
 
+# ---------------------------------------------------------------------------------------------- environment-lit shading (include/a3d_envshade.h)
+class _EnvShadePlan:
+    """How the five per-pixel inputs of env_shade reach the library: per input the element strides between pixels and between images
+    (0 = broadcast), or "copy" where the strides cannot say it (a row stride that is not W pixel strides, a channel stride other than 1,
+    an input broadcast along H or W only), and the filled descriptors.  Cached per (shapes, strides): a training loop calls with the
+    same few layouts every step, and a call then copies a descriptor and sets its pointers."""
+
+    _geometry = {}
+
+    def __init__(self, inputs):
+        key = tuple((tuple(t.shape), t.stride()) for t in inputs)
+        geo = self._geometry.get(key)
+        if geo is None:
+            if len(self._geometry) > 256:
+                self._geometry.clear()
+            geo = self._geometry[key] = self._plan(inputs) + ({},)
+        self.bhw, self.strides, self.templates = geo
+
+    @staticmethod
+    def _plan(inputs):
+        for t in inputs:
+            if t.dim() != 4 or t.shape[-1] != 3:
+                raise ValueError(f"env_shade: a per-pixel input must have shape [B, H, W, 3], got {list(t.shape)}")
+        B, H, W = torch.broadcast_shapes(*[t.shape[:-1] for t in inputs])
+        strides = []
+        for t in inputs:
+            b, h, w, _ = t.shape
+            img = 0 if b == 1 else t.stride(0)
+            if h == 1 and w == 1:
+                pix = 0
+            elif (h, w) != (H, W) or (h > 1 and w > 1 and t.stride(1) != w * t.stride(2)):
+                pix = None
+            else:
+                pix = t.stride(2) if w > 1 else t.stride(1)
+            ok = pix is not None and t.stride(3) == 1 and pix >= 0 and img >= 0
+            strides.append((pix, img) if ok else None)  # None: an expanded contiguous copy, strides (3, 3 H W)
+        return (B, H, W), strides
+
+    def resolve(self, inputs):
+        """-> the tensors the descriptor points at: the inputs, or an expanded contiguous copy where the strides cannot say the layout."""
+        B, H, W = self.bhw
+        return [t if s is not None else t.expand(B, H, W, 3).contiguous() for t, s in zip(inputs, self.strides)]
+
+    def desc(self, cfg, maps, tensors):
+        """The descriptor of a call: every field that follows from (cfg, map sizes, shapes, strides) is filled once per plan and copied;
+        a call sets its pointers."""
+        diffuse, fg, mtx, spec = maps
+        key = (cfg, diffuse.shape[1], None if fg is None else (fg.shape[1], fg.shape[2]), None if mtx is None else mtx.shape[0],
+               tuple(t.shape[1] for t in spec))
+        tmpl = self.templates.get(key)
+        if tmpl is None:
+            specular, lo, hi, n_spec = cfg
+            B, H, W = self.bhw
+            tmpl = _lib.EnvShadeDesc(size=ctypes.sizeof(_lib.EnvShadeDesc), levels=n_spec, diffuse_size=diffuse.shape[1], specular=int(specular),
+                                     mtx_batch=0 if mtx is None else mtx.shape[0], B=B, H=H, W=W, min_roughness=lo, max_roughness=hi)
+            if fg is not None:
+                tmpl.fg_height, tmpl.fg_width = fg.shape[1], fg.shape[2]
+            for l, t in enumerate(spec):
+                tmpl.spec_size[l] = t.shape[1]
+            for i, st in enumerate(self.strides):
+                tmpl.pixel_stride[i], tmpl.image_stride[i] = st if st is not None else (3, 3 * H * W)
+            if len(self.templates) > 16:
+                self.templates.clear()
+            self.templates[key] = tmpl
+        d = _lib.EnvShadeDesc.from_buffer_copy(tmpl)
+        d.diffuse, d.fg, d.mtx = diffuse.data_ptr(), ptr(fg), ptr(mtx)
+        for l, t in enumerate(spec):
+            d.spec[l] = t.data_ptr()
+        ins = getattr(d, "in")
+        for i, t in enumerate(tensors):
+            ins[i] = t.data_ptr()
+        return d
+
+
+class _EnvShade(torch.autograd.Function):
+    """ops.env_shade: one launch forward (a3d_env_shade_fwd), one backward (a3d_env_shade_bwd); nothing is saved but the inputs."""
+
+    @staticmethod
+    def forward(ctx, cfg, diffuse, fg, mtx, pos, nrm, kd, ks, view, *spec):
+        ctx.set_materialize_grads(False)
+        inputs = (pos, nrm, kd, ks, view)
+        plan = _EnvShadePlan(inputs)
+        B, H, W = plan.bhw
+        out = torch.empty((B, H, W, 3), dtype=torch.float32, device=pos.device)
+        tensors = plan.resolve(inputs)
+        if out.numel():
+            d = plan.desc(cfg, (diffuse, fg, mtx, spec), tensors)
+            d.out = out.data_ptr()
+            call("a3d_env_shade_fwd", ctypes.byref(d), stream())
+        ctx.cfg, ctx.shapes, ctx.n_spec, ctx.plan = cfg, [t.shape for t in inputs], len(spec), plan
+        ctx.save_for_backward(diffuse, fg, mtx, *tensors, *spec)  # (the tensors the kernel read: a copy made above is not made again)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out):
+        none = (None,) * (9 + ctx.n_spec)
+        if g_out is None:
+            return none
+        diffuse, fg, mtx, *rest = ctx.saved_tensors
+        tensors, spec = rest[:5], rest[5:]
+        needs = ctx.needs_input_grad
+        dev = g_out.device
+        plan = ctx.plan  # (the forward's: the saved tensors are the ones it resolved, its strides are theirs)
+        B, H, W = plan.bhw
+        need_in = [needs[4] or needs[8], needs[5], needs[6], needs[7]]  # g_view is -g_pos
+        g_dif = torch.zeros_like(diffuse) if needs[1] else None
+        g_spec = [torch.zeros_like(t) if needs[9 + l] and ctx.cfg[0] else None for l, t in enumerate(spec)]
+        g_in = [torch.empty((B, H, W, 3), dtype=torch.float32, device=dev) if n else None for n in need_in]
+        if g_out.numel():
+            d = plan.desc(ctx.cfg, (diffuse, fg, mtx, spec), tensors)
+            d.g_out = f32h(g_out).data_ptr()
+            d.g_diffuse = ptr(g_dif)
+            for l, g in enumerate(g_spec):
+                d.g_spec[l] = ptr(g)
+            for j, g in enumerate(g_in):
+                d.g_in[j] = ptr(g)
+            call("a3d_env_shade_bwd", ctypes.byref(d), stream())
+        fit = lambda g, shape: g.sum_to_size(shape)
+        g_pos, g_nrm, g_kd, g_ks = g_in
+        return (None, g_dif, None, None,
+                fit(g_pos, ctx.shapes[0]) if needs[4] else None, fit(g_nrm, ctx.shapes[1]) if needs[5] else None,
+                fit(g_kd, ctx.shapes[2]) if needs[6] else None, fit(g_ks, ctx.shapes[3]) if needs[7] else None,
+                fit(-g_pos, ctx.shapes[4]) if needs[8] else None,
+                *[(torch.zeros_like(t) if g is None else g) if needs[9 + l] else None for l, (t, g) in enumerate(zip(spec, g_spec))])
+
+
+def env_shade(diffuse, specular_levels, fg, gb_pos, gb_normal, kd, ks, view_pos, mtx=None, specular=True, min_roughness=0.08, max_roughness=0.5):
+    """EnvironmentLight.shade (model/render/light.py, reference light.py:90-128) as ONE launch forward and one backward (csrc/envshade.hip,
+    include/a3d_envshade.h): the statements of light.py operation by operation in float32, the three lookups by ops.texture's own device
+    code (its docstring is their specification).
+
+    diffuse [6,S,S,3]; specular_levels: at least 3 maps [6,S_l,S_l,3] under the halving rule; fg [1,Hf,Wf,2] (light._fg_lut); all float32
+    on the GPU, contiguous (a copy is made otherwise).  gb_pos, gb_normal, kd, ks, view_pos: float32 [b,h,w,3], each either the full
+    [B,H,W,3] or broadcast over the image ([B,1,1,3], [1,1,1,3]) or the batch; read in place through their strides (a slice
+    ``all_tex[..., 3:6]`` is not copied).  mtx: None or a float32 [1,4,4] / [B,4,4] lookup transform, whose 3 x 3 part rotates both
+    lookup directions; it receives no gradient.  min_roughness / max_roughness: the lo / hi of the level rule (get_mip).  -> [B,H,W,3].
+
+    Gradients: gb_pos, gb_normal, kd, ks, one row per pixel, bit-identical run to run; view_pos = the sum of -g_pos over what it is
+    broadcast along; diffuse and every specular level, summed in LDS per work-group where the level is at most 16 x 16 and with
+    ops.texture's in-wave merge otherwise (float atomics: the last bits depend on the order).  Subgradients at the clamps are autograd's.
+    The FG table gets none.  No double backward."""
+    spec = list(specular_levels)
+    pix = (gb_pos, gb_normal, kd, ks, view_pos)
+    maps = [diffuse] + spec + ([fg] if fg is not None else []) + ([mtx] if mtx is not None else [])
+    for t in list(pix) + maps:
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise ValueError(f"env_shade: expected float32 tensors, got {getattr(t, 'dtype', type(t))}")
+    for t in [diffuse] + spec:
+        if t.dim() != 4 or t.shape[0] != 6 or t.shape[1] != t.shape[2] or t.shape[3] != 3:
+            raise ValueError(f"env_shade: a map must have shape [6, S, S, 3], got {list(t.shape)}")
+    if specular and (fg is None or fg.dim() != 4 or fg.shape[0] != 1 or fg.shape[3] != 2):
+        raise ValueError(f"env_shade: the FG table must have shape [1, H, W, 2], got {None if fg is None else list(fg.shape)}")
+    require_device(*pix, *maps, what="env_shade")
+    b = torch.broadcast_shapes(*[t.shape[:-1] for t in pix])[0] if all(t.dim() == 4 for t in pix) else 0
+    if mtx is not None and (mtx.dim() != 3 or tuple(mtx.shape[1:]) != (4, 4) or mtx.shape[0] not in (1, b)):
+        raise ValueError(f"env_shade: the lookup transform must be [1,4,4] or [{b},4,4], got {list(mtx.shape)}")
+    cfg = (bool(specular), float(min_roughness), float(max_roughness), len(spec))
+    return _EnvShade.apply(cfg, diffuse.contiguous(), None if fg is None else fg.contiguous(), None if mtx is None else mtx.detach().contiguous(),
+                           *pix, *[t.contiguous() for t in spec])
+
+
 # ---------------------------------------------------------------------------------------------- mixed precision
 def _amp_wrap_functions():
     """Every autograd.Function of this module runs its forward with autocast OFF on float32 copies of half-precision inputs, and its
