@@ -156,21 +156,138 @@ __device__ __forceinline__ int a3d_run_scan(int* a, int* dst, int lo, int hi, in
     return run;
 }
 
-// inclusive prefix sum over the 64 lanes of a wave in six DPP additions (within rows of 16: row_shr 1, 2, 4, 8; across rows: row_bcast 15,
-// 31) -- VALU only, no LDS crossbar (six ds_bpermute round trips in the __shfl_up form)
+// ---- cross-lane scans, sums and exchanges: the one copy of each idiom that several kernels share.  (Left where
+// they are, each with one user: the quad broadcasts of skin.hip, the strided scan of rs_tri_kernel, the arg-min butterfly of bones.hip.)
+// What all of them require: the lanes that exchange values reach the call TOGETHER -- the whole wave, in wave-uniform control flow,
+// for everything built on DPP (the scans, a3d_lane_xor, the quad / row sums); the whole aligned group of WIDTH lanes for
+// a3d_group_sum.  A lane that is switched off contributes nothing defined and the others read it all the same: the result is
+// silently wrong, nothing faults.  The two a3d_block_* helpers contain barriers: EVERY thread of the work-group must arrive, or the
+// work-group hangs.  They take work-groups of whole waves, numbered by threadIdx.x alone.
+
+// DPP controls (the lane a value is read from), named once
+enum {
+    A3D_DPP_QUAD_XOR1 = 0xB1,        // quad_perm [1,0,3,2]: lane ^ 1
+    A3D_DPP_QUAD_XOR2 = 0x4E,        // quad_perm [2,3,0,1]: lane ^ 2
+    A3D_DPP_ROW_ROR8 = 0x128,        // row_ror:8: lane ^ 8
+    A3D_DPP_ROW_HALF_MIRROR = 0x141, // row_half_mirror: lane ^ 7
+    A3D_DPP_ROW_MIRROR = 0x140,      // row_mirror: lane ^ 15
+    A3D_DPP_ROW_SHR = 0x110,         // + n: row_shr:n, lane - n of the same row of 16 (none: the destination keeps `old`)
+    A3D_DPP_ROW_BCAST15 = 0x142,     // lane 15 of every row to the next row
+    A3D_DPP_ROW_BCAST31 = 0x143      // lane 31 to rows 2 and 3
+};
+template <int CTRL>
+__device__ __forceinline__ int a3d_dpp(int x) { return __builtin_amdgcn_mov_dpp(x, CTRL, 0xF, 0xF, true); }
+template <int CTRL>
+__device__ __forceinline__ float a3d_dpp(float x) { return __int_as_float(a3d_dpp<CTRL>(__float_as_int(x))); }
+
+// the value of lane ^ M: a register move (DPP) where the pattern exists, ds_bpermute otherwise.  No barrier, no LDS words.
+template <int M>
+__device__ __forceinline__ int a3d_lane_xor(int x) {
+    if (M == 1) return a3d_dpp<A3D_DPP_QUAD_XOR1>(x);
+    if (M == 2) return a3d_dpp<A3D_DPP_QUAD_XOR2>(x);
+    if (M == 8) return a3d_dpp<A3D_DPP_ROW_ROR8>(x);
+    return __shfl_xor(x, M, 64);
+}
+template <int M>
+__device__ __forceinline__ float a3d_lane_xor(float x) { return __int_as_float(a3d_lane_xor<M>(__float_as_int(x))); }
+
+// sum / maximum over the aligned quad, sum over the aligned row of 16, in every lane of it: two / four DPP moves, in this order.  No
+// barrier, no LDS words.
+__device__ __forceinline__ float a3d_quad_sum(float r) {
+    r += a3d_dpp<A3D_DPP_QUAD_XOR1>(r);
+    r += a3d_dpp<A3D_DPP_QUAD_XOR2>(r);
+    return r;
+}
+__device__ __forceinline__ float a3d_quad_max(float m) {
+    m = fmaxf(m, a3d_dpp<A3D_DPP_QUAD_XOR1>(m));
+    m = fmaxf(m, a3d_dpp<A3D_DPP_QUAD_XOR2>(m));
+    return m;
+}
+__device__ __forceinline__ float a3d_row16_sum(float r) {
+    r = a3d_quad_sum(r);
+    r += a3d_dpp<A3D_DPP_ROW_HALF_MIRROR>(r);
+    r += a3d_dpp<A3D_DPP_ROW_MIRROR>(r);
+    return r;
+}
+
+// butterfly sum over every aligned group of WIDTH lanes (a power of two up to 64), in every lane of it; the offsets descend from WIDTH / 2,
+// which fixes the order of a floating-point sum.  Only the group's own lanes must arrive together (the exchange is ds_bpermute): groups
+// of one wave may sit in different trips of a loop.  No barrier, no LDS words.
+template <int WIDTH = 64, typename T>
+__device__ __forceinline__ T a3d_group_sum(T v) {
+#pragma unroll
+    for (int o = WIDTH / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ float a3d_wave_sum(float v) { return a3d_group_sum<64>(v); }
+
+// sum over the work-group, in every thread, in a fixed order: the butterfly per wave, then red[0] + red[1] + .. + red[WAVES-1] from the
+// left.  (Starting from red[0] and not from zero: a sum whose terms are all -0 stays -0.)  Two barriers -- one BEFORE red is written,
+// so the WAVES words of red may be handed to the next call right away, and one behind.
+template <int WAVES, typename T>
+__device__ __forceinline__ T a3d_block_sum(T v, T* red) {
+    v = a3d_group_sum<64>(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    T t = red[0];
+#pragma unroll
+    for (int w = 1; w < WAVES; ++w) t += red[w];
+    return t;
+}
+
+// inclusive prefix sum within rows of 16 lanes (row_shr 1, 2, 4, 8), and over the 64 lanes of a wave (plus row_bcast 15, 31): four / six
+// DPP additions -- VALU only, no LDS crossbar (six ds_bpermute round trips in the __shfl_up form).  No barrier, no LDS words.
+__device__ __forceinline__ int a3d_row16_incl_scan(int x) {
+    x += __builtin_amdgcn_update_dpp(0, x, A3D_DPP_ROW_SHR + 1, 0xf, 0xf, false);
+    x += __builtin_amdgcn_update_dpp(0, x, A3D_DPP_ROW_SHR + 2, 0xf, 0xf, false);
+    x += __builtin_amdgcn_update_dpp(0, x, A3D_DPP_ROW_SHR + 4, 0xf, 0xf, false);
+    x += __builtin_amdgcn_update_dpp(0, x, A3D_DPP_ROW_SHR + 8, 0xf, 0xf, false);
+    return x;
+}
 __device__ __forceinline__ int a3d_wave_incl_scan(int x) {
-    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, false);  // row_shr:1
-    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xf, 0xf, false);  // row_shr:2
-    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xf, 0xf, false);  // row_shr:4
-    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xf, 0xf, false);  // row_shr:8
-    x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xa, 0xf, false);  // row_bcast:15 -> rows 1 and 3
-    x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false);  // row_bcast:31 -> rows 2 and 3
+    x = a3d_row16_incl_scan(x);
+    x += __builtin_amdgcn_update_dpp(0, x, A3D_DPP_ROW_BCAST15, 0xa, 0xf, false);  // -> rows 1 and 3
+    x += __builtin_amdgcn_update_dpp(0, x, A3D_DPP_ROW_BCAST31, 0xc, 0xf, false);  // -> rows 2 and 3
     return x;
 }
 
-__device__ __forceinline__ float a3d_wave_sum(float v) {
+// exclusive prefix sum of `mine` over the work-group of WAVES waves (thread order); *total, when asked for: the sum over the whole
+// work-group, in every thread.  ONE barrier, between the waves' totals going to s_wave[0..WAVES) and their being read: s_wave may be
+// written again only behind a further barrier (or by a further call that itself comes behind one).  Pass `total` as a literal
+// nullptr or the address of a local: the choice between the two loops below is then made when the call is inlined; a pointer only
+// known at run time would keep both.
+template <int WAVES>
+__device__ __forceinline__ int a3d_block_excl_scan(int mine, int* s_wave, int* total = nullptr) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int incl = a3d_wave_incl_scan(mine);
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    int excl = incl - mine;
+    if (total) {
+        int t = 0;
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
+        for (int w = 0; w < WAVES; ++w) {
+            if (w < wave) excl += s_wave[w];
+            t += s_wave[w];
+        }
+        *total = t;
+    } else {
+        for (int w = 0; w < wave; ++w) excl += s_wave[w];
+    }
+    return excl;
+}
+
+// eight ints into ascending order in registers: a 19-comparator network
+__device__ __forceinline__ void a3d_sort8(int a[8]) {
+#define A3D_CX(i, j) { const int x = min(a[i], a[j]), y = max(a[i], a[j]); a[i] = x; a[j] = y; }
+    A3D_CX(0, 1) A3D_CX(2, 3) A3D_CX(4, 5) A3D_CX(6, 7)
+    A3D_CX(0, 2) A3D_CX(1, 3) A3D_CX(4, 6) A3D_CX(5, 7)
+    A3D_CX(1, 2) A3D_CX(5, 6) A3D_CX(0, 4) A3D_CX(3, 7)
+    A3D_CX(1, 5) A3D_CX(2, 6)
+    A3D_CX(1, 4) A3D_CX(3, 6)
+    A3D_CX(2, 4) A3D_CX(3, 5)
+    A3D_CX(3, 4)
+#undef A3D_CX
 }
 #endif

@@ -234,19 +234,9 @@ __device__ __forceinline__ int aa_segment_offsets(const int* __restrict__ count,
     const int seg_cap = capacity / AA_SHARDS;
     __shared__ int s_wsum[AA_SHARDS / 64];
     {   // (blockDim.x == 256 == AA_SHARDS in every consumer)
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
         const int c = (int)threadIdx.x < AA_SHARDS ? min(count[threadIdx.x], seg_cap) : 0;
-        int incl = c;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int o = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += o;
-        }
-        if (lane == 63) s_wsum[wave] = incl;
-        __syncthreads();
-        int before = 0;
-        for (int w = 0; w < wave; ++w) before += s_wsum[w];
-        if ((int)threadIdx.x < AA_SHARDS) s_off[threadIdx.x + 1] = before + incl;
+        const int excl = a3d_block_excl_scan<AA_SHARDS / 64>(c, s_wsum);
+        if ((int)threadIdx.x < AA_SHARDS) s_off[threadIdx.x + 1] = excl + c;
         if (threadIdx.x == 0) s_off[0] = 0;
     }
     __syncthreads();
@@ -337,8 +327,7 @@ __global__ __launch_bounds__(256) void aa_bwd_kernel(const float* __restrict__ g
                 dd += gd * (color[p1 * C + c] - color[p0 * C + c]);
             }
         }
-#pragma unroll
-        for (int o = 16; o > 0; o >>= 1) dd += __shfl_xor(dd, o, 64);  // stays inside the 32-lane half
+        dd = a3d_group_sum<32>(dd);  // (a record's 32 lanes are in the same trip)
         if (sub != 0 || clamped || dd == 0.f) continue;
         aa_edge_adjoint(rec, (unsigned)p0, d, di, use1, dd, clip, clip_batch, tri, V, H, W, xh, yh, g_clip);
     }
@@ -658,8 +647,7 @@ __global__ __launch_bounds__(256) void ca_bwd_kernel(CaJob ja, CaJob jb, const A
                 dd += gd * (ca_pre(s, p1, c) - ca_pre(s, p0, c));
             }
         }
-#pragma unroll
-        for (int o = 16; o > 0; o >>= 1) dd += __shfl_xor(dd, o, 64);  // stays inside the 32-lane half
+        dd = a3d_group_sum<32>(dd);  // (a record's 32 lanes are in the same trip)
         if (sub != 0 || clamped || dd == 0.f) continue;
         aa_edge_adjoint(rec, p0, d, di, use1, dd, clip, clip_batch, tri, V, H, W, xh, yh, g_clip);
     }

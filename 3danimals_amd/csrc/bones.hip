@@ -98,15 +98,6 @@ __device__ __forceinline__ float eb_unkey(unsigned k) { return __uint_as_float((
 __device__ __forceinline__ float eb_lerp(float a, float b, float w) { return w < 0.5f ? a + w * (b - a) : b - (b - a) * (1.f - w); }  // torch.lerp
 
 struct EbArg { float v; int i; };
-__device__ __forceinline__ float eb_block_sum(float v, float* s_f) {
-    v = a3d_wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s_f[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float t = 0.f;
-    for (int w = 0; w < EB_THREADS / 64; ++w) t += s_f[w];
-    return t;
-}
 
 // the values of ranks s_rank[0..NG*mg) (0-based, ascending order): targets [g mg, (g+1) mg) among the values f(i, g), i in 0..total -- a
 // radix select, all targets in the same four passes over the data.  Targets whose prefixes agree so far (the two neighbours a quantile

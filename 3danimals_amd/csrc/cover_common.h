@@ -23,9 +23,7 @@ __device__ __forceinline__ int cv_block_offset_wave0(const int* __restrict__ blo
     const int lane = threadIdx.x & 63;
     int mine = lane < r ? block_count[g * A3D_COVER_GROUP + lane] : 0;
     for (int j = lane; j < g; j += 64) mine += group_sum[(long long)j * A3D_COVER_GROUP_STRIDE];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
-    return mine;
+    return a3d_group_sum(mine);
 }
 
 #endif

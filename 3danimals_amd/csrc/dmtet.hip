@@ -248,7 +248,7 @@ __global__ __launch_bounds__(DM_THREADS) void dm_count_kernel(const void* __rest
 // path between the count and the emit.  Here every work-group of the culled count launch publishes its block sums as device-scope
 // atomics (dm_put) and takes a ticket; the one that draws the LAST ticket acquires and scans: wave w owns
 // array w (edge blocks, one-triangle tets, two-triangle tets, 1024-vertex chunks of the surface-vertex plane) as rows of 64 consecutive
-// sums -- every row loaded up front (coalesced), scanned with shuffles, chained through a wave-uniform carry: no LDS, no barrier, for
+// sums -- every row loaded up front (coalesced), scanned with DPP additions, chained through a wave-uniform carry: no LDS, no barrier, for
 // up to DM_TAIL_ROWS * 64 sums per array.  Larger grids keep the separate launch (its 1024 threads and 96 KB of LDS are what 15k sums need).
 // The chunk popcounts of the vertex plane are taken by all four waves first (8 lanes per 128-byte chunk) into LDS.
 #define DM_TAIL_ROWS 32
@@ -291,7 +291,7 @@ __device__ __forceinline__ void dm_scan_tail(int* __restrict__ blk_e, int* __res
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 int c = __popc(x[k].x) + __popc(x[k].y) + __popc(x[k].z) + __popc(x[k].w);
-                c += __shfl_xor(c, 1, 64); c += __shfl_xor(c, 2, 64); c += __shfl_xor(c, 4, 64);
+                c = a3d_group_sum<8>(c);
                 if ((lane & 7) == 0 && i0 + DM_THREADS * k < n16) s_chunk[(i0 + DM_THREADS * k) >> 3] = c;
             }
         }
@@ -558,7 +558,7 @@ __global__ __launch_bounds__(1024) void dm_scan_kernel(int* __restrict__ blk_e, 
                                                        int* __restrict__ tlocal) {
     __shared__ int s_wave[16];
     __shared__ int s_arr[DM_SCAN_LDS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
     const int which = blockIdx.x;
     // the valence counters of the mesh this extraction is about to emit (a3d_dmtet_emit: topo_count), zeroed here: no memset launch
     for (int z = blockIdx.x * 1024 + tid; z < n_clear; z += gridDim.x * 1024) clear[z] = 0;
@@ -577,12 +577,7 @@ __global__ __launch_bounds__(1024) void dm_scan_kernel(int* __restrict__ blk_e, 
             const unsigned long long odd = pa.x ^ pa.y ^ pb.x ^ pb.y;
             c = __popcll(odd) | (__popcll(~odd & (pa.x | pa.y | pb.x | pb.y) & ~(pa.x & pa.y & pb.x & pb.y)) << 16);
         }
-        int incl = c;  // (both halves at once: neither sum reaches 2^16)
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) {
-            const int up = __shfl_up(incl, o, 16);
-            if ((lane & 15) >= o) incl += up;
-        }
+        const int incl = a3d_row16_incl_scan(c);  // (both halves at once: neither sum reaches 2^16)
         if (is_edge) {
             if (w < (long long)nbe * 16) wlocal[w] = incl - c;
         } else if (w < (long long)nbt * 16) tlocal[w] = incl - c;
@@ -602,7 +597,7 @@ __global__ __launch_bounds__(1024) void dm_scan_kernel(int* __restrict__ blk_e, 
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
                     int c = __popc(x[k].x) + __popc(x[k].y) + __popc(x[k].z) + __popc(x[k].w);
-                    c += __shfl_xor(c, 1, 64); c += __shfl_xor(c, 2, 64); c += __shfl_xor(c, 4, 64);
+                    c = a3d_group_sum<8>(c);
                     if ((lane & 7) == 0 && i0 + 1024 * k < n16) s_arr[(i0 + 1024 * k) >> 3] = c;
                 }
             }
@@ -611,16 +606,7 @@ __global__ __launch_bounds__(1024) void dm_scan_kernel(int* __restrict__ blk_e, 
             const int lo = min(tid * per, nvc), hi = min(lo + per, nvc);
             int mine = 0;
             for (int i = lo; i < hi; ++i) mine += s_arr[i];
-            int incl = mine;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                int up = __shfl_up(incl, o, 64);
-                if (lane >= o) incl += up;
-            }
-            if (lane == 63) s_wave[wave] = incl;
-            __syncthreads();
-            int run = incl - mine;
-            for (int w = 0; w < wave; ++w) run += s_wave[w];
+            int run = a3d_block_excl_scan<16>(mine, s_wave);
             for (int i = lo; i < hi; ++i) { const int v = s_arr[i]; s_arr[i] = run; run += v; }
             __syncthreads();
             for (int i = tid; i < nvc; i += 1024) vchunk[i] = s_arr[i];
@@ -637,16 +623,7 @@ __global__ __launch_bounds__(1024) void dm_scan_kernel(int* __restrict__ blk_e, 
             vchunk[c] = n;
         }
         const int mine = a3d_run_sum(vchunk, lo, hi);  // (this thread's own stores)
-        int incl = mine;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            int up = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += up;
-        }
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        int run = incl - mine;
-        for (int w = 0; w < wave; ++w) run += s_wave[w];
+        int run = a3d_block_excl_scan<16>(mine, s_wave);
         run = a3d_run_scan<false>(vchunk, vchunk, lo, hi, run);
         if (tid == 1023) counts[3] = run;
         return;
@@ -674,16 +651,7 @@ __global__ __launch_bounds__(1024) void dm_scan_kernel(int* __restrict__ blk_e, 
     int mine = 0;
     if (staged) for (int i = lo; i < hi; ++i) mine += s_arr[i];
     else mine = a3d_run_sum(arr, lo, hi);
-    int incl = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        int up = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += up;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int run = incl - mine;
-    for (int w = 0; w < wave; ++w) run += s_wave[w];
+    int run = a3d_block_excl_scan<16>(mine, s_wave);
     if (staged) {
         for (int i = lo; i < hi; ++i) { const int v = s_arr[i]; s_arr[i] = run; run += v; }
         __syncthreads();
@@ -718,15 +686,10 @@ __device__ __forceinline__ void dm_surface_vertices_chunk(int c, unsigned* __res
         for (int z = threadIdx.x; z < 3 * (rows - n_true); z += blockDim.x) pts[3ll * n_true + z] = 0.f;
     }
     unsigned mine = 0;
-    if (threadIdx.x < 64) {  // (first wave) exclusive prefix of the 32 word popcounts through shuffles
+    if (threadIdx.x < 64) {  // (first wave, whole) exclusive prefix of the 32 word popcounts; lanes 32.. hold 0
         mine = threadIdx.x < 32 ? vbits[32ll * c + threadIdx.x] : 0u;
         const int n = __popc(mine);
-        int incl = n;
-#pragma unroll
-        for (int o = 1; o < 32; o <<= 1) {
-            const int up = __shfl_up(incl, o, 64);
-            if ((int)threadIdx.x >= o) incl += up;
-        }
+        const int incl = a3d_wave_incl_scan(n);
         if (threadIdx.x < 32) s_pre[threadIdx.x] = incl - n;
     }
     __syncthreads();
@@ -952,7 +915,7 @@ __global__ __launch_bounds__(DM_THREADS) void dm_emit_words_kernel(const float* 
     __shared__ int s_pre[32];
     __shared__ unsigned short s_items[DM_THREADS * 64];  // (word of this work-group) << 6 | bit, 32 KB
     __shared__ int s_wave[DM_THREADS / A3D_WAVE];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     bool faces_live = F > 0;
     if (dev_counts) {
         const int dV = dev_counts[0], d1 = dev_counts[1], d2 = dev_counts[2], dS = dev_counts[3];
@@ -982,20 +945,8 @@ __global__ __launch_bounds__(DM_THREADS) void dm_emit_words_kernel(const float* 
         mine = (pa.x | pa.y | pb.x | pb.y) & ~(pa.x & pa.y & pb.x & pb.y);  // surface tets: neither case 0 nor case 15
     }
     const int c = __popcll(mine);
-    int incl = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int up = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += up;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int off = incl - c, total = 0;
-#pragma unroll
-    for (int k = 0; k < DM_THREADS / A3D_WAVE; ++k) {
-        if (k < wave) off += s_wave[k];
-        total += s_wave[k];
-    }
+    int total;
+    int off = a3d_block_excl_scan<DM_THREADS / A3D_WAVE>(c, s_wave, &total);
     if (total == 0) return;  // (uniform)
     while (mine) {
         s_items[off++] = (unsigned short)((tid << 6) | (__ffsll((long long)mine) - 1));

@@ -233,12 +233,6 @@ __device__ __forceinline__ void gb_row_direct(float* g_rows, long long row, cons
         if (gb_comp_on(k, NC, want_prior, want_clip)) atomicAdd(r + gb_col(k), c[k]);
 }
 
-// lane ^ 1 through the DPP quad permute (no LDS traffic)
-__device__ __forceinline__ float gb_xor1(float x) {
-    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), 0xB1 /* quad_perm [1,0,3,2] */, 0xF, 0xF, true));
-}
-__device__ __forceinline__ int gb_xor1(int x) { return __builtin_amdgcn_mov_dpp(x, 0xB1, 0xF, 0xF, true); }
-
 template <int GB_SLOTS, int GB_ENTRIES, int NC>  // NC = components per (pixel, corner): 12, or 15 with the extra attribute
 __global__ __launch_bounds__(256) void gb_bwd_kernel(const float* __restrict__ g_out, const float4* __restrict__ rast, const int* __restrict__ tri,
                                                      const long long* __restrict__ pix, long long P, const float* __restrict__ v_pos,
@@ -300,13 +294,13 @@ __global__ __launch_bounds__(256) void gb_bwd_kernel(const float* __restrict__ g
     A3D_STAMP(1, 1);
     // neighbouring list entries on the same triangle of the same image: the even lane takes the odd lane's sums, a third fewer entries
     const int tkey = live ? b * F + f : -1 - (int)threadIdx.x;  // (B*F < 2^31 is checked by the entry point)
-    const int tkey1 = gb_xor1(tkey);
+    const int tkey1 = a3d_lane_xor<1>(tkey);
     const bool same = live && tkey1 == tkey;
 #pragma unroll
     for (int c = 0; c < 3; ++c)
 #pragma unroll
         for (int k = 0; k < NC; ++k) {
-            const float o = gb_xor1(acc[c][k]);
+            const float o = a3d_lane_xor<1>(acc[c][k]);
             if (same) acc[c][k] += o;
         }
     bool active = live && !(same && (threadIdx.x & 1));
@@ -316,13 +310,13 @@ __global__ __launch_bounds__(256) void gb_bwd_kernel(const float* __restrict__ g
     // 16 / 32 away -- cost more exchanges than they save: 21.1 - 23.1 us.)
     {
         const int mykey = active ? tkey : -1 - (int)threadIdx.x;
-        const int other = __builtin_amdgcn_mov_dpp(mykey, 0x128, 0xF, 0xF, true);  // (outside the &&: every lane must take part)
+        const int other = a3d_lane_xor<8>(mykey);  // (outside the &&: every lane must take part)
         const bool same_r = active && other == mykey;
 #pragma unroll
         for (int c = 0; c < 3; ++c)
 #pragma unroll
             for (int k = 0; k < NC; ++k) {
-                const float o = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(acc[c][k]), 0x128, 0xF, 0xF, true));
+                const float o = a3d_lane_xor<8>(acc[c][k]);
                 if (same_r) acc[c][k] += o;
             }
         active = active && !(same_r && (threadIdx.x & 8));

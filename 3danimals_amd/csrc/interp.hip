@@ -62,11 +62,8 @@ __global__ __launch_bounds__(256) void ip_bwd_kernel(const float* __restrict__ g
             }
         }
     }
-#pragma unroll
-    for (int o = G / 2; o > 0; o >>= 1) {
-        gu += __shfl_xor(gu, o, 64);
-        gv += __shfl_xor(gv, o, 64);
-    }
+    gu = a3d_group_sum<G>(gu);
+    gv = a3d_group_sum<G>(gv);
     if (sub == 0) g_rast[i] = make_float4(gu, gv, 0.f, 0.f);
 }
 

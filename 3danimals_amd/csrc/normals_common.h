@@ -23,18 +23,6 @@ __device__ __forceinline__ NrFace nr_decode(int key, int F, const int* __restric
 // loop for the rest (keys picked in ascending order from memory).
 #define NR_SLOTS 8
 
-__device__ __forceinline__ void nr_sort8(int a[8]) {
-#define NR_CX(i, j) { const int x = min(a[i], a[j]), y = max(a[i], a[j]); a[i] = x; a[j] = y; }
-    NR_CX(0, 1) NR_CX(2, 3) NR_CX(4, 5) NR_CX(6, 7)
-    NR_CX(0, 2) NR_CX(1, 3) NR_CX(4, 6) NR_CX(5, 7)
-    NR_CX(1, 2) NR_CX(5, 6) NR_CX(0, 4) NR_CX(3, 7)
-    NR_CX(1, 5) NR_CX(2, 6)
-    NR_CX(1, 4) NR_CX(3, 6)
-    NR_CX(2, 4) NR_CX(3, 5)
-    NR_CX(3, 4)
-#undef NR_CX
-}
-
 // the NR_SLOTS smallest keys of the list, ascending (0x7fffffff = none); for lists of up to NR_SLOTS entries: the whole list
 __device__ __forceinline__ void nr_first_keys(const int* __restrict__ adj, int lo, int n, int keys[NR_SLOTS]) {
     nr_load_keys(adj, lo, n, keys);  // eight unconditional loads in flight
@@ -52,7 +40,7 @@ __device__ __forceinline__ void nr_first_keys(const int* __restrict__ adj, int l
             }
         }
     }
-    nr_sort8(keys);
+    a3d_sort8(keys);
 }
 
 // One (image, vertex) of the forward pass: the un-normalised sum of the incident faces' cross products in ascending key order -> acc,

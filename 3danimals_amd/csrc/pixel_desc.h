@@ -85,14 +85,7 @@ __device__ __forceinline__ T comp(V3T<T> v, int c) { return c == 0 ? v.x : c == 
 
 // sum of v over the work-group, in a fixed order (red: 4 doubles of LDS).  Sums are carried in double from the lane to the finishing
 // launch: what is left in a reduced gradient is the rounding of the per-pixel terms, not of the summation
-__device__ __forceinline__ double block_sum(double v, double* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
+__device__ __forceinline__ double block_sum(double v, double* red) { return a3d_block_sum<THREADS / 64>(v, red); }
 
 // The one kernel body.  P is the operator's policy:
 //   NIN, cin(i), CO    inputs, channels of input i, channels of the result

@@ -394,18 +394,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
             const int4 bx = s_box[s_big[threadIdx.x] >> 8][s_big[threadIdx.x] & 255];
             cnt = (((bx.z & 0xFFFF) + 7) >> 3) * (((bx.z >> 16) + 7) >> 3);
         }
-        int incl = cnt;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int o = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += o;
-        }
-        if (lane == 63) s_wsum[wv] = incl;
-        __syncthreads();
-        int base = 0;
-        for (int k = 0; k < wv; ++k) base += s_wsum[k];
-        s_bpre[threadIdx.x] = base + incl - cnt;
-        if (threadIdx.x == 255) s_bpre[256] = base + incl;
+        const int excl = a3d_block_excl_scan<4>(cnt, s_wsum);  // (every thread is here: the returns above are uniform)
+        s_bpre[threadIdx.x] = excl;
+        if (threadIdx.x == 255) s_bpre[256] = excl + cnt;
     }
     __syncthreads();
     const int total_tiles = s_bpre[256];
@@ -624,20 +615,9 @@ __global__ __launch_bounds__(256) void rs_fine_kernel(const float4* __restrict__
                 }
             }
         }
-        {   // inclusive scan of the candidate counts over the work-group
-            int incl = cand;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const int o = __shfl_up(incl, d, 64);
-                if (lane >= d) incl += o;
-            }
-            if (lane == 63) s_wsum[wv] = incl;
-            __syncthreads();
-            int base = 0;
-            for (int k = 0; k < wv; ++k) base += s_wsum[k];
-            s_pre[threadIdx.x + 1] = base + incl;
-            if (threadIdx.x == 0) s_pre[0] = 0;
-        }
+        // inclusive scan of the candidate counts over the work-group (s_wsum is free again: the trip ends in a barrier)
+        s_pre[threadIdx.x + 1] = a3d_block_excl_scan<4>(cand, s_wsum) + cand;
+        if (threadIdx.x == 0) s_pre[0] = 0;
         __syncthreads();
         const int total = s_pre[256];
         for (int c = threadIdx.x; c < total; c += 256) {
@@ -774,8 +754,7 @@ __global__ __launch_bounds__(256) void rs_resolve_cover_kernel(const float4* __r
     if (wave == 0 && (cnt > 0 || last_of_group)) {
         int timeout = 0;
         int own = lane < r ? rs_await(blk_flag + g * A3D_COVER_GROUP + lane, &timeout, exp) : 0;  // earlier blocks of my group
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) own += __shfl_xor(own, d, 64);
+        own = a3d_group_sum(own);
         // (a group's total depends on its own blocks' counts ONLY and is published before this wave waits for the totals of earlier groups: no
         // chain from group to group)
         if (last_of_group && lane == 0) {
@@ -785,8 +764,7 @@ __global__ __launch_bounds__(256) void rs_resolve_cover_kernel(const float4* __r
         if (cnt > 0 || pads) {
             int before = 0;
             for (int j = lane; j < g; j += 64) before += rs_await(grp_flag + j, &timeout, exp);  // earlier groups
-#pragma unroll
-            for (int d = 32; d > 0; d >>= 1) before += __shfl_xor(before, d, 64);
+            before = a3d_group_sum(before);
             if (lane == 0) { s_off = before + own; s_total = before + own + cnt; }
         }
         if (__ballot(timeout != 0) && lane == 0) atomicOr(group_sum + 3, 1);  // status word (never in the sums: word 3 of the first line)

@@ -40,14 +40,6 @@ __global__ __launch_bounds__(256) void sh_fwd_kernel(const float* __restrict__ g
     }
 }
 
-__device__ __forceinline__ float sh_row16_sum(float r) {  // sum over the 16-lane DPP row, in every lane of the row
-    r += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(r), 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
-    r += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(r), 0x4E, 0xF, 0xF, true));   // quad_perm [2,3,0,1]
-    r += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(r), 0x141, 0xF, 0xF, true));  // row_half_mirror
-    r += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(r), 0x140, 0xF, 0xF, true));  // row_mirror
-    return r;
-}
-
 // where the gradient of the per-image rows goes: the layout of ShPar, writable
 struct ShParGrad {
     float *rot, *view, *light;
@@ -149,7 +141,7 @@ __global__ __launch_bounds__(256) void sh_bwd_kernel(const float* __restrict__ g
         const bool mine = live && row == bi;
 #pragma unroll
         for (int k = 0; k < 17; ++k) {
-            const float r = sh_row16_sum(mine ? gp[k] : 0.f);
+            const float r = a3d_row16_sum(mine ? gp[k] : 0.f);
             if ((lane & 15) == 0) s_red[r16][k] = r;
         }
         __syncthreads();

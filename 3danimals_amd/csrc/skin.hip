@@ -174,8 +174,7 @@ __global__ __launch_bounds__(SK_THREADS) void sk_fwd_kernel(const float* __restr
         lg[q] = (EXACT || k < K) ? sk_logit(s_bone[(EXACT || k < K) ? k : 0], px, py, pz, neg_inv_temp) : -INFINITY;
         m = fmaxf(m, lg[q]);
     }
-    m = fmaxf(m, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(m), 0xB1, 0xF, 0xF, true)));  // quad_perm [1,0,3,2]
-    m = fmaxf(m, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(m), 0x4E, 0xF, 0xF, true)));  // quad_perm [2,3,0,1]
+    m = a3d_quad_max(m);
     // (the logits of the first group only need the bones: they run beside the chain products above, and the one barrier both wait at is here)
     if (POSE && gi == 0) {
         __syncthreads();  // s_T complete (the blend below only reads it)
@@ -195,12 +194,7 @@ __global__ __launch_bounds__(SK_THREADS) void sk_fwd_kernel(const float* __restr
             oz += e * (t[8] * px + t[9] * py + t[10] * pz + t[11]);
         }
     }
-    auto quad_sum = [](float r) {
-        r += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(r), 0xB1, 0xF, 0xF, true));
-        r += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(r), 0x4E, 0xF, 0xF, true));
-        return r;
-    };
-    s = quad_sum(s); ox = quad_sum(ox); oy = quad_sum(oy); oz = quad_sum(oz);
+    s = a3d_quad_sum(s); ox = a3d_quad_sum(ox); oy = a3d_quad_sum(oy); oz = a3d_quad_sum(oz);
     if (!valid) continue;
     const float inv = 1.f / s;
     if (sub < 3) out[((long long)b * V + i) * 3 + sub] = (sub == 0 ? ox : (sub == 1 ? oy : oz)) * inv;

@@ -29,21 +29,14 @@ __device__ __forceinline__ void ts_pixel(int tile_x0, int tile_y0, int& px, int&
 // partner lane ^ m when both hold the same key; the partner retires.  Same-address LDS float atomics serialise (measured: the 9 adds
 // per pixel of a3d_rast_bwd were 24 of its 37 us with every pixel going to the table itself), so every merged pair is three contended
 // adds less.  ROUNDS: 6 = down to one entry per aligned run of the block, fewer for wide rows (each round moves N values).
-template <int M>
-__device__ __forceinline__ int ts_xor(int x) {  // lane ^ M: register moves (DPP) where the pattern exists, ds_bpermute otherwise
-    if (M == 1) return __builtin_amdgcn_mov_dpp(x, 0xB1 /* quad_perm [1,0,3,2] */, 0xF, 0xF, true);
-    if (M == 2) return __builtin_amdgcn_mov_dpp(x, 0x4E /* quad_perm [2,3,0,1] */, 0xF, 0xF, true);
-    if (M == 8) return __builtin_amdgcn_mov_dpp(x, 0x128 /* row_ror:8 */, 0xF, 0xF, true);
-    return __shfl_xor(x, M, 64);
-}
 template <int N, int M>
 __device__ __forceinline__ void ts_merge_round(int& key, float (&v)[N]) {
     const int lane = threadIdx.x & 63;
-    const int other = ts_xor<M>(key);
+    const int other = a3d_lane_xor<M>(key);
     const bool same = key >= 0 && other == key;
 #pragma unroll
     for (int n = 0; n < N; ++n) {
-        const float o = __int_as_float(ts_xor<M>(__float_as_int(v[n])));
+        const float o = a3d_lane_xor<M>(v[n]);
         if (same && !(lane & M)) v[n] += o;
     }
     if (same && (lane & M)) key = -1;

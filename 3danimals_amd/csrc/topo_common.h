@@ -173,20 +173,10 @@ constexpr int NR_SCAN_THREADS = 1024;
 // element slabs with three barriers each: 9 us at V = 5.7k).
 __global__ __launch_bounds__(NR_SCAN_THREADS) void nr_adj_scan_kernel(int* __restrict__ cnt, int V, int* __restrict__ off) {
     __shared__ int wave_tot[NR_SCAN_THREADS / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int per = (V + NR_SCAN_THREADS - 1) / NR_SCAN_THREADS;
     const int lo = min((int)threadIdx.x * per, V), hi = min(lo + per, V);
     const int mine = a3d_run_sum(cnt, lo, hi);
-    int incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += o;
-    }
-    if (lane == 63) wave_tot[wave] = incl;
-    __syncthreads();
-    int run = incl - mine;
-    for (int w = 0; w < wave; ++w) run += wave_tot[w];
+    int run = a3d_block_excl_scan<NR_SCAN_THREADS / 64>(mine, wave_tot);
     run = a3d_run_scan<true>(cnt, off, lo, hi, run);
     if (threadIdx.x == NR_SCAN_THREADS - 1) off[V] = run;
 }
@@ -200,15 +190,7 @@ __device__ __forceinline__ void nr_adj_sort_vertex(const int* __restrict__ off, 
         int a[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) a[k] = k < n ? adj[lo + k] : 0x7fffffff;
-#define NR_CX(i, j) { const int x = min(a[i], a[j]), y = max(a[i], a[j]); a[i] = x; a[j] = y; }
-        NR_CX(0, 1) NR_CX(2, 3) NR_CX(4, 5) NR_CX(6, 7)
-        NR_CX(0, 2) NR_CX(1, 3) NR_CX(4, 6) NR_CX(5, 7)
-        NR_CX(1, 2) NR_CX(5, 6) NR_CX(0, 4) NR_CX(3, 7)
-        NR_CX(1, 5) NR_CX(2, 6)
-        NR_CX(1, 4) NR_CX(3, 6)
-        NR_CX(2, 4) NR_CX(3, 5)
-        NR_CX(3, 4)
-#undef NR_CX
+        a3d_sort8(a);
 #pragma unroll
         for (int k = 0; k < 8; ++k)
             if (k < n) adj[lo + k] = a[k];

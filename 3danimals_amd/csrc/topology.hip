@@ -78,7 +78,7 @@ __global__ __launch_bounds__(256) void tp_finalize_kernel(const int* __restrict_
                                                           int* __restrict__ adj, int* __restrict__ cnt_next, int v_next) {
     extern __shared__ int s_off[];  // [V + 1]
     __shared__ int s_wave[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int idx = blockIdx.x * blockDim.x + tid;
     const int my_v = idx < 3 * F ? tri[idx] : -1;  // (issued first: overlaps with the scan)
     {   // exclusive scan of (cnt & 0xFFFF) over the vertices: a contiguous run per thread, eight unconditional loads in flight
@@ -97,16 +97,7 @@ __global__ __launch_bounds__(256) void tp_finalize_kernel(const int* __restrict_
                 }
             }
         }
-        int incl = mine;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int o = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += o;
-        }
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        int base = incl - mine;
-        for (int w = 0; w < wave; ++w) base += s_wave[w];
+        const int base = a3d_block_excl_scan<4>(mine, s_wave);
         for (int i = lo; i < hi; ++i) s_off[i] += base;
         if (tid == 255) s_off[V] = base + mine;
         __syncthreads();

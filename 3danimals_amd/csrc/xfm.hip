@@ -73,11 +73,7 @@ __global__ __launch_bounds__(256) void xf_bwd_kernel(const float* __restrict__ g
     const int lane = threadIdx.x & 63, row = threadIdx.x >> 4;
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
-        float r = gm[k];
-        r += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(r), 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
-        r += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(r), 0x4E, 0xF, 0xF, true));   // quad_perm [2,3,0,1]
-        r += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(r), 0x141, 0xF, 0xF, true));  // row_half_mirror
-        r += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(r), 0x140, 0xF, 0xF, true));  // row_mirror
+        const float r = a3d_row16_sum(gm[k]);
         if ((lane & 15) == 0) s_red[row][k] = r;
     }
     __syncthreads();
