@@ -1,4 +1,4 @@
-"""ctypes binding of liba3d_hip.so (include/a3d.h, include/a3d_bsdf.h, include/a3d_deriv.h, include/a3d_tangent.h, include/a3d_reg.h, include/a3d_envshade.h).  No fallback: if the library is missing we say so and stop."""
+"""ctypes binding of liba3d_hip.so (include/a3d.h, include/a3d_bsdf.h, include/a3d_deriv.h, include/a3d_tangent.h, include/a3d_reg.h, include/a3d_envshade.h, include/a3d_sdfreg.h).  No fallback: if the library is missing we say so and stop."""
 from __future__ import annotations
 
 import ctypes
@@ -269,6 +269,14 @@ class EnvShadeDesc(ctypes.Structure):
                 ("g_out", _p), ("g_in", _p * 4)]
 
 
+# the entry points of include/a3d_sdfreg.h (same library, same a3d_version(); tests/test_sdfreg_cpu.py checks this table against that header)
+SDFREG_SIGNATURES = {
+    "a3d_sdf_bce_fwd": (_c_int, [_p, _c_int, _p, _c_int, _p, _p, _p, _p]),
+    "a3d_sdf_bce_bwd": (_c_int, [_p, _p, _c_int, _p, _c_int, _p, _p, _p, _p, _p]),
+}
+SDF_BCE_BLOCK_EDGES = 1024  # A3D_SDF_BCE_BLOCK_EDGES
+SDF_BCE_PARTIAL_WORDS = 3  # A3D_SDF_BCE_PARTIAL_WORDS
+
 ABI_VERSION = 404  # a3d_version() of the library these signatures belong to (include/a3d.h)
 _lib = None
 
@@ -287,7 +295,7 @@ def lib():
                 "(or __graft_entry__.build()).  There is no CPU fallback for the HIP hot path."
             )
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(BSDF_SIGNATURES.items()) + list(DERIV_SIGNATURES.items()) + list(TANGENT_SIGNATURES.items()) + list(REG_SIGNATURES.items()) + list(ENVSHADE_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(BSDF_SIGNATURES.items()) + list(DERIV_SIGNATURES.items()) + list(TANGENT_SIGNATURES.items()) + list(REG_SIGNATURES.items()) + list(ENVSHADE_SIGNATURES.items()) + list(SDFREG_SIGNATURES.items()):
             fn = getattr(handle, name)  # AttributeError here == ABI drift
             fn.restype, fn.argtypes = res, args
         if handle.a3d_version() != ABI_VERSION:  # same symbols, other argument lists: a stale build must not be called

@@ -50,6 +50,7 @@ class TetGridTopology:
         uniq, inverse = torch.unique(lo * nv + hi, return_inverse=True)  # sorted == lexicographic (min,max)
         self.all_edges = torch.stack([uniq // nv, uniq % nv], -1)  # int64, == reference generate_edges (dmtet.py:283-288)
         self.edges32 = self.all_edges.to(torch.int32).contiguous()
+        ops.register_grid_edges(self.all_edges, self.edges32, nv)  # sdf_bce_reg_loss(sdf, all_edges) streams edges32
         self.tet2edge32 = inverse.reshape(-1, 6).to(torch.int32).contiguous()
         self.tets32 = idx.to(torch.int32).contiguous()
         self.num_verts = nv
@@ -281,13 +282,35 @@ class DMTet:
         return verts, faces, topo.uvs(), uv_idx
 
 
-def sdf_bce_reg_loss(sdf, all_edges):
-    """reference dmtet.py:161-169 (torch; off by default: sdf_bce_reg_loss_weight 0)."""
+HIP_SDF_REG = True  # a CUDA float32 SDF through csrc/sdfreg.hip (False: always the torch statements, e.g. for a caller that differentiates twice)
+
+
+def _sdf_bce_reg_loss_torch(sdf, all_edges):
+    """reference dmtet.py:161-169 (torch; off by default: sdf_bce_reg_loss_weight 0).  The targets take the dtype of the SDF where the
+    reference writes .float(): the same statements for a float32 SDF, and a float64 SDF is evaluated in float64 (with float32 targets
+    torch carries the terms of a float64 input in float32 and returns float32)."""
     pair = sdf[all_edges.reshape(-1)].reshape(-1, 2)
     mask = torch.sign(pair[..., 0]) != torch.sign(pair[..., 1])
     pair = pair[mask]
     bce = torch.nn.functional.binary_cross_entropy_with_logits
-    return bce(pair[..., 0], (pair[..., 1] > 0).float()) + bce(pair[..., 1], (pair[..., 0] > 0).float())
+    return bce(pair[..., 0], (pair[..., 1] > 0).to(pair.dtype)) + bce(pair[..., 1], (pair[..., 0] > 0).to(pair.dtype))
+
+
+def _sdf_reg_hip_ok(sdf, all_edges):
+    return (HIP_SDF_REG and torch.is_tensor(sdf) and sdf.is_cuda and sdf.dtype == torch.float32 and sdf.shape[0] > 0
+            and (sdf.dim() == 1 or (sdf.dim() == 2 and sdf.shape[1] == 1)) and torch.is_tensor(all_edges)
+            and all_edges.dtype in (torch.int32, torch.int64) and all_edges.dim() == 2 and all_edges.shape[1] == 2 and all_edges.shape[0] > 0
+            and all_edges.device == sdf.device)
+
+
+def sdf_bce_reg_loss(sdf, all_edges):
+    """reference dmtet.py:161-169, evaluated every training iteration by the reference's Trainer whatever its weight (AnimalModel.py:312).
+    A CUDA float32 ``sdf`` [Nv] or [Nv,1] with an integer ``all_edges`` [Ne,2] on the same device runs in csrc/sdfreg.hip
+    (ops.sdf_bce_reg_loss: two launches forward, one backward, double sums in a fixed order, no host synchronisation, once
+    differentiable); CPU, float64, other shapes and ``HIP_SDF_REG = False`` take the torch statements."""
+    if _sdf_reg_hip_ok(sdf, all_edges):
+        return ops.sdf_bce_reg_loss(sdf, all_edges)
+    return _sdf_bce_reg_loss_torch(sdf, all_edges)
 
 
 GRAPH_SDF_GRADIENT = True  # replay the eikonal regulariser's launch-bound chain from HIP graphs (DMTetGeometry._graphed_sdf_gradient)

@@ -3093,6 +3093,103 @@ def env_shade(diffuse, specular_levels, fg, gb_pos, gb_normal, kd, ks, view_pos,
                            *pix, *[t.contiguous() for t in spec])
 
 
+# ---------------------------------------------------------------------------------------------- SDF sign-agreement regulariser (include/a3d_sdfreg.h)
+def edge_incidence(edges32: torch.Tensor, num_vertices: int):
+    """(off int32 [Nv + 1], inc int32 [2 Ne]) of an int32 edge list [Ne,2] with indices in [0, Nv): the entries 2 * edge + side of vertex
+    v are inc[off[v] : off[v + 1]], in ascending order -- every (edge, side) once, under the vertex edges32[edge, side].  A stable sort
+    over both endpoints; runs wherever the list lives (one host synchronisation on the GPU: the counts)."""
+    ends = edges32.reshape(-1).long()
+    inc = torch.sort(ends, stable=True).indices.to(torch.int32)
+    off = torch.zeros(int(num_vertices) + 1, dtype=torch.int64, device=ends.device)
+    off[1:] = torch.cumsum(torch.bincount(ends, minlength=int(num_vertices)), 0)
+    return off.to(torch.int32), inc.contiguous()
+
+
+class SdfEdges:
+    """What sdf_bce_reg_loss keeps per edge tensor: the contiguous, 16-byte aligned int32 rows the kernels stream, the smallest and largest
+    index in them (read back once, when the entry is made), and -- from the first backward on -- the vertex -> (edge, side) list."""
+
+    def __init__(self, edges32: torch.Tensor, lo=None, hi=None):
+        if edges32.data_ptr() % 16:
+            edges32 = edges32.clone()
+        self.edges32 = edges32
+        if lo is None or hi is None:
+            lo, hi = (int(v) for v in torch.stack(torch.aminmax(edges32)).tolist())
+        self.lo, self.hi = int(lo), int(hi)
+        self._incidence = None
+
+    def check(self, num_vertices: int):
+        if self.lo < 0 or self.hi >= num_vertices:
+            raise IndexError(f"sdf_bce_reg_loss: edge indices span [{self.lo}, {self.hi}], the SDF has {num_vertices} values")
+
+    def incidence(self, num_vertices: int):
+        if self._incidence is None or self._incidence[0] != num_vertices:
+            self._incidence = (num_vertices,) + edge_incidence(self.edges32, num_vertices)
+        return self._incidence[1:]
+
+
+_sdf_edges_cache = _IdentityCache(maxsize=2)  # (an entry pins its edge tensor and the int32 rows: 24 B per edge)
+
+
+def register_grid_edges(all_edges: torch.Tensor, edges32: torch.Tensor, num_vertices: int):
+    """A tet grid's own lists (TetGridTopology): sdf_bce_reg_loss on ``all_edges`` streams the existing ``edges32``, no copy, and the
+    index range is known by construction.  The entry rides on the tensor object itself, so it lives exactly as long as the grid does."""
+    if edges32.is_cuda and edges32.shape[0] > 0:
+        all_edges._a3d_sdf_edges = (_IdentityCache.key(all_edges), SdfEdges(edges32, 0, int(num_vertices) - 1))
+
+
+def sdf_edges(all_edges: torch.Tensor) -> SdfEdges:
+    """The cached SdfEdges of an integer [Ne,2] edge tensor, keyed by identity; made (int32 copy, index range) on first use."""
+    own = getattr(all_edges, "_a3d_sdf_edges", None)
+    if own is not None and own[0] == _IdentityCache.key(all_edges):
+        return own[1]
+    return _sdf_edges_cache.get(all_edges, lambda t: SdfEdges(t.to(torch.int32).contiguous()))
+
+
+class _SdfBceReg(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, sdf, cached):
+        flat = f32c(sdf).reshape(-1)
+        Nv, Ne = flat.shape[0], cached.edges32.shape[0]
+        blocks = -(-Ne // _lib.SDF_BCE_BLOCK_EDGES)
+        partials = torch.empty(_lib.SDF_BCE_PARTIAL_WORDS * blocks, dtype=torch.float64, device=flat.device)
+        state = torch.empty(2, dtype=torch.float64, device=flat.device)
+        loss = torch.empty((), dtype=torch.float32, device=flat.device)
+        call("a3d_sdf_bce_fwd", ptr(flat), Nv, ptr(cached.edges32), Ne, ptr(partials), ptr(state), ptr(loss), stream())
+        ctx.save_for_backward(flat, state)
+        ctx.cached, ctx.shape = cached, sdf.shape
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss):
+        flat, state = ctx.saved_tensors
+        Nv, Ne = flat.shape[0], ctx.cached.edges32.shape[0]
+        off, inc = ctx.cached.incidence(Nv)
+        g_sdf = torch.empty_like(flat)
+        call("a3d_sdf_bce_bwd", ptr(f32h(g_loss)), ptr(flat), Nv, ptr(ctx.cached.edges32), Ne, ptr(off), ptr(inc), ptr(state), ptr(g_sdf), stream())
+        return g_sdf.reshape(ctx.shape), None
+
+
+def sdf_bce_reg_loss(sdf, all_edges):
+    """sdf_bce_reg_loss (reference dmtet.py:161-169) of a float32 SDF [Nv] or [Nv,1] over an integer edge tensor [Ne,2], both on the
+    current device: two launches forward and one backward (csrc/sdfreg.hip), double sums in a fixed order, no host synchronisation once
+    the edge tensor is cached -> a 0-dim float32 tensor with the same bits on every run.  The int32 rows and the index range of an edge
+    tensor are cached by identity (a tet grid's own all_edges uses its edges32); an index outside [0, Nv) raises IndexError here, before
+    any launch.  The vertex -> (edge, side) list of the backward is built at the first backward of an edge tensor."""
+    if not torch.is_tensor(sdf) or sdf.dtype != torch.float32 or not (sdf.dim() == 1 or (sdf.dim() == 2 and sdf.shape[1] == 1)):
+        raise ValueError(f"sdf_bce_reg_loss: expected a float32 sdf [Nv] or [Nv,1], got {getattr(sdf, 'dtype', type(sdf))} {list(getattr(sdf, 'shape', []))}")
+    if not torch.is_tensor(all_edges) or all_edges.dtype not in (torch.int32, torch.int64) or all_edges.dim() != 2 or all_edges.shape[1] != 2:
+        raise ValueError(f"sdf_bce_reg_loss: expected int32 / int64 edges [Ne,2], got {getattr(all_edges, 'dtype', type(all_edges))} "
+                         f"{list(getattr(all_edges, 'shape', []))}")
+    if sdf.shape[0] == 0 or all_edges.shape[0] == 0:
+        raise ValueError("sdf_bce_reg_loss: empty sdf or edge list")
+    require_device(sdf, all_edges, what="sdf_bce_reg_loss")
+    cached = sdf_edges(all_edges)
+    cached.check(sdf.shape[0])
+    return _SdfBceReg.apply(sdf, cached)
+
+
 # ---------------------------------------------------------------------------------------------- mixed precision
 def _amp_wrap_functions():
     """Every autograd.Function of this module runs its forward with autocast OFF on float32 copies of half-precision inputs, and its
