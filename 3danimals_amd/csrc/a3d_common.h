@@ -36,9 +36,6 @@ void a3d_set_error(const char* fmt, ...);
 
 static inline int a3d_div_up(long long a, long long b) { return (int)((a + b - 1) / b); }
 
-// experiment knob for kernel bisection (tools/kernel_lab.py): integer value of the environment variable A3D_EXP, 0 when unset
-int a3d_exp(void);
-
 #ifdef __HIPCC__
 // ---- phase stamps inside kernels (tools/kernel_phases.py; the library proper is built WITHOUT them: build.py --profile makes a second,
 // instrumented liba3d_hip_prof.so).  A3D_STAMP(kernel id within the TU, slot 0..7): thread 0 of every work-group writes the 100 MHz wall

@@ -430,7 +430,9 @@ struct CaJob {
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void ca_compose_kernel(CaJob ja, CaJob jb, unsigned n_pix, unsigned nb_compose, AaAnalyzeJob an, int extra_first) {
     __shared__ int s_src[256];  // >= 0: point row; -1: zero; <= -2: background texel -(v + 2)
     A3D_STAMP(0, 0);  // (A3D_STAMP kernel ids of this file: 0 = ca_compose_kernel, 1 = ca_blend_kernel, 2 = ca_gather_kernel, 3 = ca_bwd_kernel)
-    // (extra_first: the analysis work-groups -- gather chains -- are dispatched BEFORE the pixel movers of their row, not as the launch's tail)
+    // (extra_first: the analysis work-groups -- gather chains -- are dispatched BEFORE the pixel movers of their row, not as the launch's tail.
+    // Always 1; it stays a run-time argument because the kernel runs at a forced 8 waves with spills, and with the remapping made
+    // unconditional the compiler spills more: 84 instead of 72 bytes of scratch per lane)
     unsigned bx = blockIdx.x;
     if (extra_first) {
         const unsigned n_extra = gridDim.x - nb_compose;
@@ -832,7 +834,7 @@ extern "C" int a3d_composite_aa_fwd(const a3d_ca_buffer* first, const a3d_ca_buf
     const CaJob jb = two ? ca_job(vals2_or_null, C2, inv, bg2_or_null, bg2_batch, H, W, out2_or_null, nullptr, nullptr, second_or_null) : ja;
     const unsigned n_pix = (unsigned)B * ja.s.hw;
     const unsigned nb_compose = (unsigned)a3d_div_up(n_pix, 256), rows = two ? 2u : 1u;
-    hipLaunchKernelGGL(ca_compose_kernel, dim3(nb_compose + (nb_an + rows - 1) / rows, rows), dim3(256), 0, s, ja, jb, n_pix, nb_compose, an, a3d_exp() == 43 ? 0 : 1);
+    hipLaunchKernelGGL(ca_compose_kernel, dim3(nb_compose + (nb_an + rows - 1) / rows, rows), dim3(256), 0, s, ja, jb, n_pix, nb_compose, an, 1);
     A3D_LAUNCH_CHECK();
     if (ja.s.sh_gb && ja.s.sh_out) {  // the colours the compose launch kept: the blends read them as plain value rows
         ja.s.vals = ja.s.sh_out;
@@ -898,7 +900,7 @@ extern "C" int a3d_mask_aa_fwd(const float* rast, int C, const float* bg_or_null
     CaJob ja = ca_job(nullptr, C, nullptr, bg_or_null, bg_batch, H, W, out, nullptr, nullptr);
     ja.s.rast = (const float4*)rast;
     const unsigned n_pix = (unsigned)B * ja.s.hw, nb_compose = (unsigned)a3d_div_up(n_pix, 256);
-    hipLaunchKernelGGL(ca_compose_kernel, dim3(nb_compose + nb_an, 1), dim3(256), 0, s, ja, ja, n_pix, nb_compose, an, a3d_exp() == 43 ? 0 : 1);
+    hipLaunchKernelGGL(ca_compose_kernel, dim3(nb_compose + nb_an, 1), dim3(256), 0, s, ja, ja, n_pix, nb_compose, an, 1);
     A3D_LAUNCH_CHECK();
     hipLaunchKernelGGL(ca_blend_kernel, dim3(512, 1), dim3(256), 0, s, ja, ja, (const AaRec*)work, count, capacity, W);
     A3D_LAUNCH_CHECK();

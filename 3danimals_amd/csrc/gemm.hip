@@ -248,13 +248,7 @@ extern "C" int a3d_gemm_nn_relumask(const float* A, const float* B, const float*
     if (M == 0) return A3D_OK;
     A3D_CHECK_ARG(A && B && C);
     hipStream_t s = (hipStream_t)stream;
-#ifdef A3D_EXPERIMENT
-    static const int variant = getenv("A3D_GEMM_VARIANT") ? atoi(getenv("A3D_GEMM_VARIANT")) : 3;  // experiment knob (build.py --exp only); 3 = persistent
-#else
-    const int variant = 3;  // persistent (the product library reads no environment)
-#endif
-    const dim3 block256(256);
-    if (variant == 3 && K == 256) {  // persistent, weight half resident in LDS
+    if (K == 256) {  // persistent, weight half resident in LDS
         // per device ordinal (a process may drive more than one GPU); idempotent values, so a race between threads is harmless
         static int n_cu_of[64] = {0};
         int dev = 0;
@@ -274,15 +268,10 @@ extern "C" int a3d_gemm_nn_relumask(const float* A, const float* B, const float*
         A3D_LAUNCH_CHECK();
         return A3D_OK;
     }
-    if (variant == 1) {  // 64 x 256 tile, wave 32 x 128, 3 work-groups per CU
-        const dim3 grid(a3d_div_up(M, 64), 1);
-        if (X) hipLaunchKernelGGL((gm_nn_kernel<2, 2, 256, 3, true>), grid, block256, 0, s, A, B, X, (int)M, K, C);
-        else hipLaunchKernelGGL((gm_nn_kernel<2, 2, 256, 3, false>), grid, block256, 0, s, A, B, X, (int)M, K, C);
-    } else {  // 128 x 128 tile, wave 32 x 128, 4 work-groups per CU
-        const dim3 grid(a3d_div_up(M, 128), 2);
-        if (X) hipLaunchKernelGGL((gm_nn_kernel<4, 1, 128, 3, true>), grid, block256, 0, s, A, B, X, (int)M, K, C);  // +16 VGPRs for the mask
-        else hipLaunchKernelGGL((gm_nn_kernel<4, 1, 128, 4, false>), grid, block256, 0, s, A, B, X, (int)M, K, C);
-    }
+    // any other K: 128 x 128 tile, wave 32 x 128, 4 work-groups per CU
+    const dim3 grid(a3d_div_up(M, 128), 2), block256(256);
+    if (X) hipLaunchKernelGGL((gm_nn_kernel<4, 1, 128, 3, true>), grid, block256, 0, s, A, B, X, (int)M, K, C);  // +16 VGPRs for the mask
+    else hipLaunchKernelGGL((gm_nn_kernel<4, 1, 128, 4, false>), grid, block256, 0, s, A, B, X, (int)M, K, C);
     A3D_LAUNCH_CHECK();
     return A3D_OK;
 }

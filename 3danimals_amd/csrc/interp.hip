@@ -69,7 +69,7 @@ __global__ __launch_bounds__(256) void ip_bwd_kernel(const float* __restrict__ g
 
 // Round 6, C <= 16: one thread per pixel of a 16 x 16 tile; pixels on the same triangle merge their three bary-weighted gradient rows
 // inside the wave (ts_merge), the survivors meet their neighbours' in the work-group's LDS table (tile_scatter.h) and leave as one row
-// of adjacent atomics per vertex and tile.  Kernel us at B = 16, 256 x 256 (rocprofv3, tools/shim_bwd_prof.sh; per-pixel form ->
+// of adjacent atomics per vertex and tile.  Kernel us at B = 16, 256 x 256 (rocprofv3 over tools/shim_bwd_bench.py; per-pixel form ->
 // this one): 3 channels 50.7 -> 27.6 on the fresh mesh, 115 -> 30 on the trained-like one (its long thin triangles make the per-pixel
 // form's atomics collide); 16 channels 137 -> 92.  105 VGPRs (4 waves per SIMD): forcing 6 spills and loses (33 us).
 // CM = the channel count rounded up (register rows), ROUNDS = merge rounds.
@@ -167,7 +167,7 @@ extern "C" int a3d_interp_bwd(const float* g_out, const float* attr, int attr_ba
     hipStream_t s = (hipStream_t)stream;
     if (g_attr_or_null) A3D_HIP(hipMemsetAsync(g_attr_or_null, 0, sizeof(float) * (size_t)attr_batch * V * C, s));
     const long long hw = (long long)H * W, npix = hw * B;
-    if (C <= 16 && B <= 65535 && (long long)attr_batch * V < 0x7fffffffll && a3d_exp() != 140) {
+    if (C <= 16 && B <= 65535 && (long long)attr_batch * V < 0x7fffffffll) {
         const int tiles_x = a3d_div_up(W, TS_TILE), tiles_y = a3d_div_up(H, TS_TILE);
 #define IP_TILE(CM_, R_)                                                                                                                      \
     hipLaunchKernelGGL((ip_bwd_tile_kernel<CM_, R_>), dim3(tiles_x * tiles_y, B), dim3(256), g_attr_or_null ? TileScatter::lds_bytes(C) : 0, s, g_out, \

@@ -143,7 +143,7 @@ __device__ __forceinline__ void rs_row_span(const float4 p0, const float4 p1, co
 // layer's (depth, id) survive, pixels the previous layer left empty stay empty
 __device__ __forceinline__ void rs_test_pixel(const float4 p0, const float4 p1, const float4 p2, int px, int py, int W, float xs, float xo,
                                               float ys, float yo, unsigned f, unsigned long long* __restrict__ keys,
-                                              const float4* __restrict__ prev, int exp = 0) {
+                                              const float4* __restrict__ prev) {
     const RsFrag fr = rs_frag(p0, p1, p2, __builtin_fmaf(xs, (float)px, xo), __builtin_fmaf(ys, (float)py, yo));
     if (fr.hit) {
         const unsigned long long key = ((unsigned long long)rs_order(fr.zw) << 32) | f;
@@ -154,14 +154,6 @@ __device__ __forceinline__ void rs_test_pixel(const float4 p0, const float4 p1, 
             if (key <= key_prev) return;
         }
         unsigned long long* slot = keys + (long long)py * W + px;
-#ifdef A3D_EXPERIMENT
-        // measurement knobs (liba3d_hip_exp.so only): 101 = fragment tests without the atomics (what a perfect occlusion filter could save at
-        // most); 103 / 104 = a read of the key first for the fragments of triangles with positive / negative screen area, 105 = for all
-        if (exp == 101) { if (key == 0x123456789ull) atomicMin(slot, key); return; }
-        if (exp == 105 || (exp == 103 && fr.pos) || (exp == 104 && !fr.pos)) {
-            if (__hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= key) return;
-        }
-#endif
         // fire and forget.  (Reading the key first to skip atomics that cannot win looked like a saving and measured as a loss: the
         // dependent 8-byte read costs more than the ~50 % of atomics it removes -- 42.7 us with the filter, 33.0 us without.)
         atomicMin(slot, key);
@@ -186,17 +178,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
                                                      int nb_tri, float2* __restrict__ aa_screen, int* __restrict__ aa_count, int aa_shards,
                                                      int* __restrict__ cover_group_sum, int cover_groups, int nb_screen,
                                                      const int* __restrict__ topo_off, const int* __restrict__ topo_adj,
-                                                     int* __restrict__ topo_opp, int nb_opp, RsNormalsJob nj, int extra_first, int exp, RsBins bins) {
+                                                     int* __restrict__ topo_opp, int nb_opp, RsNormalsJob nj, RsBins bins) {
     const int b = blockIdx.y;
     A3D_STAMP(0, 0);  // (A3D_STAMP kernel ids of this file: 0 = rs_tri_kernel -- triangle work-groups only stamp 1..5 --, 1 = rs_resolve_kernel)
-    // the riding jobs (dependent-gather chains: vertex normals, opposite-vertex table, screen positions) are DISPATCHED FIRST (extra_first):
+    // the riding jobs (dependent-gather chains: vertex normals, opposite-vertex table, screen positions) are DISPATCHED FIRST:
     // their round trips then run under the triangle work instead of as the launch's tail.  bx = the work-group's index in the order the
     // branches below are written in (triangles first).
-    int bx = (int)blockIdx.x;
-    if (extra_first) {
-        const int n_extra = (int)gridDim.x - nb_tri;
-        bx = bx < n_extra ? nb_tri + bx : bx - n_extra;
-    }
+    const int n_extra = (int)gridDim.x - nb_tri;
+    const int bx = (int)blockIdx.x < n_extra ? nb_tri + (int)blockIdx.x : (int)blockIdx.x - n_extra;
     if (bx >= nb_tri + nb_screen + nb_opp) {
         // yet more extra work-groups: the vertex normals of the mesh being rasterised (and of a second, small vertex array over the same
         // triangle list) -- normals.hip's forward pass, which the G-buffer pass of this frame reads next.  As a launch of its own it is
@@ -277,11 +266,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     __shared__ int s_tiles[RS_TILE_CHUNK];
     __shared__ int s_bpre[257], s_wsum[4];
     const int wv = threadIdx.x >> 6, q = lane / LPT;  // this wave's slice, this lane's triangle slot
-    int big_limit = RS_BIG;
-#ifdef A3D_EXPERIMENT
-    if (exp >= 130 && exp < 140) big_limit = 32 << (exp - 130);  // measurement: the tile stage from 32, 64, .. pixels on
-#endif
-    bool big = area > big_limit;
+    bool big = area > RS_BIG;
     if (BIN && area > 0) {  // binned path: "big" = more than four tiles; such a box is widened to whole tiles of the screen for the tile stage
         const int x1 = x0 + bw - 1, y1 = y0 + area / bw - 1;
         big = (((x1 >> 3) - (x0 >> 3) + 1) * ((y1 >> 3) - (y0 >> 3) + 1)) > 4;
@@ -348,9 +333,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     } else {
     // candidate c of the work-group: first the wave slice (three compares on the four totals), then the slot inside it
     const int t0 = s_pre[0][TPW], t1 = t0 + s_pre[1][TPW], t2 = t1 + s_pre[2][TPW], total = t2 + s_pre[3][TPW];
-#ifdef A3D_EXPERIMENT
-    if (exp == 102) return;  // (the set-up alone)
-#endif
     // (round 6, measured and dropped: boxes above 48 pixels pooled ROW by row -- the lane that draws a row solves its span of columns
     // (rs_row_span) and tests only those -- in every work-group: 45.9 -> 51.9 us on the trained-like mesh, 28.9 -> 31.1 fresh (a row is
     // ~6 pixel tests by ONE lane while the lanes with single pixels wait, and a usual work-group's pool is only 2-3 trips of its 256 lanes
@@ -372,7 +354,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         if (i < (1 << 20)) cy = (int)(((float)i + 0.5f) * __builtin_amdgcn_rcpf((float)bx.z));
         else cy = i / bx.z;
         const int cx = i - cy * bx.z;
-        rs_test_pixel(s_p[w][j][0], s_p[w][j][1], s_p[w][j][2], bx.x + cx, bx.y + cy, W, xs, xo, ys, yo, (unsigned)bx.w, kb, pv, exp);
+        rs_test_pixel(s_p[w][j][0], s_p[w][j][1], s_p[w][j][2], bx.x + cx, bx.y + cy, W, xs, xo, ys, yo, (unsigned)bx.w, kb, pv);
     }
     }  // (!BIN)
     // ---- the big boxes of this work-group: their TILES are pooled like the pixels above (prefix of the tile counts, a search per
@@ -466,10 +448,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
             const float fxm = fmaxf(fabsf(__builtin_fmaf(xs, (float)xl, xo)), fabsf(__builtin_fmaf(xs, (float)xh, xo)));
             int xa, xb;
             rs_row_span(q0, q1, q2, __builtin_fmaf(ys, (float)py, yo), xs, xo, fxm, xl, xh, xa, xb);
-#ifdef A3D_EXPERIMENT
-            if (exp == 111) { xa = xl; xb = xh; }  // measurement: surviving tiles pixel by pixel (trained-like mesh: 49.7 against 47.6 us with the spans)
-#endif
-            for (int px = xa; px <= xb; ++px) rs_test_pixel(q0, q1, q2, px, py, W, xs, xo, ys, yo, (unsigned)bx.w, kb, pv, exp);
+            for (int px = xa; px <= xb; ++px) rs_test_pixel(q0, q1, q2, px, py, W, xs, xo, ys, yo, (unsigned)bx.w, kb, pv);
         }
         __syncthreads();
         if (threadIdx.x == 0) s_ns = 0;
@@ -672,18 +651,7 @@ __global__ __launch_bounds__(256) void rs_fine_kernel(const float4* __restrict__
 // ``p_cap``: rows the caller allocated for the list (it does not know P yet: the previous frame's + a margin); entries past it are
 // dropped and the caller, who reads P from the group sums as before, re-runs a3d_cover_gbuffer_fwd when P > p_cap (the texels, the
 // block counts and the sums are complete either way).
-__device__ __forceinline__ int rs_await(const int* p, int* timeout, int exp = 0) {
-#ifdef A3D_EXPERIMENT
-    if (exp == 61) {  // measurement: poll with agent-scope LOADS (see below)
-        int w = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        for (int spin = 0; w == 0 && spin < (1 << 12); ++spin) {
-            __builtin_amdgcn_s_sleep(8);
-            w = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        if (w == 0) { *timeout = 1; return 0; }
-        return w - 1;
-    }
-#endif
+__device__ __forceinline__ int rs_await(const int* p, int* timeout) {
     // (a RETURNING atomic, not a load: the flags live in ordinary device memory, which an XCD's L2 caches without cross-XCD coherence inside
     // a kernel -- an sc1 load that has once fetched the line keeps answering from it, and the first version of this loop spun for
     // seconds on flags that had long been published; atomics are performed at the memory side, where the publishers' adds land)
@@ -704,7 +672,7 @@ __global__ __launch_bounds__(256) void rs_resolve_cover_kernel(const float4* __r
                                                                const float* __restrict__ v_pos, const float* __restrict__ v_nrm,
                                                                const float* __restrict__ prior, int prior_batch, float* __restrict__ out,
                                                                const float* __restrict__ extra, int E, float* __restrict__ extra_out,
-                                                               float4* __restrict__ zero_rows, long long n_zero4, int exp,
+                                                               float4* __restrict__ zero_rows, long long n_zero4,
                                                                const GbAux aux) {
     float* __restrict__ tex_out = aux.tex_out;
     long long* __restrict__ img_out = aux.img_out;
@@ -753,7 +721,7 @@ __global__ __launch_bounds__(256) void rs_resolve_cover_kernel(const float4* __r
     const bool pads = L == nb_total - 1 && aux.pad_to > 0 && (aux.tex_out || aux.img_out);
     if (wave == 0 && (cnt > 0 || last_of_group)) {
         int timeout = 0;
-        int own = lane < r ? rs_await(blk_flag + g * A3D_COVER_GROUP + lane, &timeout, exp) : 0;  // earlier blocks of my group
+        int own = lane < r ? rs_await(blk_flag + g * A3D_COVER_GROUP + lane, &timeout) : 0;  // earlier blocks of my group
         own = a3d_group_sum(own);
         // (a group's total depends on its own blocks' counts ONLY and is published before this wave waits for the totals of earlier groups: no
         // chain from group to group)
@@ -763,7 +731,7 @@ __global__ __launch_bounds__(256) void rs_resolve_cover_kernel(const float4* __r
         }
         if (cnt > 0 || pads) {
             int before = 0;
-            for (int j = lane; j < g; j += 64) before += rs_await(grp_flag + j, &timeout, exp);  // earlier groups
+            for (int j = lane; j < g; j += 64) before += rs_await(grp_flag + j, &timeout);  // earlier groups
             before = a3d_group_sum(before);
             if (lane == 0) { s_off = before + own; s_total = before + own + cnt; }
         }
@@ -874,48 +842,6 @@ __global__ __launch_bounds__(256) void rs_bwd_kernel(const float4* __restrict__ 
     A3D_STAMP(4, 5);
 }
 
-// the per-pixel form of rounds 1-5 (four lanes per pixel, one line-coalesced request per (pixel, vertex)): kept for the A/B of
-// tools/shim_bwd_bench.py in the experiment build (A3D_EXP=140); the product library never launches it
-__global__ __launch_bounds__(256) void rs_bwd_pixel_kernel(const float4* __restrict__ g_rast, const float4* __restrict__ rast,
-                                                     const float4* __restrict__ clip, int clip_batch, const int* __restrict__ tri,
-                                                     int V, int F, int H, int W, long long npix, float* __restrict__ g_clip) {
-    const long long t4 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long i = t4 >> 2;
-    const int sub = (int)(t4 & 3);
-    if (i >= npix || sub == 2) return;
-    const float4 r = rast[i];
-    const int f = (int)r.w - 1;
-    if (f < 0 || f >= F) return;
-    const float4 g = g_rast[i];
-    if (g.x == 0.f && g.y == 0.f) return;
-    const unsigned hw = (unsigned)H * (unsigned)W;
-    const int b = (int)((unsigned)i / hw);
-    const int rem = (int)((unsigned)i - (unsigned)b * hw);
-    const int py = rem / W, px = rem - py * W;
-    const long long vb = clip_batch == 1 ? 0ll : (long long)b * V;
-    const int i0 = tri[3 * f], i1 = tri[3 * f + 1], i2 = tri[3 * f + 2];
-    const float4 p0 = clip[vb + i0], p1 = clip[vb + i1], p2 = clip[vb + i2];
-    const float fx = ((float)px + 0.5f) * (2.f / (float)W) - 1.f;
-    const float fy = ((float)py + 0.5f) * (2.f / (float)H) - 1.f;
-    const float q0x = p0.x - fx * p0.w, q0y = p0.y - fy * p0.w;
-    const float q1x = p1.x - fx * p1.w, q1y = p1.y - fy * p1.w;
-    const float q2x = p2.x - fx * p2.w, q2y = p2.y - fy * p2.w;
-    const float a0 = q1x * q2y - q1y * q2x, a1 = q2x * q0y - q2y * q0x, a2 = q0x * q1y - q0y * q1x;
-    const float s = a0 + a1 + a2;
-    if (s == 0.f) return;
-    const float is = 1.f / s;
-    const float u = a0 * is, v = a1 * is;
-    const float t = g.x * u + g.y * v;
-    const float ga0 = (g.x - t) * is, ga1 = (g.y - t) * is, ga2 = -t * is;
-    const float g0x = -ga1 * q2y + ga2 * q1y, g0y = ga1 * q2x - ga2 * q1x;
-    const float g1x = ga0 * q2y - ga2 * q0y, g1y = -ga0 * q2x + ga2 * q0x;
-    const float g2x = -ga0 * q1y + ga1 * q0y, g2y = ga0 * q1x - ga1 * q0x;
-    auto comp = [&](float gx, float gy) { return sub == 0 ? gx : (sub == 1 ? gy : -fx * gx - fy * gy); };
-    atomicAdd(g_clip + (vb + i0) * 4 + sub, comp(g0x, g0y));
-    atomicAdd(g_clip + (vb + i1) * 4 + sub, comp(g1x, g1y));
-    atomicAdd(g_clip + (vb + i2) * 4 + sub, comp(g2x, g2y));
-}
-
 extern "C" size_t a3d_rast_scratch_bytes(int B, int H, int W) { return sizeof(unsigned long long) * (size_t)B * (size_t)H * (size_t)W; }
 
 // binned path: per 8x8 tile a count and a list of ``cap`` triangle ids; 0 when the frame cannot take the path (not whole tiles / blocks,
@@ -997,7 +923,7 @@ extern "C" int a3d_rast_fwd(const float* clip, int clip_batch, const int32_t* tr
                        (const float4*)clip, clip_batch, \
                        tri, V, F, H, W, keys, (const float4*)prev_rast_or_null, nb_tri, (float2*)aa_screen_or_null, aa_count_or_null, \
                        a3d_aa_shards(), cover_scratch_or_null ? (int*)cover_scratch_or_null + cover_nb : nullptr, cover_ng, nb_screen, \
-                       topo_off_or_null, topo_adj_or_null, topo_opp_or_null, nb_opp, nj, a3d_exp() == 43 ? 0 : 1, a3d_exp(), bins); \
+                       topo_off_or_null, topo_adj_or_null, topo_opp_or_null, nb_opp, nj, bins); \
 
     if (binned) { RS_LAUNCH_TRI(1, true) } else if (lpt == 4) { RS_LAUNCH_TRI(4, false) } else if (lpt == 2) { RS_LAUNCH_TRI(2, false) } else { RS_LAUNCH_TRI(1, false) }
 #undef RS_LAUNCH_TRI
@@ -1053,7 +979,7 @@ extern "C" int a3d_rast_resolve_gbuffer_fwd(const float* clip, int clip_batch, c
     hipLaunchKernelGGL(rs_resolve_cover_kernel, dim3(a3d_div_up((long long)H * W, 256), B), dim3(256), 0, (hipStream_t)stream, (const float4*)clip, clip_batch,
                        tri, V, F, H, W, (unsigned long long*)scratch, (float4*)rast, cs, group_sum, blk_flag, blk_flag + nb, nb, (long long*)pix,
                        inv_or_null, (long long)p_cap, v_pos, v_nrm, prior, prior_batch, out, extra_or_null, E, extra_out_or_null,
-                       (float4*)g_rows_to_clear_or_null, n_zero4, a3d_exp(), gb_aux_of(aux_or_null));
+                       (float4*)g_rows_to_clear_or_null, n_zero4, gb_aux_of(aux_or_null));
     A3D_LAUNCH_CHECK();
     return A3D_OK;
 }
@@ -1096,12 +1022,6 @@ extern "C" int a3d_rast_bwd(const float* g_rast, const float* rast, const float*
     const long long npix = (long long)B * H * W;
     A3D_CHECK_ARG(npix < 0x7fffffffll && B <= 65535 && (long long)clip_batch * V < 0x7fffffffll);
     const int tiles_x = a3d_div_up(W, TS_TILE), tiles_y = a3d_div_up(H, TS_TILE);
-    if (a3d_exp() == 140) {
-        hipLaunchKernelGGL(rs_bwd_pixel_kernel, dim3(a3d_div_up(4 * npix, 256)), dim3(256), 0, s, (const float4*)g_rast, (const float4*)rast,
-                           (const float4*)clip, clip_batch, tri, V, F, H, W, npix, g_clip);
-        A3D_LAUNCH_CHECK();
-        return A3D_OK;
-    }
     hipLaunchKernelGGL(rs_bwd_kernel, dim3(tiles_x * tiles_y, B), dim3(256), TileScatter::lds_bytes(4), s, (const float4*)g_rast, (const float4*)rast,
                        (const float4*)clip, clip_batch, tri, V, F, H, W, tiles_x, g_clip);
     A3D_LAUNCH_CHECK();

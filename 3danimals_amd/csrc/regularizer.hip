@@ -30,18 +30,6 @@ __device__ __forceinline__ void key_split(int key, int F, int& c, int& f) {
     f = key - c * F;
 }
 
-__device__ __forceinline__ void rg_sort8(int a[8]) {
-#define RG_CX(i, j) { const int x = min(a[i], a[j]), y = max(a[i], a[j]); a[i] = x; a[j] = y; }
-    RG_CX(0, 1) RG_CX(2, 3) RG_CX(4, 5) RG_CX(6, 7)
-    RG_CX(0, 2) RG_CX(1, 3) RG_CX(4, 6) RG_CX(5, 7)
-    RG_CX(1, 2) RG_CX(5, 6) RG_CX(0, 4) RG_CX(3, 7)
-    RG_CX(1, 5) RG_CX(2, 6)
-    RG_CX(1, 4) RG_CX(3, 6)
-    RG_CX(2, 4) RG_CX(3, 5)
-    RG_CX(3, 4)
-#undef RG_CX
-}
-
 // fn(key) for every entry of a list in ascending key order, whatever order it is stored in: up to eight keys are sorted in registers,
 // a longer list is re-read from memory for every entry
 template <typename Fn>
@@ -50,7 +38,7 @@ __device__ __forceinline__ void rg_each_key(const int* __restrict__ adj, int lo,
     if (cnt <= 8) {
         int keys[8];
         nr_load_keys(adj, lo, cnt, keys);
-        rg_sort8(keys);
+        a3d_sort8(keys);
 #pragma unroll
         for (int e = 0; e < 8; ++e)
             if (e < cnt) fn(keys[e]);

@@ -146,18 +146,6 @@ __device__ __forceinline__ TgFace tg_face(int key, int F, const int* __restrict_
     return r;
 }
 
-__device__ __forceinline__ void tg_sort8(int a[8]) {
-#define TG_CX(i, j) { const int x = min(a[i], a[j]), y = max(a[i], a[j]); a[i] = x; a[j] = y; }
-    TG_CX(0, 1) TG_CX(2, 3) TG_CX(4, 5) TG_CX(6, 7)
-    TG_CX(0, 2) TG_CX(1, 3) TG_CX(4, 6) TG_CX(5, 7)
-    TG_CX(1, 2) TG_CX(5, 6) TG_CX(0, 4) TG_CX(3, 7)
-    TG_CX(1, 5) TG_CX(2, 6)
-    TG_CX(1, 4) TG_CX(3, 6)
-    TG_CX(2, 4) TG_CX(3, 5)
-    TG_CX(3, 4)
-#undef TG_CX
-}
-
 // sum over the vertex's incident faces of the face tangent, in ascending key order (cnt >= 1)
 __device__ __forceinline__ D3 tg_sum(const float* __restrict__ vp, const float* __restrict__ uv, const int* __restrict__ tri,
                                      const int* __restrict__ ttri, const int* __restrict__ adj, int lo, int cnt, int F) {
@@ -189,7 +177,7 @@ __device__ __forceinline__ D3 tg_sum(const float* __restrict__ vp, const float* 
             }
         }
     }
-    tg_sort8(keys);
+    a3d_sort8(keys);
 #pragma unroll
     for (int e = 0; e < 8; ++e)
         if (e < cnt) add(keys[e]);

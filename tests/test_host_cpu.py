@@ -610,21 +610,24 @@ def test_bench_credit_table_is_frozen_against_the_survey_formulas():
     assert 9e6 < want["a3d_normals_bwd[B16]"] < 20e6 and want["a3d_skin_pose_fwd"] < 2.4e6 and want["a3d_skin_pose_bwd"] < 3.5e6
 
 
-def test_product_library_ignores_the_experiment_knob(monkeypatch):
-    """The A3D_EXP measurement knobs (tools/kernel_lab.py) are compiled into the experiment / profile builds only (csrc/build.py --exp /
-    --profile): the library the package loads never reads the environment, so no setting of a measurement can change what it computes."""
-    src = open(os.path.join(ROOT, "3danimals_amd", "csrc", "common.hip")).read()
-    body = src.split("int a3d_exp(void) {")[1].split("\n}")[0]
-    assert "#if defined(A3D_EXPERIMENT) || defined(A3D_PROFILE)" in body and body.count("getenv") == 1 and body.index("getenv") < body.index("#else")
+def test_product_library_ignores_the_experiment_knob():
+    """There is no experiment knob to ignore any more: no source under csrc/ reads the environment or names a measurement knob (the
+    dropped experiments live in the history), there is no experiment build of the library, and the library the
+    package loads does not import getenv -- so no setting of a measurement can change what it computes."""
     import glob
-
-    for path in glob.glob(os.path.join(ROOT, "3danimals_amd", "csrc", "*.hip")):  # every getenv sits behind the experiment macro
-        text = open(path).read()
-        for m in re.finditer(r"getenv\(", text):
-            before = text[: m.start()]
-            assert before.rfind("#if") > max(before.rfind("#endif"), before.rfind("#else")) and "A3D_EXPERIMENT" in before[before.rfind("#if"):], os.path.basename(path)
+    import inspect
     import subprocess
 
+    csrc = os.path.join(ROOT, "3danimals_amd", "csrc")
+    sources = glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h"))
+    assert len(sources) > 30
+    for path in sources:
+        text = open(path).read()
+        for name in ("getenv", "A3D_EXPERIMENT", "a3d_exp", "A3D_EXP", "A3D_GEMM_VARIANT", "A3D_SS_ROWS"):
+            assert name not in text, (os.path.basename(path), name)
+    build = importlib.import_module("3danimals_amd.csrc.build")
+    assert "exp" not in inspect.signature(build.build).parameters
+    assert "A3D_EXPERIMENT" not in open(os.path.join(csrc, "build.py")).read()
     lib = os.path.join(ROOT, "3danimals_amd", "lib", "liba3d_hip.so")
     syms = subprocess.run(["nm", "-D", "--undefined-only", lib], capture_output=True, text=True).stdout
     assert "getenv" not in syms, "the product library must not read the environment"

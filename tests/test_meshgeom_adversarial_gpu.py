@@ -14,7 +14,7 @@ at most two crossing edges feed -- 0 + a + b does not depend on the order -- and
 Normals: every case through ops.vertex_normals, then bit for bit: faces-first against prepass + gather, the three list layouts (sorted
 CSR, the lists of ops.mesh_topology, a hand-built fixed-stride layout with every list shuffled), the pair launch against two single
 ones, the forward riding in the rasteriser launch against the stand-alone launch, a strided upstream gradient against its contiguous
-copy.  The A3D_EXP 41 / 45 forms of the backward exist in experiment builds only and are not run here.
+copy.  (The one-launch and 12-byte-per-face forms of the backward were measured, dropped and removed: DESIGN.md section 4.)
 
 Measured on an MI355X, the largest figure over every run of a case, in units, with the float32 restatement's figure on the CPU in
 brackets (the bound is 4 x the bracket + 4 ulp; the largest ratio met is 2.7, g_v of the patch and of the mesh with a NaN vertex):
