@@ -1,4 +1,4 @@
-"""ctypes binding of liba3d_hip.so (include/a3d.h, include/a3d_bsdf.h, include/a3d_deriv.h, include/a3d_tangent.h, include/a3d_reg.h, include/a3d_envshade.h, include/a3d_sdfreg.h).  No fallback: if the library is missing we say so and stop."""
+"""ctypes binding of liba3d_hip.so (include/a3d.h, include/a3d_bsdf.h, include/a3d_deriv.h, include/a3d_tangent.h, include/a3d_reg.h, include/a3d_envshade.h, include/a3d_sdfreg.h, include/a3d_edt.h).  No fallback: if the library is missing we say so and stop."""
 from __future__ import annotations
 
 import ctypes
@@ -277,6 +277,14 @@ SDFREG_SIGNATURES = {
 SDF_BCE_BLOCK_EDGES = 1024  # A3D_SDF_BCE_BLOCK_EDGES
 SDF_BCE_PARTIAL_WORDS = 3  # A3D_SDF_BCE_PARTIAL_WORDS
 
+# the entry points of include/a3d_edt.h (same library, same a3d_version(); tests/test_edt_cpu.py checks this table against that header)
+EDT_SIGNATURES = {
+    "a3d_edt_scratch_bytes": (_c_size_t, [_c_int, _c_int, _c_int]),
+    "a3d_edt_fwd": (_c_int, [_p, _c_int, _c_float, _c_float, _c_int, _c_int, _c_int, ctypes.c_double, _p, _p, _p, _p, _p]),
+}
+EDT_MAX_SIDE = 4096  # A3D_EDT_MAX_SIDE
+EDT_SRC_U8, EDT_SRC_F32 = 0, 1  # A3D_EDT_SRC_*
+
 ABI_VERSION = 404  # a3d_version() of the library these signatures belong to (include/a3d.h)
 _lib = None
 
@@ -295,7 +303,7 @@ def lib():
                 "(or __graft_entry__.build()).  There is no CPU fallback for the HIP hot path."
             )
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(BSDF_SIGNATURES.items()) + list(DERIV_SIGNATURES.items()) + list(TANGENT_SIGNATURES.items()) + list(REG_SIGNATURES.items()) + list(ENVSHADE_SIGNATURES.items()) + list(SDFREG_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(BSDF_SIGNATURES.items()) + list(DERIV_SIGNATURES.items()) + list(TANGENT_SIGNATURES.items()) + list(REG_SIGNATURES.items()) + list(ENVSHADE_SIGNATURES.items()) + list(SDFREG_SIGNATURES.items()) + list(EDT_SIGNATURES.items()):
             fn = getattr(handle, name)  # AttributeError here == ABI drift
             fn.restype, fn.argtypes = res, args
         if handle.a3d_version() != ABI_VERSION:  # same symbols, other argument lists: a stale build must not be called

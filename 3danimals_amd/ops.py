@@ -3190,6 +3190,50 @@ def sdf_bce_reg_loss(sdf, all_edges):
     return _SdfBceReg.apply(sdf, cached)
 
 
+# ---------------------------------------------------------------------------------------------- exact Euclidean distance transform (include/a3d_edt.h)
+def distance_transform(src, scale=1.0, squared=False, return_indices=False, thresholds=None):
+    """The exact Euclidean distance of every pixel to the nearest ZERO pixel of its image (csrc/edt.hip: two launches, integers until the
+    final store, no atomics, no host synchronisation; the same bits on every run).  No autograd node: the result never requires grad.
+
+    ``src`` uint8 / bool [M,H,W] (non-zero is != 0) -> [M,H,W]; or float32 [N,H,W] with ``thresholds = (t_in, t_out)`` -> [N,2,H,W], both
+    channels of the reference's compute_distance_transform from one read of the mask: channel 0 is non-zero where m >= t_in, channel 1
+    where m <= t_out, a NaN is zero in both (the reference's np.uint8(m) / np.uint8(1 - m) on a mask in [0,1] is (1, 0)).
+    Returns float32 ``(float)(sqrt((double)d2) / scale)`` -- one float64 root, one float64 divide, one rounding -- or, with
+    ``squared``, the int32 squared distance d2 itself (above sides of 1024 neighbouring d2 share a float32 root).  With
+    ``return_indices`` also int32 ``idx``: the flat index qy * W + qx of a nearest zero pixel, the smallest one among equally near.
+    An image WITHOUT a zero pixel gets d2 = H * H + W * W everywhere and idx = -1: finite on purpose (scipy's distance_transform_edt
+    returns arbitrary values there; it is the one input on which the two differ).  1 <= H, W <= 4096, M * H * W < 2^31."""
+    if not torch.is_tensor(src) or src.dim() != 3:
+        raise ValueError(f"distance_transform: expected a [M,H,W] tensor, got {list(getattr(src, 'shape', [])) or type(src)}")
+    if src.dtype in (torch.uint8, torch.bool):
+        if thresholds is not None:
+            raise ValueError("distance_transform: thresholds belong to a float32 mask; a uint8 / bool source is non-zero where != 0")
+        kind, channels, t_in, t_out = _lib.EDT_SRC_U8, 1, 0.0, 0.0
+    elif src.dtype == torch.float32:
+        if thresholds is None or len(thresholds) != 2:
+            raise ValueError("distance_transform: a float32 mask needs thresholds=(t_in, t_out)")
+        kind, channels, (t_in, t_out) = _lib.EDT_SRC_F32, 2, (float(t) for t in thresholds)
+    else:
+        raise ValueError(f"distance_transform: expected uint8, bool or float32, got {src.dtype}")
+    n, h, w = (int(v) for v in src.shape)
+    m = n * channels
+    if n < 1 or not (1 <= h <= _lib.EDT_MAX_SIDE and 1 <= w <= _lib.EDT_MAX_SIDE) or m * h * w >= 1 << 31:
+        raise ValueError(f"distance_transform: {list(src.shape)} is outside 1 <= H, W <= {_lib.EDT_MAX_SIDE}, M * H * W < 2^31")
+    if not float(scale) > 0.0 or math.isinf(float(scale)):
+        raise ValueError(f"distance_transform: scale must be positive and finite, got {scale}")
+    require_device(src, what="distance_transform")
+    src = src.detach().contiguous()
+    if src.dtype == torch.bool:
+        src = src.view(torch.uint8)
+    shape = (n, 2, h, w) if channels == 2 else (n, h, w)
+    scratch = torch.empty(_lib.lib().a3d_edt_scratch_bytes(m, h, w), dtype=torch.uint8, device=src.device)
+    out = torch.empty(shape, dtype=torch.int32 if squared else torch.float32, device=src.device)
+    idx = torch.empty(shape, dtype=torch.int32, device=src.device) if return_indices else None
+    call("a3d_edt_fwd", ptr(src), kind, t_in, t_out, m, h, w, float(scale), ptr(scratch), None if squared else ptr(out), ptr(out) if squared else None,
+         ptr(idx), stream())
+    return (out, idx) if return_indices else out
+
+
 # ---------------------------------------------------------------------------------------------- mixed precision
 def _amp_wrap_functions():
     """Every autograd.Function of this module runs its forward with autocast OFF on float32 copies of half-precision inputs, and its

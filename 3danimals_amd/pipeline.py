@@ -228,7 +228,7 @@ class SyntheticScene(torch.nn.Module):
             arti0 = synthetic.seeded((B, F, 20, 3), seed + 5 + 7919 * pose_seed, -0.25, 0.25).to(dev)
             mask = self.forward_render(arti0, prior=prior, modes=["shaded"], with_nets=False)[0][:, 3]
             self.mask_gt = (mask > 0.5).float()
-            self.mask_dt = _distance_transforms(self.mask_gt).to(dev)
+            self.mask_dt = _distance_transforms(self.mask_gt)  # (on the GPU: ops.distance_transform, no host round trip)
         self.mask_valid = torch.ones(N, H, W, device=dev)
         self._eye4, self._proj = torch.eye(4, device=dev), synthetic.perspective(25.0).to(dev)
 
@@ -432,7 +432,18 @@ def prior_normal_regulariser(prior):
 
 def _distance_transforms(mask: torch.Tensor) -> torch.Tensor:
     """[B,H,W] {0,1} -> [B,2,H,W]: Euclidean distance to the mask and to its complement, normalised by the image size
-    (what ImageDataset stores as mask_dt; scipy EDT since cv2 is absent)."""
+    (what ImageDataset stores as mask_dt), on the mask's device.  Channel 0 is the distance OUTSIDE the mask to it, channel 1 the
+    distance inside to the background: the reverse of the reference's compute_distance_transform.
+    A mask on the GPU stays there (ops.distance_transform, csrc/edt.hip); a CPU mask takes scipy's EDT.  The two are bit for bit
+    equal on every mask that has both classes; for an all-zero or all-one image scipy returns arbitrary values in the channel that
+    has no zero pixel, the GPU path sqrt(H * H + W * W) / max(H, W)."""
+    if mask.is_cuda:
+        from . import ops
+
+        # (as two bool images, [~m, m]: this function's channel order, and a NaN lands where the numpy statements below put it)
+        m = mask.detach() > 0.5
+        return ops.distance_transform(torch.stack([~m, m], dim=1).reshape(-1, *m.shape[1:]), scale=float(max(m.shape[1:]))).reshape(
+            m.shape[0], 2, *m.shape[1:])
     from scipy.ndimage import distance_transform_edt
 
     m = mask.detach().cpu().numpy() > 0.5
