@@ -1,4 +1,4 @@
-"""ctypes binding of liba3d_hip.so (include/a3d.h, include/a3d_bsdf.h, include/a3d_deriv.h, include/a3d_tangent.h, include/a3d_reg.h, include/a3d_envshade.h, include/a3d_sdfreg.h, include/a3d_edt.h).  No fallback: if the library is missing we say so and stop."""
+"""ctypes binding of liba3d_hip.so (include/a3d.h, include/a3d_bsdf.h, include/a3d_deriv.h, include/a3d_tangent.h, include/a3d_reg.h, include/a3d_envshade.h, include/a3d_sdfreg.h, include/a3d_edt.h, include/a3d_fields.h).  No fallback: if the library is missing we say so and stop."""
 from __future__ import annotations
 
 import ctypes
@@ -285,6 +285,17 @@ EDT_SIGNATURES = {
 EDT_MAX_SIDE = 4096  # A3D_EDT_MAX_SIDE
 EDT_SRC_U8, EDT_SRC_F32 = 0, 1  # A3D_EDT_SRC_*
 
+# the entry points of include/a3d_fields.h (same library, same a3d_version(); tests/test_fieldhead_cpu.py checks this table against that header)
+FIELDS_SIGNATURES = {
+    "a3d_field_head_scratch_bytes": (_c_size_t, [ctypes.c_int64, _c_int]),
+    "a3d_field_head_fwd": (_c_int, [_p, _p, _p, _p, _c_int, ctypes.c_int64, _c_int, _p, _p, _p]),
+    "a3d_field_head_bwd": (_c_int, [_p, _p, _p, _p, _p, _c_int, ctypes.c_int64, _c_int, _p, _p, _p, _p]),
+}
+FIELD_HEAD_WIDTH = 256  # A3D_FIELD_HEAD_WIDTH
+FIELD_HEAD_MAX_C = 16  # A3D_FIELD_HEAD_MAX_C
+FIELD_HEAD_WG_ROWS = 512  # A3D_FIELD_HEAD_WG_ROWS
+FIELD_HEAD_ACT_NONE, FIELD_HEAD_ACT_SIGMOID = 0, 1  # A3D_FIELD_HEAD_ACT_*
+
 ABI_VERSION = 404  # a3d_version() of the library these signatures belong to (include/a3d.h)
 _lib = None
 
@@ -303,7 +314,7 @@ def lib():
                 "(or __graft_entry__.build()).  There is no CPU fallback for the HIP hot path."
             )
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(BSDF_SIGNATURES.items()) + list(DERIV_SIGNATURES.items()) + list(TANGENT_SIGNATURES.items()) + list(REG_SIGNATURES.items()) + list(ENVSHADE_SIGNATURES.items()) + list(SDFREG_SIGNATURES.items()) + list(EDT_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(BSDF_SIGNATURES.items()) + list(DERIV_SIGNATURES.items()) + list(TANGENT_SIGNATURES.items()) + list(REG_SIGNATURES.items()) + list(ENVSHADE_SIGNATURES.items()) + list(SDFREG_SIGNATURES.items()) + list(EDT_SIGNATURES.items()) + list(FIELDS_SIGNATURES.items()):
             fn = getattr(handle, name)  # AttributeError here == ABI drift
             fn.restype, fn.argtypes = res, args
         if handle.a3d_version() != ABI_VERSION:  # same symbols, other argument lists: a stale build must not be called

@@ -15,7 +15,8 @@ Same mathematics as the reference classes, evaluated faster for long point lists
 DESIGN.md "What is not a HIP kernel"): split-K weight gradients (``_LinearSplitK``), ReLU in the GEMM epilogue
 (``_LinearReLUSplitK``), the per-image feature as a [B,C] GEMM plus a per-point add folded into the ReLU pass
 (``CoordMLP._forward_indexed``), the input stage [x, sin, cos, 1] from one HIP kernel with the first bias as a weight column
-(``CoordMLP._fused_input``), and the frequency table kept on the device.  Short lists (the SDF regulariser, which needs double
+(``CoordMLP._fused_input``), the output stage Linear(256 -> C <= 16) [+ sigmoid] [+ min_max] and its adjoint as one HIP pass over the
+hidden vectors each way (``_FieldStackHead``, csrc/fieldhead.hip), and the frequency table kept on the device.  Short lists (the SDF regulariser, which needs double
 backward) take the plain torch path.
 """
 from __future__ import annotations
@@ -68,6 +69,11 @@ class HarmonicEmbedding(nn.Module):
 
 
 USE_FIELD_STACK = True  # the hidden stack of a field as one autograd node with MFMA input-gradient GEMMs (_FieldStack)
+USE_FIELD_HEAD = True  # ... and the output stage Linear(256 -> C <= 16) [+ sigmoid] [+ min_max] in the same node (_FieldStackHead)
+# A head without activation and map (the deformation field) keeps the library GEMM in the FORWARD: its values are vertex offsets, and the
+# rasteriser's edge blending turns a last-bit difference there into 4e-6 of a pixel's colour; with the same product as before, the step's
+# images stay within rounding of what they were.  Its backward is the fused pass all the same.
+_PLAIN_HEAD_FORWARD_GEMM = True
 SPLITK_MIN_ROWS = 65536  # point lists at least this long take the split-K weight gradient below
 SPLITK_PARTS = 16
 
@@ -149,16 +155,7 @@ class _FieldStack(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x_emb, w_in, per_image, index, w_first, *hidden):
-        from . import ops
-
-        zero = _zero_bias(x_emb, w_in)
-        ys = [torch._addmm_activation(zero, x_emb, w_in.t(), use_gelu=False)]
-        if w_first is not None:
-            y = ys[0].mm(w_first.t())
-            ops.rows_add_relu_raw_(y, per_image, index)
-            ys.append(y)
-        for w in hidden:
-            ys.append(torch._addmm_activation(zero, ys[-1], w.t(), use_gelu=False))
+        ys = _stack_forward(x_emb, w_in, per_image, index, w_first, hidden)
         ctx.save_for_backward(x_emb, w_in, index, w_first, *hidden, *ys)
         ctx.n_hidden, ctx.n_images = len(hidden), (per_image.shape[0] if per_image is not None else 0)
         return ys[-1]
@@ -166,26 +163,84 @@ class _FieldStack(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        from . import ops
-
         saved = ctx.saved_tensors
         x_emb, w_in, index, w_first = saved[:4]
         hidden, ys = saved[4:4 + ctx.n_hidden], saved[4 + ctx.n_hidden:]
         g = torch.ops.aten.threshold_backward(g.contiguous(), ys[-1], 0)
-        g_hidden = []
-        for i in range(ctx.n_hidden - 1, -1, -1):
-            y_prev = ys[len(ys) - ctx.n_hidden - 1 + i]
-            g_hidden.append(_split_k_weight_grad(g, y_prev))
-            g = ops.gemm_nn_relumask(g, hidden[i], y_prev)
-        g_hidden.reverse()
-        g_rows = g_first = None
-        if w_first is not None:
-            g_rows = ops.rows_segsum_raw(g, index, ctx.n_images)
-            g_first = _split_k_weight_grad(g, ys[0])
-            g = ops.gemm_nn_relumask(g, w_first, ys[0])
-        g_in = _split_k_weight_grad(g, x_emb)
-        g_x = g.mm(w_in) if ctx.needs_input_grad[0] else None
+        g_x, g_in, g_rows, g_first, g_hidden = _stack_backward(g, x_emb, w_in, index, w_first, hidden, ys, ctx.n_images, ctx.needs_input_grad[0])
         return (g_x, g_in, g_rows, None, g_first, *g_hidden)
+
+
+def _stack_forward(x_emb, w_in, per_image, index, w_first, hidden):
+    """[y0, (y1,) .. y_n] of _FieldStack."""
+    from . import ops
+
+    zero = _zero_bias(x_emb, w_in)
+    ys = [torch._addmm_activation(zero, x_emb, w_in.t(), use_gelu=False)]
+    if w_first is not None:
+        y = ys[0].mm(w_first.t())
+        ops.rows_add_relu_raw_(y, per_image, index)
+        ys.append(y)
+    for w in hidden:
+        ys.append(torch._addmm_activation(zero, ys[-1], w.t(), use_gelu=False))
+    return ys
+
+
+def _stack_backward(g, x_emb, w_in, index, w_first, hidden, ys, n_images, need_x):
+    """_FieldStack's backward from g = the gradient of ys[-1] with that layer's ReLU adjoint applied -> (g_x, g_in, g_rows, g_first, g_hidden)."""
+    from . import ops
+
+    n_hidden = len(hidden)
+    g_hidden = []
+    for i in range(n_hidden - 1, -1, -1):
+        y_prev = ys[len(ys) - n_hidden - 1 + i]
+        g_hidden.append(_split_k_weight_grad(g, y_prev))
+        g = ops.gemm_nn_relumask(g, hidden[i], y_prev)
+    g_hidden.reverse()
+    g_rows = g_first = None
+    if w_first is not None:
+        g_rows = ops.rows_segsum_raw(g, index, n_images)
+        g_first = _split_k_weight_grad(g, ys[0])
+        g = ops.gemm_nn_relumask(g, w_first, ys[0])
+    g_in = _split_k_weight_grad(g, x_emb)
+    g_x = g.mm(w_in) if need_x else None
+    return g_x, g_in, g_rows, g_first, g_hidden
+
+
+class _FieldStackHead(torch.autograd.Function):
+    """_FieldStack with the field's output stage in the same node (csrc/fieldhead.hip):
+
+        out = act(y_n W_head^T) * scale + lo                      Linear(256 -> C <= 16), none / sigmoid, the min_max map
+
+    The forward reads y_n once; the backward starts with ONE pass over y_n that applies the map's, the activation's and the Linear's
+    adjoints, masks the result with (y_n > 0) -- so the stack's last threshold_backward pass is gone too -- and sums the head's weight
+    gradient (deterministically: per-work-group partial sums, added in a fixed order).  First-order only, like _FieldStack.
+    """
+
+    @staticmethod
+    def forward(ctx, x_emb, w_in, per_image, index, w_first, w_head, lo, scale, act, *hidden):
+        from . import ops
+
+        ys = _stack_forward(x_emb, w_in, per_image, index, w_first, hidden)
+        if _PLAIN_HEAD_FORWARD_GEMM and not act and scale is None:
+            s, out = None, ys[-1].mm(w_head.t())
+        else:
+            s, out = ops.field_head_fwd(ys[-1], w_head, lo, scale, act)
+        ctx.save_for_backward(x_emb, w_in, index, w_first, w_head, scale, s if act else None, *hidden, *ys)  # (s: the sigmoid's adjoint)
+        ctx.n_hidden, ctx.n_images, ctx.act = len(hidden), (per_image.shape[0] if per_image is not None else 0), act
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        from . import ops
+
+        saved = ctx.saved_tensors
+        x_emb, w_in, index, w_first, w_head, scale, s = saved[:7]
+        hidden, ys = saved[7:7 + ctx.n_hidden], saved[7 + ctx.n_hidden:]
+        g, g_head = ops.field_head_bwd(g, s, ys[-1], w_head, scale, ctx.act)
+        g_x, g_in, g_rows, g_first, g_hidden = _stack_backward(g, x_emb, w_in, index, w_first, hidden, ys, ctx.n_images, ctx.needs_input_grad[0])
+        return (g_x, g_in, g_rows, None, g_first, g_head, None, None, None, *g_hidden)
 
 
 def _long_list(x, weight):
@@ -379,6 +434,26 @@ class CoordMLP(nn.Module):
             n_pairs += 1
         return n_pairs >= 1
 
+    def _fused_head(self, tail):
+        """(weight, lo, scale, act) when ``tail`` -- the layers behind the stack's Linear/ReLU pairs -- is exactly one bias-free
+        Linear(256 -> C <= 16), optionally followed by a Sigmoid, with an optional min_max: the output stage _FieldStackHead fuses.
+        None for everything else (tanh, dropout, a biased head ...), which keeps the layer-by-layer tail of _stacked.  Reached only
+        from _stacked, that is behind _stack_ok: long lists with grad enabled -- never the SDF's grad-free grid pass or a short list."""
+        if not USE_FIELD_HEAD or not 1 <= len(tail) <= 2 or not isinstance(tail[0], nn.Linear) or tail[0].bias is not None:
+            return None
+        weight = tail[0].weight
+        if weight.shape[1] != 256 or not 1 <= weight.shape[0] <= 16 or weight.dtype != torch.float32:
+            return None
+        if len(tail) == 2 and not isinstance(tail[1], nn.Sigmoid):
+            return None
+        lo = scale = None
+        if self.min_max is not None:
+            if tuple(self.min_max.shape) != (weight.shape[0], 2) or self.min_max.requires_grad or self.min_max.dtype != torch.float32:
+                return None
+            lo = self.min_max[:, 0].contiguous()
+            scale = self.min_max[:, 1] - self.min_max[:, 0]
+        return weight, lo, scale, len(tail) - 1
+
     def _stacked(self, x, feat, feat_index):
         from . import ops
 
@@ -389,12 +464,15 @@ class CoordMLP(nn.Module):
             i += 2
         x_emb = ops.harmonic_embed(x, self.embedder._frequencies(x.device), symmetrize=self.symmetrize, ones=True)
         w_in = torch.cat([self.in_layer.weight, self.in_layer.bias[:, None]], dim=1)
+        per_image = w_first = None
         if feat is not None:
-            first = pairs[0].weight
+            first, pairs = pairs[0].weight, pairs[1:]
             per_image = F.linear(torch.relu(feat), first[:, 256:])  # [B, 256]
-            h = _FieldStack.apply(x_emb, w_in, per_image, feat_index, first[:, :256].contiguous(), *[l.weight for l in pairs[1:]])
-        else:
-            h = _FieldStack.apply(x_emb, w_in, None, None, None, *[l.weight for l in pairs])
+            w_first = first[:, :256].contiguous()
+        head = self._fused_head(layers[i:])
+        if head is not None:
+            return _FieldStackHead.apply(x_emb, w_in, per_image, feat_index if feat is not None else None, w_first, *head, *[l.weight for l in pairs])
+        h = _FieldStack.apply(x_emb, w_in, per_image, feat_index if feat is not None else None, w_first, *[l.weight for l in pairs])
         for layer in layers[i:]:
             h = linear(h, layer.weight, layer.bias) if isinstance(layer, nn.Linear) else layer(h)
         if self.min_max is not None:

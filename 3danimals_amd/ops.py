@@ -2082,6 +2082,53 @@ def gemm_nn_relumask(a, b, x=None):
     return c
 
 
+def _field_head_args(what, h, weight, scale, act):
+    if h.dim() != 2 or weight.dim() != 2 or h.shape[1] != _lib.FIELD_HEAD_WIDTH or weight.shape[1] != _lib.FIELD_HEAD_WIDTH \
+            or not 1 <= weight.shape[0] <= _lib.FIELD_HEAD_MAX_C or not 1 <= h.shape[0] < 1 << 31:
+        raise ValueError(f"{what}: expected h [M,{_lib.FIELD_HEAD_WIDTH}] with M >= 1 and weight [C <= {_lib.FIELD_HEAD_MAX_C},{_lib.FIELD_HEAD_WIDTH}], "
+                         f"got {list(h.shape)} and {list(weight.shape)}")
+    if act not in (_lib.FIELD_HEAD_ACT_NONE, _lib.FIELD_HEAD_ACT_SIGMOID):
+        raise ValueError(f"{what}: act is 0 (none) or 1 (sigmoid), got {act!r}")
+    if scale is not None and tuple(scale.shape) != (weight.shape[0],):
+        raise ValueError(f"{what}: scale / lo must be [C] = [{weight.shape[0]}], got {list(scale.shape)}")
+    return int(h.shape[0]), int(weight.shape[0])
+
+
+def field_head_fwd(h, weight, lo=None, scale=None, act=0):
+    """s = act(h [M,256] @ weight [C,256]^T), out = s * scale + lo  (csrc/fieldhead.hip, fp32 MFMA, one pass over h).  ``act`` 0: none,
+    1: sigmoid; ``lo`` / ``scale`` [C] or both None.  -> (s, out), s None when there is neither an activation nor the map.
+    No autograd: it is the output stage inside hostnets' stack Function."""
+    require_device(h, weight, lo, scale, what="field_head_fwd")
+    if (lo is None) != (scale is None):
+        raise ValueError("field_head_fwd: lo and scale come together")
+    M, C = _field_head_args("field_head_fwd", h, weight, scale, act)
+    if lo is not None and tuple(lo.shape) != (C,):
+        raise ValueError(f"field_head_fwd: scale / lo must be [C] = [{C}], got {list(lo.shape)}")
+    h, weight = f32c(h), f32c(weight)
+    out = torch.empty((M, C), dtype=torch.float32, device=h.device)
+    s = torch.empty((M, C), dtype=torch.float32, device=h.device) if (act or scale is not None) else None
+    call("a3d_field_head_fwd", ptr(h), ptr(weight), None if lo is None else ptr(f32h(lo)), None if scale is None else ptr(f32h(scale)), int(act), M, C,
+         ptr(s), ptr(out), stream(), tag=f"[C{C}]")
+    return s, out
+
+
+def field_head_bwd(g_out, s, h, weight, scale=None, act=0):
+    """The adjoint of field_head_fwd and of the ReLU that produced h, one pass over h: with ga = g_out * scale * act'(s),
+    g_h = (ga @ weight) * (h > 0) [M,256] and g_w = ga^T @ h [C,256] (per-work-group partial sums added in a fixed order by a second
+    launch: no atomics, the same bits on every run).  ``s`` is what the forward returned (None without the sigmoid).  No autograd."""
+    require_device(g_out, s, h, weight, scale, what="field_head_bwd")
+    M, C = _field_head_args("field_head_bwd", h, weight, scale, act)
+    if tuple(g_out.shape) != (M, C) or (act and (s is None or tuple(s.shape) != (M, C))):
+        raise ValueError(f"field_head_bwd: g_out and s must be [M,C] = [{M},{C}], got {list(g_out.shape)} and {None if s is None else list(s.shape)}")
+    g_out, h, weight = f32c(g_out), f32c(h), f32c(weight)
+    scratch = torch.empty(_lib.lib().a3d_field_head_scratch_bytes(M, C), dtype=torch.uint8, device=h.device)
+    g_h = torch.empty((M, _lib.FIELD_HEAD_WIDTH), dtype=torch.float32, device=h.device)
+    g_w = torch.empty((C, _lib.FIELD_HEAD_WIDTH), dtype=torch.float32, device=h.device)
+    call("a3d_field_head_bwd", ptr(g_out), None if not act else ptr(f32h(s)), ptr(h), ptr(weight), None if scale is None else ptr(f32h(scale)), int(act),
+         M, C, ptr(scratch), ptr(g_h), ptr(g_w), stream(), tag=f"[C{C}]")
+    return g_h, g_w
+
+
 # ---------------------------------------------------------------------------------------------- texture sampling
 _TEX_FILTERS = {"nearest": 0, "linear": 1, "linear-mipmap-nearest": 2, "linear-mipmap-linear": 3}
 _TEX_BOUNDARIES = {"wrap": 0, "clamp": 1, "zero": 2, "cube": 3}

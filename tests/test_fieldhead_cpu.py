@@ -1,0 +1,172 @@
+"""The fields' output stage without a GPU: the ninth ABI surface (include/a3d_fields.h against _lib.FIELDS_SIGNATURES) with the other
+eight untouched, argument validation before any launch, the float64 restatement (tests/fieldhead_ref.py) against torch.autograd, the
+noise floor the GPU test is held to, and which networks hostnets hands to the fused stage."""
+import ctypes
+import importlib
+import math
+import os
+import sys
+
+import pytest
+import torch
+
+from conftest import ROOT
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import fieldhead_ref as R  # noqa: E402
+from test_bsdf_cpu import _prototypes  # noqa: E402
+
+ENTRIES = ("a3d_field_head_scratch_bytes", "a3d_field_head_fwd", "a3d_field_head_bwd")
+FAKE = 0x1000  # non-NULL, 16-byte aligned, never dereferenced
+
+
+def _L():
+    return importlib.import_module("3danimals_amd._lib")
+
+
+def test_ninth_header_matches_the_ninth_table_and_the_other_surfaces_are_untouched():
+    L = _L()
+    path = os.path.join(ROOT, "include", "a3d_fields.h")
+    protos = _prototypes(path)
+    assert set(protos) == set(L.FIELDS_SIGNATURES) == set(ENTRIES), set(protos) ^ set(L.FIELDS_SIGNATURES)
+    ck = {ctypes.c_void_p: "ptr", ctypes.c_int: "int", ctypes.c_int64: "int64", ctypes.c_float: "float", ctypes.c_size_t: "size_t"}
+    for name, (res, args) in L.FIELDS_SIGNATURES.items():
+        assert protos[name] == (ck[res], [ck[a] for a in args]), (name, protos[name])
+        assert hasattr(L.lib(), name), name
+    assert len(protos["a3d_field_head_fwd"][1]) == 10 and len(protos["a3d_field_head_bwd"][1]) == 12
+    assert protos["a3d_field_head_scratch_bytes"] == ("size_t", ["int64", "int"])
+    others = (L.SIGNATURES, L.BSDF_SIGNATURES, L.DERIV_SIGNATURES, L.TANGENT_SIGNATURES, L.REG_SIGNATURES, L.ENVSHADE_SIGNATURES, L.SDFREG_SIGNATURES,
+              L.EDT_SIGNATURES)
+    assert tuple(len(t) for t in others) == (92, 5, 4, 5, 8, 2, 2, 2)
+    for other in others:
+        assert not set(protos) & set(other)
+    first = _prototypes(os.path.join(ROOT, "include", "a3d.h"))
+    assert set(first) == set(L.SIGNATURES) and not set(first) & set(protos)
+    assert L.lib().a3d_version() == L.ABI_VERSION == 404
+    text = open(path).read()
+    for macro, value in (("WIDTH", L.FIELD_HEAD_WIDTH), ("MAX_C", L.FIELD_HEAD_MAX_C), ("WG_ROWS", L.FIELD_HEAD_WG_ROWS),
+                         ("ACT_NONE", L.FIELD_HEAD_ACT_NONE), ("ACT_SIGMOID", L.FIELD_HEAD_ACT_SIGMOID)):
+        assert "#define A3D_FIELD_HEAD_%s %d" % (macro, value) in text, macro
+    assert R.WG_ROWS == L.FIELD_HEAD_WG_ROWS and 2 * R.WG_ROWS + 1 in R.ROWS
+
+
+def test_entry_points_refuse_invalid_arguments_before_anything_is_launched():
+    """None of the pointers below is ever dereferenced and nothing is launched (this runs without a GPU)."""
+    lib = _L().lib()
+    fwd = dict(h=FAKE, W=FAKE, lo=FAKE, scale=FAKE, act=1, M=100, C=9, s=FAKE, out=FAKE)
+    bwd = dict(g_out=FAKE, s=FAKE, h=FAKE, W=FAKE, scale=FAKE, act=1, M=100, C=9, scratch=FAKE, g_h=FAKE, g_W=FAKE)
+
+    def refused(fn, good, **bad):
+        assert getattr(lib, fn)(*dict(good, **bad).values(), None) == -1, (fn, bad)
+        msg = lib.a3d_last_error().decode()
+        assert "invalid argument" in msg and fn in msg, (bad, msg)
+
+    for fn, good in (("a3d_field_head_fwd", fwd), ("a3d_field_head_bwd", bwd)):
+        for bad in (dict(M=0), dict(M=-1), dict(M=1 << 31), dict(C=0), dict(C=17), dict(act=2), dict(act=-1), dict(h=None), dict(W=None),
+                    dict(h=FAKE + 4), dict(W=FAKE + 8), dict(s=None)):
+            refused(fn, good, **bad)
+    refused("a3d_field_head_fwd", fwd, lo=None)  # lo and scale come together
+    refused("a3d_field_head_fwd", fwd, scale=None)
+    refused("a3d_field_head_fwd", fwd, out=None)
+    refused("a3d_field_head_fwd", fwd, act=0, s=None)  # the map alone still writes s
+    for key in ("g_out", "scratch", "g_h", "g_W"):
+        refused("a3d_field_head_bwd", bwd, **{key: None})
+    refused("a3d_field_head_bwd", bwd, g_h=FAKE + 4)
+    refused("a3d_field_head_bwd", bwd, scratch=FAKE + 8)
+    scratch = lib.a3d_field_head_scratch_bytes
+    assert scratch(1, 1) == 1024 and scratch(512, 16) == 16384 and scratch(513, 16) == 2 * 16384 and scratch(204800, 9) == 400 * 9 * 1024
+    for sizes in ((0, 3), (-1, 3), (1 << 31, 3), (5, 0), (5, 17)):
+        assert scratch(*sizes) == 0, sizes
+
+
+def test_ops_raise_on_cpu_tensors_and_on_wrong_shapes():
+    L = _L()
+    ops = importlib.import_module("3danimals_amd.ops")
+    h, w = torch.zeros(5, 256), torch.zeros(3, 256)
+    with pytest.raises(L.A3DError, match="field_head_fwd"):
+        ops.field_head_fwd(h, w)
+    with pytest.raises(L.A3DError, match="field_head_bwd"):
+        ops.field_head_bwd(torch.zeros(5, 3), None, h, w)
+    assert not any(name in L.SIGNATURES for name in L.FIELDS_SIGNATURES)
+
+
+@pytest.mark.parametrize("act,with_map", R.MODES)
+def test_the_float64_statements_are_what_autograd_gives(act, with_map):
+    inp = R.make_inputs(37, 9, with_map, seed=1)
+    z = torch.randn(37, 256, generator=torch.Generator().manual_seed(2)).double().requires_grad_(True)
+    w = inp["w"].double().requires_grad_(True)
+    h = torch.relu(z)
+    s = h @ w.t()
+    if act:
+        s = torch.sigmoid(s)
+    out = s * inp["scale"].double() + inp["lo"].double() if with_map else s
+    g_z, g_w = torch.autograd.grad(out, (z, w), inp["g_out"].double())
+    s_ref, out_ref = R.head_fwd_ref(h.detach(), inp["w"], inp["lo"], inp["scale"], act)
+    assert torch.allclose(s_ref, s.detach(), rtol=1e-13, atol=1e-14) and torch.allclose(out_ref, out.detach(), rtol=1e-13, atol=1e-14)
+    g_h_ref, g_w_ref = R.head_bwd_ref(inp["g_out"], s_ref, h.detach(), inp["w"], inp["scale"], act)
+    assert torch.allclose(g_h_ref, g_z, rtol=1e-12, atol=1e-14) and torch.allclose(g_w_ref, g_w, rtol=1e-12, atol=1e-13)
+    assert torch.equal(g_h_ref != 0, (z > 0).detach())  # the ReLU's adjoint is in the statement
+
+
+def test_the_inputs_hold_the_special_values_and_the_mask_rule_is_threshold_backward():
+    for m in R.ROWS:
+        h = R.make_inputs(m, 3, False)["h"]
+        assert R.has_the_special_values(h), m
+        want = torch.ops.aten.threshold_backward(torch.ones_like(h), h, 0) != 0
+        assert torch.equal(want, h > 0) and torch.equal(want, h.view(torch.int32) > 0)  # strictly positive; on the bits: a denormal counts
+        assert want[0, 2] and not want[0, 0] and not want[0, 1] and not want[0, 3]
+
+
+def test_noise_floor_of_the_float32_cpu_evaluation():
+    floor = R.noise_floor()
+    print({k: round(v, 4) for k, v in floor.items()})
+    assert set(floor) == {(name, m) for name in R.QUANTITIES for m in R.ROWS}
+    for (name, m), v in floor.items():
+        # a float32 evaluation is off by a fraction of eps32 (sum |terms| + |value|) and, with at most 4099 terms, by far less than their
+        # count -- but for the denormal product that is a whole g_w entry when there is one row (fieldhead_ref.noise_floor)
+        assert math.isfinite(v) and 0.01 < v and (v < 64.0 or (name, m) == ("g_w", 1)), (name, m, v)
+    floor = {name: floor[name, 33] for name in R.QUANTITIES}
+    # the statistic bites: one ulp of a sum whose terms cancel is many eps of it, a wrong mask is unbounded
+    inp = R.make_inputs(33, 9, True)
+    good = R.float32_cpu(inp, 1)
+    off = dict(good, g_h=good["g_h"] + 1e-3 * (inp["h"] > 0))
+    assert R.statistics(off, inp, 1)["g_h"] > 100 * R.MARGIN * floor["g_h"]
+    leaky = dict(good, g_h=good["g_h"] + 1e-3 * (inp["h"] <= 0))
+    assert R.statistics(leaky, inp, 1)["g_h"] > 100 * R.MARGIN * floor["g_h"]
+
+
+def test_which_networks_take_the_fused_output_stage():
+    hostnets = importlib.import_module("3danimals_amd.hostnets")
+    mm = lambda c: torch.tensor([[0.0, 1.0]] * c)
+
+    def head(net):
+        layers = list(net.mlp.network)
+        i = 0
+        while i + 1 < len(layers) and isinstance(layers[i], torch.nn.Linear) and isinstance(layers[i + 1], torch.nn.ReLU):
+            i += 2
+        return net._fused_head(layers[i:])
+
+    assert hostnets.USE_FIELD_HEAD is True
+    w, lo, scale, act = head(hostnets.CoordMLP(3, 9, 5, activation="sigmoid", min_max=mm(9)))
+    assert tuple(w.shape) == (9, 256) and act == 1 and torch.equal(lo, torch.zeros(9)) and torch.equal(scale, torch.ones(9))
+    w, lo, scale, act = head(hostnets.CoordMLP(3, 3, 5))
+    assert tuple(w.shape) == (3, 256) and act == 0 and lo is None and scale is None
+    assert head(hostnets.CoordMLP(3, 16, 5, activation="sigmoid", extra_feat_dim=256))[3] == 1
+    assert head(hostnets.CoordMLP(3, 3, 5, activation="tanh")) is None
+    assert head(hostnets.CoordMLP(3, 3, 5, activation="relu")) is None
+    assert head(hostnets.CoordMLP(3, 17, 5)) is None  # too wide
+    assert head(hostnets.CoordMLP(3, 3, 5, nf=128)) is None
+    assert head(hostnets.CoordMLP(3, 3, 5, dropout=0.1)) is None  # the Dropout layers end the Linear/ReLU pairs early
+    biased = hostnets.CoordMLP(3, 3, 5)
+    biased.mlp.network[-1] = torch.nn.Linear(256, 3, bias=True)
+    assert head(biased) is None
+    hostnets.USE_FIELD_HEAD = False
+    try:
+        assert head(hostnets.CoordMLP(3, 3, 5)) is None
+    finally:
+        hostnets.USE_FIELD_HEAD = True
+    # a CPU or short list never reaches the stage: the stack it belongs to is not taken
+    net = hostnets.CoordMLP(3, 1, 5)
+    assert not net._stack_ok(torch.zeros(70000, 3), False)
+    with torch.no_grad():
+        assert not net._stack_ok(torch.zeros(70000, 3), False)
