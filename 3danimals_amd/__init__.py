@@ -13,7 +13,7 @@ reference tree).  There is NO CPU fallback: every compute
 entry point raises if ``liba3d_hip.so`` is missing or the tensors are not on a
 HIP device.
 """
-from . import synthetic, tetgrid  # noqa: F401  (pure numpy/torch helpers; no native code needed)
+from . import evaluation, synthetic, tetgrid  # noqa: F401  (pure numpy/torch helpers; evaluation loads the native code at its first call on CUDA tensors)
 
-__all__ = ["synthetic", "tetgrid"]
+__all__ = ["evaluation", "synthetic", "tetgrid"]
 __version__ = "0.6.0"  # round 6 (C ABI: a3d_version() = 404)

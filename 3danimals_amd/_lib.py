@@ -1,4 +1,4 @@
-"""ctypes binding of liba3d_hip.so (include/a3d.h, include/a3d_bsdf.h, include/a3d_deriv.h, include/a3d_tangent.h, include/a3d_reg.h, include/a3d_envshade.h, include/a3d_sdfreg.h, include/a3d_edt.h, include/a3d_fields.h).  No fallback: if the library is missing we say so and stop."""
+"""ctypes binding of liba3d_hip.so (include/a3d.h, include/a3d_bsdf.h, include/a3d_deriv.h, include/a3d_tangent.h, include/a3d_reg.h, include/a3d_envshade.h, include/a3d_sdfreg.h, include/a3d_edt.h, include/a3d_fields.h, include/a3d_eval.h).  No fallback: if the library is missing we say so and stop."""
 from __future__ import annotations
 
 import ctypes
@@ -296,6 +296,17 @@ FIELD_HEAD_MAX_C = 16  # A3D_FIELD_HEAD_MAX_C
 FIELD_HEAD_WG_ROWS = 512  # A3D_FIELD_HEAD_WG_ROWS
 FIELD_HEAD_ACT_NONE, FIELD_HEAD_ACT_SIGMOID = 0, 1  # A3D_FIELD_HEAD_ACT_*
 
+# the entry points of include/a3d_eval.h (same library, same a3d_version(); tests/test_keypoints_cpu.py checks this table against that header)
+EVAL_SIGNATURES = {
+    "a3d_vertex_visibility_fwd": (_c_int, [_p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _p]),
+    "a3d_nearest_visible_vertex_scratch_bytes": (_c_size_t, [_c_int, _c_int]),
+    "a3d_nearest_visible_vertex_slab": (_c_int, [_c_int, _c_int]),
+    "a3d_nearest_visible_vertex_fwd": (_c_int, [_p, _p, _p, _c_int, _c_int, _c_int, _p, _p, _p]),
+}
+NVV_THREADS = 256  # A3D_NVV_THREADS
+NVV_MAX_TRIPS = 32  # A3D_NVV_MAX_TRIPS
+NVV_KEYPOINT_TILE = 16  # A3D_NVV_KEYPOINT_TILE
+
 ABI_VERSION = 404  # a3d_version() of the library these signatures belong to (include/a3d.h)
 _lib = None
 
@@ -314,7 +325,7 @@ def lib():
                 "(or __graft_entry__.build()).  There is no CPU fallback for the HIP hot path."
             )
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(BSDF_SIGNATURES.items()) + list(DERIV_SIGNATURES.items()) + list(TANGENT_SIGNATURES.items()) + list(REG_SIGNATURES.items()) + list(ENVSHADE_SIGNATURES.items()) + list(SDFREG_SIGNATURES.items()) + list(EDT_SIGNATURES.items()) + list(FIELDS_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(BSDF_SIGNATURES.items()) + list(DERIV_SIGNATURES.items()) + list(TANGENT_SIGNATURES.items()) + list(REG_SIGNATURES.items()) + list(ENVSHADE_SIGNATURES.items()) + list(SDFREG_SIGNATURES.items()) + list(EDT_SIGNATURES.items()) + list(FIELDS_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()):
             fn = getattr(handle, name)  # AttributeError here == ABI drift
             fn.restype, fn.argtypes = res, args
         if handle.a3d_version() != ABI_VERSION:  # same symbols, other argument lists: a stale build must not be called

@@ -3,7 +3,7 @@
     python 3danimals_amd/csrc/build.py [--force] [--profile]
 
 One object per .hip file, linked into 3danimals_amd/lib/liba3d_hip.so (in-tree, git-ignored, travels to the
-GPU box with the snapshot).  raster/dmtet/antialias/normals (and shade, embed, xfm, texture, envlight, bsdf, deriv, tangent, regularizer, envshade, sdfreg, edt, fieldhead) are compiled with -ffp-contract=off: their arithmetic is
+GPU box with the snapshot).  raster/dmtet/antialias/normals (and shade, embed, xfm, texture, envlight, bsdf, deriv, tangent, regularizer, envshade, sdfreg, edt, fieldhead, keypoints) are compiled with -ffp-contract=off: their arithmetic is
 specified operation by operation (oracle/raster_ref.c, reference dmtet.py:124-131, mesh.py:276-304).
 """
 import os
@@ -45,6 +45,7 @@ SOURCES = {
     "sdfreg.hip": ["-ffp-contract=off"],
     "edt.hip": ["-ffp-contract=off"],
     "fieldhead.hip": ["-ffp-contract=off"],
+    "keypoints.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wall",
           "-Wno-unused-function"]
@@ -74,7 +75,7 @@ def build(force=False, verbose=True, profile=False):
     hipcc = _hipcc()
     # every header of csrc/ (a kernel's object is stale when ANY of them is newer: a header left out of a hand-kept list once kept a
     # stale interp.o in the library), the public header and this script
-    headers = sorted(os.path.join(HERE, f) for f in os.listdir(HERE) if f.endswith(".h")) + [os.path.join(os.path.dirname(PKG), "include", h) for h in ("a3d.h", "a3d_bsdf.h", "a3d_deriv.h", "a3d_tangent.h", "a3d_reg.h", "a3d_envshade.h", "a3d_sdfreg.h", "a3d_edt.h", "a3d_fields.h")] + [os.path.abspath(__file__)]
+    headers = sorted(os.path.join(HERE, f) for f in os.listdir(HERE) if f.endswith(".h")) + [os.path.join(os.path.dirname(PKG), "include", h) for h in ("a3d.h", "a3d_bsdf.h", "a3d_deriv.h", "a3d_tangent.h", "a3d_reg.h", "a3d_envshade.h", "a3d_sdfreg.h", "a3d_edt.h", "a3d_fields.h", "a3d_eval.h")] + [os.path.abspath(__file__)]
     jobs = []
     objs = []
     for src, extra in SOURCES.items():

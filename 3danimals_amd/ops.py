@@ -3281,6 +3281,56 @@ def distance_transform(src, scale=1.0, squared=False, return_indices=False, thre
     return (out, idx) if return_indices else out
 
 
+# ---------------------------------------------------------------------------------------------- keypoint-transfer evaluation (include/a3d_eval.h)
+def vertex_visibility(rast, tri, num_vertices):
+    """rast [B,H,W,4] (channel 3: triangle id + 1, 0 = empty), tri [F,3] -> float32 [B, num_vertices]: 1 where the vertex is a corner of
+    a triangle that owns at least one pixel of the image, else 0 (the reference's visualize_results.py:238-246 without its per-image
+    mask compaction, sort and host synchronisation).  csrc/keypoints.hip: one thread per pixel, plain stores of 1, the same bits on
+    every run.  No autograd node: the result never requires grad.  A raster buffer from rasterize(defer_resolve=True) is resolved
+    first.  An id above F or a triangle corner outside [0, num_vertices) is skipped on the device and reported at the next host
+    read-back of the path (_lib.defer_check)."""
+    if not torch.is_tensor(rast) or rast.dim() != 4 or rast.shape[3] != 4 or not rast.is_floating_point():
+        raise ValueError(f"vertex_visibility: expected a float rast [B,H,W,4], got {getattr(rast, 'dtype', type(rast))} {list(getattr(rast, 'shape', []))}")
+    if not torch.is_tensor(tri) or tri.dtype not in (torch.int32, torch.int64) or not (tri.dim() == 2 or (tri.dim() == 3 and tri.shape[0] == 1)) or tri.shape[-1] != 3:
+        raise ValueError(f"vertex_visibility: expected int32 / int64 triangles [F,3], got {getattr(tri, 'dtype', type(tri))} {list(getattr(tri, 'shape', []))}")
+    B, H, W = (int(v) for v in rast.shape[:3])
+    V, F = int(num_vertices), int(tri.shape[-2])
+    if min(B, H, W, V, F) < 1 or B * H * W >= 1 << 31 or B * V >= 1 << 31:
+        raise ValueError(f"vertex_visibility: rast {list(rast.shape)}, {F} triangles, {V} vertices: every count must be >= 1, B * H * W and B * V < 2^31")
+    require_device(rast, tri, what="vertex_visibility")
+    ensure_resolved(rast)
+    rast = f32c(rast.detach())
+    tri32 = tri_int32(tri)
+    vis = torch.empty((B, V), dtype=torch.float32, device=rast.device)
+    ok = torch.empty(1, dtype=torch.int32, device=rast.device)
+    call("a3d_vertex_visibility_fwd", ptr(rast), ptr(tri32), B, H, W, F, V, ptr(vis), ptr(ok), stream())
+    _lib.defer_check(ok[0], "vertex_visibility: a triangle id above F in rast, or a triangle corner outside [0, num_vertices) (skipped)")
+    return vis
+
+
+def nearest_visible_vertex(uv, visibility, keypoints):
+    """uv [N,V,2], visibility [N,V] (0 = invisible), keypoints [N,K,2] in the same frame -> int64 [N,K]: per keypoint the index of the
+    visible vertex with the smallest float32 d2 = dx * dx + dy * dy (dx = x - kp.x, dy = y - kp.y, each one operation, no FMA), an
+    invisible vertex read as (+inf, +inf) like the reference's source_verts[visibility == 0] = np.inf (evaluate.py:464); the lowest
+    index among equals, a NaN d2 below every number, 0 when nothing is visible: np.argmin's rules on the reference's matrix, without
+    the [N,K,V] matrix.  csrc/keypoints.hip; the same bits on every run.  No autograd node: the result never requires grad."""
+    for name, t, last in (("uv", uv, 2), ("visibility", visibility, None), ("keypoints", keypoints, 2)):
+        if not torch.is_tensor(t) or not t.is_floating_point() or t.dim() != (2 if last is None else 3) or (last is not None and t.shape[2] != last):
+            raise ValueError(f"nearest_visible_vertex: expected float {name} {'[N,V]' if last is None else '[N,*,2]'}, got "
+                             f"{getattr(t, 'dtype', type(t))} {list(getattr(t, 'shape', []))}")
+    N, V, K = int(uv.shape[0]), int(uv.shape[1]), int(keypoints.shape[1])
+    if tuple(visibility.shape) != (N, V) or keypoints.shape[0] != N:
+        raise ValueError(f"nearest_visible_vertex: uv {list(uv.shape)}, visibility {list(visibility.shape)} and keypoints {list(keypoints.shape)} do not belong together")
+    if min(N, V, K) < 1 or V > 1 << 30 or N * V >= 1 << 31 or N * K >= 1 << 31:
+        raise ValueError(f"nearest_visible_vertex: N = {N}, V = {V}, K = {K}: every count must be >= 1, V <= 2^30, N * V and N * K < 2^31")
+    require_device(uv, visibility, keypoints, what="nearest_visible_vertex")
+    uv, visibility, keypoints = f32c(uv.detach()), f32c(visibility.detach()), f32c(keypoints.detach())
+    keys = torch.empty((N, K), dtype=torch.int64, device=uv.device)
+    idx = torch.empty((N, K), dtype=torch.int32, device=uv.device)
+    call("a3d_nearest_visible_vertex_fwd", ptr(uv), ptr(visibility), ptr(keypoints), N, V, K, ptr(keys), ptr(idx), stream())
+    return idx.long()
+
+
 # ---------------------------------------------------------------------------------------------- mixed precision
 def _amp_wrap_functions():
     """Every autograd.Function of this module runs its forward with autocast OFF on float32 copies of half-precision inputs, and its
