@@ -1,8 +1,10 @@
-"""ctypes binding of liba3d_hip.so (include/a3d.h, include/a3d_bsdf.h, include/a3d_deriv.h, include/a3d_tangent.h, include/a3d_reg.h, include/a3d_envshade.h, include/a3d_sdfreg.h, include/a3d_edt.h, include/a3d_fields.h, include/a3d_eval.h).  No fallback: if the library is missing we say so and stop."""
+"""ctypes binding of liba3d_hip.so: SURFACES registers each public header of include/ with its entry points, struct mirrors and
+constants.  No fallback: if the library is missing we say so and stop."""
 from __future__ import annotations
 
 import ctypes
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -12,117 +14,14 @@ LIB_PATH = os.environ.get("A3D_LIB") or os.path.join(_HERE, "lib", "liba3d_hip.s
 
 _c_int, _c_float, _c_size_t, _p = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_void_p
 
-# name -> (restype, argtypes); must list every symbol declared in include/a3d.h (tests/test_host_cpu.py::test_library_exports_every_declared_symbol checks)
-SIGNATURES = {
-    "a3d_version": (_c_int, []),
-    "a3d_last_error": (ctypes.c_char_p, []),
-    "a3d_bw_probe_fill": (_c_int, [_p, ctypes.c_int64, _p]),
-    "a3d_bw_probe_read": (_c_int, [_p, ctypes.c_int64, _p, _p]),
-    "a3d_dmtet_scratch_bytes": (_c_size_t, [_c_int, _c_int]),
-    "a3d_dmtet_count": (_c_int, [_p, _p, _p, _c_int, _c_int, _p, _p, _p, _c_int, _c_int, _p, _p, _c_int, _p, _c_int, _p]),
-    "a3d_dmtet_count_ordered": (_c_int, [_p, _c_int, _c_int, _c_int, _p, _p, _p, _p, _c_int, _p, _c_int, _p]),
-    "a3d_dmtet_word_group_slots": (_c_int, []),
-    "a3d_dmtet_word_group_bits": (_c_int, []),
-    "a3d_dmtet_block_items": (_c_int, []),
-    "a3d_dmtet_vertex_scratch_bytes": (_c_size_t, [_c_int]),
-    "a3d_dmtet_gather_rows": (_c_int, [_p, _p, ctypes.c_int64, ctypes.c_int64, _c_int, _p, _p]),
-    "a3d_dmtet_emit": (_c_int, [_p, _p, _p, _p, _c_int, _c_int, _p, _c_int, _c_int, _c_int, _p, _p, _p, _p, _p, _p]),
-    "a3d_dmtet_emit_sparse": (_c_int, [_p, _p, _p, _p, _c_int, _c_int, _p, _c_int, _c_int, _c_int, _p, _p, _p, _p, _p, _p]),
-    "a3d_dmtet_bwd": (_c_int, [_p, _p, _p, _p, _p, _c_int, _c_int, _p, _p, _c_int, _p]),
-    "a3d_skin_fwd": (_c_int, [_p, _c_int, _p, _c_int, _p, _c_int, _c_int, _c_int, _c_float, _p, _p, _p, _p]),
-    "a3d_skin_bwd": (_c_int, [_p, _p, _c_int, _p, _c_int, _p, _c_int, _c_int, _c_int, _c_float, _p, _p, _c_int, _p]),
-    "a3d_bone_transforms_fwd": (_c_int, [_p, _c_int, _p, _p, _c_int, _c_int, _c_int, _p, _p]),
-    "a3d_bone_transforms_bwd": (_c_int, [_p, _p, _c_int, _p, _p, _c_int, _c_int, _c_int, _p, _p]),
-    "a3d_estimate_bones": (_c_int, [_p, _p]),
-    "a3d_skin_pose_max_bones": (_c_int, []),
-    "a3d_skin_pose_products_floats": (_c_size_t, [_c_int, _c_int]),
-    "a3d_skin_pose_fwd": (_c_int, [_p, _c_int, _p, _c_int, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_float, _p, _p, _p, _p, _p]),
-    "a3d_skin_pose_bwd": (_c_int, [_p, _p, _c_int, _p, _c_int, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_float, _p, _p, _p, _c_int, _p]),
-    "a3d_normals_adjacency": (_c_int, [_p, _c_int, _c_int, _p, _p, _p, _p]),
-    "a3d_normals_fwd": (_c_int, [_p, _p, _p, _p, _c_int, _c_int, _c_int, _p, _p, _c_int, _p]),
-    "a3d_normals_fwd_pair": (_c_int, [_p, _c_int, _p, _c_int, _p, _p, _p, _c_int, _c_int, _p, _p, _p, _p, _c_int, _p]),
-    "a3d_normals_bwd": (_c_int, [_p, _c_int, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _p, _p, _c_int, _p, _p]),
-    "a3d_shade_fwd": (_c_int, [_p, _p, _c_int, _p, _p, _c_int, ctypes.c_int64, _c_int, _p, _p, _p, _p, _c_int, _p]),
-    "a3d_shade_bwd": (_c_int, [_p, _p, _p, _p, _p, _c_int, _p, _c_int, _p, _c_int, ctypes.c_int64, _c_int, _p, _p, _p, _c_int, _p]),
-    "a3d_shade_bwd_rows": (_c_int, [_p, _p, _p, _p, _p, ctypes.c_int64, _p, _c_int, ctypes.c_int64, _c_int, _p, _p, _c_int, ctypes.c_int64, _p]),
-    "a3d_xfm_points_fwd": (_c_int, [_p, _c_int, _p, _c_int, _c_int, _c_int, _p, _p, _p]),
-    "a3d_flow_delta_fwd": (_c_int, [_p, _c_int, _c_int, _c_int, _p, _p]),
-    "a3d_flow_delta_bwd": (_c_int, [_p, _c_int, _p, _c_int, _c_int, _c_int, _p, _p]),
-    "a3d_xfm_points_bwd": (_c_int, [_p, _c_int, _p, _c_int, _p, _c_int, _c_int, _c_int, _p, _p, _c_int, _p, _c_int, _p, _c_int, _p, _c_int, _p]),
-    "a3d_cover_scratch_bytes": (_c_size_t, [_c_int, _c_int, _c_int]),
-    "a3d_cover_blocks": (_c_int, [_c_int, _c_int, _c_int]),
-    "a3d_cover_groups": (_c_int, [_c_int, _c_int, _c_int]),
-    "a3d_cover_group_stride": (_c_int, []),
-    "a3d_cover_count": (_c_int, [_p, _c_int, _c_int, _c_int, _c_int, _p, _p]),
-    "a3d_cover_emit": (_c_int, [_p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p]),
-    "a3d_rast_scratch_bytes": (_c_size_t, [_c_int, _c_int, _c_int]),
-    "a3d_rast_bins_bytes": (_c_size_t, [_c_int, _c_int, _c_int, _c_int]),
-    "a3d_rast_resolve": (_c_int, [_p, _c_int, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p]),
-    "a3d_rast_resolve_gbuffer_fwd": (_c_int, [_p, _c_int, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, ctypes.c_int64, _p, _p, _p, _p, _p,
-                                              _c_int, _p, _p, _c_int, _p, _p, _p, _p]),
-    "a3d_rast_fwd": (_c_int, [_p, _c_int, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _c_int, _p, _p]),
-    "a3d_dispatch_order_probe": (_c_int, [_c_int, _c_int, _p, _p]),
-    "a3d_rast_bwd": (_c_int, [_p, _p, _p, _c_int, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p]),
-    "a3d_interp_fwd": (_c_int, [_p, _c_int, _c_int, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p]),
-    "a3d_interp_bwd": (_c_int, [_p, _p, _c_int, _c_int, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _p]),
-    "a3d_mesh_topology": (_c_int, [_p, _c_int, _c_int, _p, _p, _p, _p, _p, _c_int, _p]),
-    "a3d_mesh_topology_finalize_max_vertices": (_c_int, []),
-    "a3d_mesh_topology_finalize": (_c_int, [_p, _c_int, _c_int, _p, _p, _p, _p, _c_int, _p]),
-    "a3d_gbuffer_fwd": (_c_int, [_p, _p, _p, ctypes.c_int64, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _c_int, _p, _p, _p, _p]),
-    "a3d_cover_gbuffer_fwd": (_c_int, [_p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, ctypes.c_int64, _p, _p, _p, _p, _p, _c_int, _p, _p, _c_int,
-                                       _p, _p, _p, _p]),
-    "a3d_gbuffer_bwd": (_c_int, [_p, _p, _p, _p, ctypes.c_int64, _p, _p, _p, _c_int, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _c_int,
-                                 _c_int, _p, _c_int, _p, _p, _p]),
-    "a3d_gbuffer_prior_grad": (_c_int, [_p, _c_int, _c_int, _p, _p]),
-    "a3d_gemm_nn_relumask": (_c_int, [_p, _p, _p, ctypes.c_int64, _c_int, _c_int, _p, _p]),
-    "a3d_harmonic_embed_fwd": (_c_int, [_p, _p, _c_int, _c_int, _c_int, ctypes.c_int64, _p, _p]),
-    "a3d_harmonic_embed_bwd": (_c_int, [_p, _p, _p, _c_int, _c_int, _c_int, ctypes.c_int64, _p, _p]),
-    "a3d_recon_losses_scratch_bytes": (_c_size_t, [_c_int, _c_int, _c_int]),
-    "a3d_recon_losses_mask_bytes": (_c_size_t, [_c_int, _c_int, _c_int]),
-    "a3d_recon_losses_columns": (_c_int, []),
-    "a3d_recon_losses_fwd": (_c_int, [_p, _p, _c_int, _c_int, _p, _p, _p, _p, _p, ctypes.c_int64, _p, _c_int, _c_int, _c_int, _p, _p, _p, _p]),
-    "a3d_recon_losses_bwd": (_c_int, [_p, _p, _p, _c_int, _c_int, _c_int, _p, _p, _p, _p, _p, ctypes.c_int64, _p, _c_int, _c_int, _c_int, _p, _p, _p, _p]),
-    "a3d_flow_loss_scratch_bytes": (_c_size_t, [_c_int, _c_int, _c_int, _c_int]),
-    "a3d_flow_loss_fwd": (_c_int, [_p, _c_int, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p]),
-    "a3d_flow_loss_bwd": (_c_int, [_p, _p, _p, _c_int, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p]),
-    "a3d_rows_segsum": (_c_int, [_p, _p, ctypes.c_int64, _c_int, _c_int, _p, _p]),
-    "a3d_rows_add_relu_fwd": (_c_int, [_p, _p, _p, ctypes.c_int64, _c_int, _c_int, _p]),
-    "a3d_rows_add_relu_bwd": (_c_int, [_p, _p, _p, ctypes.c_int64, _c_int, _c_int, _p, _p, _p]),
-    "a3d_aa_hash_bytes": (_c_size_t, [_c_int]),
-    "a3d_aa_shards": (_c_int, []),
-    "a3d_aa_capacity": (_c_int, [_c_int, _c_int, _c_int]),
-    "a3d_aa_topology": (_c_int, [_p, _c_int, _c_int, _p, _p, _p]),
-    "a3d_aa_topology_from_lists": (_c_int, [_p, _c_int, _p, _p, _p, _c_int, _p]),
-    "a3d_aa_analyze": (_c_int, [_p, _p, _c_int, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _c_int, _p, _c_int, _p, _p, _c_int, _p]),
-    "a3d_aa_fwd": (_c_int, [_p, _c_int, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p]),
-    "a3d_aa_bwd": (_c_int, [_p, _p, _c_int, _p, _p, _c_int, _p, _c_int, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _p]),
-    "a3d_composite_aa_fwd": (_c_int, [_p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p]),
-    "a3d_mask_aa_fwd": (_c_int, [_p, _c_int, _p, _c_int, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p]),
-    "a3d_mask_aa_bwd": (_c_int, [_p, _p, _c_int, _p, _c_int, _p, _p, _c_int, _p, _c_int, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _c_int, _p]),
-    "a3d_composite_aa_bwd": (_c_int, [_p, _p, _p, ctypes.c_int64, _p, _p, _p, _c_int, _p, _c_int, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _p]),
-    "a3d_texture_fwd": (_c_int, [_p, _p, _p, _p, _c_int, _c_int, _c_int, _p, _p]),
-    "a3d_texture_bwd": (_c_int, [_p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _p, _p, _p, _p]),
-    "a3d_texture_mip_fwd": (_c_int, [_p, _p]),
-    "a3d_texture_mip_bwd": (_c_int, [_p, _p]),
-    "a3d_cubemap_diffuse_fwd": (_c_int, [_p, _p]),
-    "a3d_cubemap_diffuse_bwd": (_c_int, [_p, _p]),
-    "a3d_cubemap_specular_bounds": (_c_int, [_p, _p]),
-    "a3d_cubemap_specular_fwd": (_c_int, [_p, _p]),
-    "a3d_cubemap_specular_bwd": (_c_int, [_p, _p]),
-}
 
-
-
+# ---- ctypes mirrors of the headers' structs (registered by their C names in SURFACES below)
 class DmtetOrder(ctypes.Structure):
-    """a3d_dmtet_order of include/a3d.h (field for field; tests/test_host_cpu.py compares the two)."""
-
     _fields_ = [("size", ctypes.c_uint32), ("group_slots", ctypes.c_int32), ("vertex_of_rank", _p), ("edges_ranked", _p), ("edge_of_row", _p),
                 ("tets_ranked", _p), ("tet_of_row", _p), ("edge_groups", _p), ("tet_groups", _p)]
 
 
 class RastOpts(ctypes.Structure):
-    """a3d_rast_opts of include/a3d.h."""
-
     _fields_ = [("size", ctypes.c_uint32), ("lists_stride", ctypes.c_int32), ("prev_rast", _p), ("cover_scratch", _p), ("aa_screen", _p),
                 ("aa_count", _p), ("topo_off", _p), ("topo_adj", _p), ("topo_opp", _p), ("normals_v_a", _p), ("normals_v_b", _p),
                 ("normals_off", _p), ("normals_adj", _p), ("normals_acc_a", _p), ("normals_a", _p), ("normals_acc_b", _p), ("normals_b", _p),
@@ -131,52 +30,38 @@ class RastOpts(ctypes.Structure):
 
 
 class AaRide(ctypes.Structure):
-    """a3d_aa_ride of include/a3d.h."""
-
     _fields_ = [("size", ctypes.c_uint32), ("clip_batch", ctypes.c_int32), ("rast", _p), ("screen", _p), ("tri", _p), ("opp", _p), ("off", _p),
                 ("adj", _p), ("V", ctypes.c_int32), ("F", ctypes.c_int32), ("lists_stride", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 class CaBuffer(ctypes.Structure):
-    """a3d_ca_buffer of include/a3d.h."""
-
     _fields_ = [("size", ctypes.c_uint32), ("C", ctypes.c_int32), ("vals", _p), ("bg", _p), ("out", _p), ("g_out", _p), ("g_vals", _p),
                 ("bg_batch", ctypes.c_int32), ("reserved", ctypes.c_int32), ("bg_channels", ctypes.c_int32), ("g_stride", ctypes.c_int32),
                 ("g_channels", ctypes.c_int32), ("out_channels", ctypes.c_int32), ("vals_rows", ctypes.c_int64)]
 
 
 class CaShade(ctypes.Structure):
-    """a3d_ca_shade of include/a3d.h."""
-
     _fields_ = [("size", ctypes.c_uint32), ("kd_stride", ctypes.c_int32), ("gb", _p), ("par", _p), ("kd", _p), ("clear", _p),
                 ("n_clear", ctypes.c_int32), ("two_sided", ctypes.c_int32), ("params", _p), ("shaded_out", _p)]
 
 
 class ShadeParams(ctypes.Structure):
-    """a3d_shade_params of include/a3d.h."""
-
     _fields_ = [("size", ctypes.c_uint32), ("rot_row_stride", ctypes.c_int32), ("rot", _p), ("view", _p), ("light", _p),
                 ("rot_image_stride", ctypes.c_int64), ("view_image_stride", ctypes.c_int64), ("light_image_stride", ctypes.c_int64)]
 
 
 class EstimateBonesArgs(ctypes.Structure):
-    """a3d_estimate_bones_args of include/a3d.h."""
-
     _fields_ = [("size", ctypes.c_uint32), ("N", ctypes.c_int32), ("pos", _p), ("bones", _p), ("nearest", _p), ("ok", _p), ("V", ctypes.c_int32),
                 ("n_body", ctypes.c_int32), ("n_leg", ctypes.c_int32), ("body_mode_y_plus", ctypes.c_int32), ("use_y_threshold", ctypes.c_int32),
                 ("y_threshold", ctypes.c_float), ("attach", ctypes.c_int32 * 4), ("blend", ctypes.c_float * 17), ("ramp", ctypes.c_float * 9), ("workspace", _p)]
 
 
 class GbAux(ctypes.Structure):
-    """a3d_gb_aux of include/a3d.h."""
-
     _fields_ = [("size", ctypes.c_uint32), ("reserved", ctypes.c_int32), ("tex_out", _p), ("img_out", _p), ("rows", ctypes.c_int64),
                 ("pad_to", ctypes.c_int64)]
 
 
 class DmtetEmitOpts(ctypes.Structure):
-    """a3d_dmtet_emit_opts of include/a3d.h."""
-
     _fields_ = [("size", ctypes.c_uint32), ("Nv", ctypes.c_int32), ("vertex_scratch", _p), ("surf_idx", _p), ("g_sdf_to_clear", _p), ("tri32", _p),
                 ("topo_count", _p), ("topo_adj", _p), ("device_counts", _p), ("n_surf", ctypes.c_int32), ("topo_stride", ctypes.c_int32),
                 ("use_block_lists", ctypes.c_int32), ("n_edge_blocks_listed", ctypes.c_int32), ("n_tet_blocks_listed", ctypes.c_int32),
@@ -184,83 +69,23 @@ class DmtetEmitOpts(ctypes.Structure):
 
 
 class TexDesc(ctypes.Structure):
-    """a3d_tex_desc of include/a3d.h."""
-
     _fields_ = [("size", ctypes.c_uint32), ("C", ctypes.c_int32), ("tex_batch", ctypes.c_int32), ("filter", ctypes.c_int32), ("boundary", ctypes.c_int32),
                 ("levels", ctypes.c_int32), ("height", ctypes.c_int32 * 16), ("width", ctypes.c_int32 * 16), ("level", _p * 16), ("grad", _p * 16)]
 
 
 class EnvDesc(ctypes.Structure):
-    """a3d_env_desc of include/a3d.h."""
-
     _fields_ = [("size", ctypes.c_uint32), ("N", ctypes.c_int32), ("roughness", ctypes.c_float), ("costheta_cutoff", ctypes.c_float), ("src", _p),
                 ("dst", _p), ("bounds", _p), ("area", _p)]
 
 
 class BsdfDesc(ctypes.Structure):
-    """a3d_bsdf_desc of include/a3d_bsdf.h (field for field; tests/test_bsdf_cpu.py compares the two)."""
-
     _fields_ = [("size", ctypes.c_uint32), ("op", ctypes.c_int32), ("variant", ctypes.c_int32), ("min_roughness", ctypes.c_float),
                 ("ndim", ctypes.c_int32), ("reserved", ctypes.c_int32), ("shape", ctypes.c_int64 * 4), ("seg", ctypes.c_int64), ("in", _p * 6),
                 ("stride", ctypes.c_int64 * 24), ("cstride", ctypes.c_int64 * 6), ("out", _p), ("scratch", _p), ("g_out", _p),
                 ("g_mode", ctypes.c_int32 * 6), ("seg_div", ctypes.c_int64 * 6), ("g_in", _p * 6), ("g_final", _p * 6)]
 
 
-# the entry points of include/a3d_bsdf.h (same library, same a3d_version(); tests/test_bsdf_cpu.py checks this table against that header)
-BSDF_SIGNATURES = {
-    "a3d_bsdf_rows": (ctypes.c_int64, [_p]),
-    "a3d_bsdf_fwd": (_c_int, [_p, _p]),
-    "a3d_bsdf_bwd": (_c_int, [_p, _p]),
-    "a3d_image_loss_fwd": (_c_int, [_p, _p]),
-    "a3d_image_loss_bwd": (_c_int, [_p, _p]),
-}
-BSDF_TILE = 1024  # A3D_BSDF_TILE
-BSDF_MAX_DIMS = 4  # A3D_BSDF_MAX_DIMS
-
-# the entry points of include/a3d_deriv.h (same library, same a3d_version(); tests/test_deriv_cpu.py checks this table against that header)
-DERIV_SIGNATURES = {
-    "a3d_rast_db_fwd": (_c_int, [_p, _c_int, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p]),
-    "a3d_rast_db_bwd": (_c_int, [_p, _p, _c_int, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p]),
-    "a3d_interp_da_fwd": (_c_int, [_p, _c_int, _c_int, _p, _c_int, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p]),
-    "a3d_interp_da_bwd": (_c_int, [_p, _p, _c_int, _c_int, _p, _c_int, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _p]),
-}
-DERIV_MAX_SELECTED = 64  # A3D_DERIV_MAX_SELECTED
-
-# the entry points of include/a3d_tangent.h (same library, same a3d_version(); tests/test_tangent_cpu.py checks this table against that header)
-TANGENT_SIGNATURES = {
-    "a3d_shading_normal_rows": (ctypes.c_int64, [_p]),
-    "a3d_shading_normal_fwd": (_c_int, [_p, _p]),
-    "a3d_shading_normal_bwd": (_c_int, [_p, _p]),
-    "a3d_tangents_fwd": (_c_int, [_p, _p, ctypes.c_int64, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p]),
-    "a3d_tangents_bwd": (_c_int, [_p, _p, _p, ctypes.c_int64, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p]),
-}
-SHADING_NORMAL_OP = 5  # A3D_SHADING_NORMAL
-
-# the entry points of include/a3d_reg.h (same library, same a3d_version(); tests/test_regularizer_cpu.py checks this table against that header)
-REG_SIGNATURES = {
-    "a3d_edge_topology": (_c_int, [_p, _c_int, _c_int, _p, _p, _c_int, _p, _p, _p]),
-    "a3d_reg_partials": (_c_size_t, [_c_int, _c_int]),
-    "a3d_laplace_fwd": (_c_int, [_p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p]),
-    "a3d_laplace_bwd": (_c_int, [_p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p]),
-    "a3d_normal_consistency_fwd": (_c_int, [_p, _p, _p, _p, _c_int, _c_int, _c_int, _p, _p, _p, _p]),
-    "a3d_normal_consistency_bwd": (_c_int, [_p, _p, _p, _p, _p, _p, _p, _c_int, _p, _c_int, _c_int, _c_int, _p, _p, _p]),
-    "a3d_edge_length_fwd": (_c_int, [_p, _p, _p, _p, _c_int, _c_int, _c_int, _p, _p, _p]),
-    "a3d_edge_length_bwd": (_c_int, [_p, _p, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p]),
-}
-EDGE_REPRESENTATIVE, EDGE_WINNER, EDGE_STAND_IN = 1, 2, 4  # A3D_EDGE_* bits of an edge-table row
-
-# the entry points of include/a3d_envshade.h (same library, same a3d_version(); tests/test_envshade_cpu.py checks this table against that header)
-ENVSHADE_SIGNATURES = {
-    "a3d_env_shade_fwd": (_c_int, [_p, _p]),
-    "a3d_env_shade_bwd": (_c_int, [_p, _p]),
-}
-ENV_SHADE_INPUTS = 5  # A3D_ENV_SHADE_INPUTS: pos, normal, kd, ks, view_pos
-ENV_SHADE_MIN_LEVELS = 3  # the level rule divides by levels - 2
-
-
 class EnvShadeDesc(ctypes.Structure):
-    """a3d_env_shade_desc of include/a3d_envshade.h (field for field; tests/test_envshade_cpu.py compares the two)."""
-
     _fields_ = [("size", ctypes.c_uint32), ("levels", ctypes.c_int32), ("diffuse_size", ctypes.c_int32), ("fg_height", ctypes.c_int32),
                 ("fg_width", ctypes.c_int32), ("specular", ctypes.c_int32), ("mtx_batch", ctypes.c_int32), ("B", ctypes.c_int32),
                 ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("min_roughness", ctypes.c_float), ("max_roughness", ctypes.c_float),
@@ -269,43 +94,195 @@ class EnvShadeDesc(ctypes.Structure):
                 ("g_out", _p), ("g_in", _p * 4)]
 
 
-# the entry points of include/a3d_sdfreg.h (same library, same a3d_version(); tests/test_sdfreg_cpu.py checks this table against that header)
-SDFREG_SIGNATURES = {
-    "a3d_sdf_bce_fwd": (_c_int, [_p, _c_int, _p, _c_int, _p, _p, _p, _p]),
-    "a3d_sdf_bce_bwd": (_c_int, [_p, _p, _c_int, _p, _c_int, _p, _p, _p, _p, _p]),
-}
-SDF_BCE_BLOCK_EDGES = 1024  # A3D_SDF_BCE_BLOCK_EDGES
-SDF_BCE_PARTIAL_WORDS = 3  # A3D_SDF_BCE_PARTIAL_WORDS
+# ---- Python values of the headers' macros (registered by their C names in SURFACES below)
+BSDF_TILE = 1024
+BSDF_MAX_DIMS = 4
+DERIV_MAX_SELECTED = 64
+SHADING_NORMAL_OP = 5
+EDGE_REPRESENTATIVE, EDGE_WINNER, EDGE_STAND_IN = 1, 2, 4  # bits of an edge-table row
+ENV_SHADE_INPUTS = 5  # pos, normal, kd, ks, view_pos
+ENV_SHADE_MIN_LEVELS = 3  # (no macro: the level rule divides by levels - 2)
+SDF_BCE_BLOCK_EDGES = 1024
+SDF_BCE_PARTIAL_WORDS = 3
+EDT_MAX_SIDE = 4096
+EDT_SRC_U8, EDT_SRC_F32 = 0, 1
+FIELD_HEAD_WIDTH = 256
+FIELD_HEAD_MAX_C = 16
+FIELD_HEAD_WG_ROWS = 512
+FIELD_HEAD_ACT_NONE, FIELD_HEAD_ACT_SIGMOID = 0, 1
+NVV_THREADS = 256
+NVV_MAX_TRIPS = 32
+NVV_KEYPOINT_TILE = 16
 
-# the entry points of include/a3d_edt.h (same library, same a3d_version(); tests/test_edt_cpu.py checks this table against that header)
-EDT_SIGNATURES = {
-    "a3d_edt_scratch_bytes": (_c_size_t, [_c_int, _c_int, _c_int]),
-    "a3d_edt_fwd": (_c_int, [_p, _c_int, _c_float, _c_float, _c_int, _c_int, _c_int, ctypes.c_double, _p, _p, _p, _p, _p]),
-}
-EDT_MAX_SIDE = 4096  # A3D_EDT_MAX_SIDE
-EDT_SRC_U8, EDT_SRC_F32 = 0, 1  # A3D_EDT_SRC_*
 
-# the entry points of include/a3d_fields.h (same library, same a3d_version(); tests/test_fieldhead_cpu.py checks this table against that header)
-FIELDS_SIGNATURES = {
-    "a3d_field_head_scratch_bytes": (_c_size_t, [ctypes.c_int64, _c_int]),
-    "a3d_field_head_fwd": (_c_int, [_p, _p, _p, _p, _c_int, ctypes.c_int64, _c_int, _p, _p, _p]),
-    "a3d_field_head_bwd": (_c_int, [_p, _p, _p, _p, _p, _c_int, ctypes.c_int64, _c_int, _p, _p, _p, _p]),
-}
-FIELD_HEAD_WIDTH = 256  # A3D_FIELD_HEAD_WIDTH
-FIELD_HEAD_MAX_C = 16  # A3D_FIELD_HEAD_MAX_C
-FIELD_HEAD_WG_ROWS = 512  # A3D_FIELD_HEAD_WG_ROWS
-FIELD_HEAD_ACT_NONE, FIELD_HEAD_ACT_SIGMOID = 0, 1  # A3D_FIELD_HEAD_ACT_*
+class Surface(NamedTuple):
+    """One public header of the library and everything this module mirrors of it.  tests/test_abi_cpu.py holds every field of every
+    entry to the header; a new entry point is a line in its header's table, a new header one more entry ("Adding an
+    entry point")."""
 
-# the entry points of include/a3d_eval.h (same library, same a3d_version(); tests/test_keypoints_cpu.py checks this table against that header)
-EVAL_SIGNATURES = {
-    "a3d_vertex_visibility_fwd": (_c_int, [_p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _p]),
-    "a3d_nearest_visible_vertex_scratch_bytes": (_c_size_t, [_c_int, _c_int]),
-    "a3d_nearest_visible_vertex_slab": (_c_int, [_c_int, _c_int]),
-    "a3d_nearest_visible_vertex_fwd": (_c_int, [_p, _p, _p, _c_int, _c_int, _c_int, _p, _p, _p]),
-}
-NVV_THREADS = 256  # A3D_NVV_THREADS
-NVV_MAX_TRIPS = 32  # A3D_NVV_MAX_TRIPS
-NVV_KEYPOINT_TILE = 16  # A3D_NVV_KEYPOINT_TILE
+    header: str  # file name under include/
+    signatures: dict  # entry point -> (restype, argtypes)
+    structs: dict  # C struct name -> its ctypes mirror
+    constants: dict  # macro name -> the Python value that mirrors it
+
+
+SURFACES = (
+    Surface("a3d.h", {
+        "a3d_version": (_c_int, []),
+        "a3d_last_error": (ctypes.c_char_p, []),
+        "a3d_bw_probe_fill": (_c_int, [_p, ctypes.c_int64, _p]),
+        "a3d_bw_probe_read": (_c_int, [_p, ctypes.c_int64, _p, _p]),
+        "a3d_dmtet_scratch_bytes": (_c_size_t, [_c_int, _c_int]),
+        "a3d_dmtet_count": (_c_int, [_p, _p, _p, _c_int, _c_int, _p, _p, _p, _c_int, _c_int, _p, _p, _c_int, _p, _c_int, _p]),
+        "a3d_dmtet_count_ordered": (_c_int, [_p, _c_int, _c_int, _c_int, _p, _p, _p, _p, _c_int, _p, _c_int, _p]),
+        "a3d_dmtet_word_group_slots": (_c_int, []),
+        "a3d_dmtet_word_group_bits": (_c_int, []),
+        "a3d_dmtet_block_items": (_c_int, []),
+        "a3d_dmtet_vertex_scratch_bytes": (_c_size_t, [_c_int]),
+        "a3d_dmtet_gather_rows": (_c_int, [_p, _p, ctypes.c_int64, ctypes.c_int64, _c_int, _p, _p]),
+        "a3d_dmtet_emit": (_c_int, [_p, _p, _p, _p, _c_int, _c_int, _p, _c_int, _c_int, _c_int, _p, _p, _p, _p, _p, _p]),
+        "a3d_dmtet_emit_sparse": (_c_int, [_p, _p, _p, _p, _c_int, _c_int, _p, _c_int, _c_int, _c_int, _p, _p, _p, _p, _p, _p]),
+        "a3d_dmtet_bwd": (_c_int, [_p, _p, _p, _p, _p, _c_int, _c_int, _p, _p, _c_int, _p]),
+        "a3d_skin_fwd": (_c_int, [_p, _c_int, _p, _c_int, _p, _c_int, _c_int, _c_int, _c_float, _p, _p, _p, _p]),
+        "a3d_skin_bwd": (_c_int, [_p, _p, _c_int, _p, _c_int, _p, _c_int, _c_int, _c_int, _c_float, _p, _p, _c_int, _p]),
+        "a3d_bone_transforms_fwd": (_c_int, [_p, _c_int, _p, _p, _c_int, _c_int, _c_int, _p, _p]),
+        "a3d_bone_transforms_bwd": (_c_int, [_p, _p, _c_int, _p, _p, _c_int, _c_int, _c_int, _p, _p]),
+        "a3d_estimate_bones": (_c_int, [_p, _p]),
+        "a3d_skin_pose_max_bones": (_c_int, []),
+        "a3d_skin_pose_products_floats": (_c_size_t, [_c_int, _c_int]),
+        "a3d_skin_pose_fwd": (_c_int, [_p, _c_int, _p, _c_int, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_float, _p, _p, _p, _p, _p]),
+        "a3d_skin_pose_bwd": (_c_int, [_p, _p, _c_int, _p, _c_int, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_float, _p, _p, _p, _c_int, _p]),
+        "a3d_normals_adjacency": (_c_int, [_p, _c_int, _c_int, _p, _p, _p, _p]),
+        "a3d_normals_fwd": (_c_int, [_p, _p, _p, _p, _c_int, _c_int, _c_int, _p, _p, _c_int, _p]),
+        "a3d_normals_fwd_pair": (_c_int, [_p, _c_int, _p, _c_int, _p, _p, _p, _c_int, _c_int, _p, _p, _p, _p, _c_int, _p]),
+        "a3d_normals_bwd": (_c_int, [_p, _c_int, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _p, _p, _c_int, _p, _p]),
+        "a3d_shade_fwd": (_c_int, [_p, _p, _c_int, _p, _p, _c_int, ctypes.c_int64, _c_int, _p, _p, _p, _p, _c_int, _p]),
+        "a3d_shade_bwd": (_c_int, [_p, _p, _p, _p, _p, _c_int, _p, _c_int, _p, _c_int, ctypes.c_int64, _c_int, _p, _p, _p, _c_int, _p]),
+        "a3d_shade_bwd_rows": (_c_int, [_p, _p, _p, _p, _p, ctypes.c_int64, _p, _c_int, ctypes.c_int64, _c_int, _p, _p, _c_int, ctypes.c_int64, _p]),
+        "a3d_xfm_points_fwd": (_c_int, [_p, _c_int, _p, _c_int, _c_int, _c_int, _p, _p, _p]),
+        "a3d_flow_delta_fwd": (_c_int, [_p, _c_int, _c_int, _c_int, _p, _p]),
+        "a3d_flow_delta_bwd": (_c_int, [_p, _c_int, _p, _c_int, _c_int, _c_int, _p, _p]),
+        "a3d_xfm_points_bwd": (_c_int, [_p, _c_int, _p, _c_int, _p, _c_int, _c_int, _c_int, _p, _p, _c_int, _p, _c_int, _p, _c_int, _p, _c_int, _p]),
+        "a3d_cover_scratch_bytes": (_c_size_t, [_c_int, _c_int, _c_int]),
+        "a3d_cover_blocks": (_c_int, [_c_int, _c_int, _c_int]),
+        "a3d_cover_groups": (_c_int, [_c_int, _c_int, _c_int]),
+        "a3d_cover_group_stride": (_c_int, []),
+        "a3d_cover_count": (_c_int, [_p, _c_int, _c_int, _c_int, _c_int, _p, _p]),
+        "a3d_cover_emit": (_c_int, [_p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p]),
+        "a3d_rast_scratch_bytes": (_c_size_t, [_c_int, _c_int, _c_int]),
+        "a3d_rast_bins_bytes": (_c_size_t, [_c_int, _c_int, _c_int, _c_int]),
+        "a3d_rast_resolve": (_c_int, [_p, _c_int, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p]),
+        "a3d_rast_resolve_gbuffer_fwd": (_c_int, [_p, _c_int, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, ctypes.c_int64, _p, _p, _p, _p, _p,
+                                                  _c_int, _p, _p, _c_int, _p, _p, _p, _p]),
+        "a3d_rast_fwd": (_c_int, [_p, _c_int, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _c_int, _p, _p]),
+        "a3d_dispatch_order_probe": (_c_int, [_c_int, _c_int, _p, _p]),
+        "a3d_rast_bwd": (_c_int, [_p, _p, _p, _c_int, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p]),
+        "a3d_interp_fwd": (_c_int, [_p, _c_int, _c_int, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p]),
+        "a3d_interp_bwd": (_c_int, [_p, _p, _c_int, _c_int, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _p]),
+        "a3d_mesh_topology": (_c_int, [_p, _c_int, _c_int, _p, _p, _p, _p, _p, _c_int, _p]),
+        "a3d_mesh_topology_finalize_max_vertices": (_c_int, []),
+        "a3d_mesh_topology_finalize": (_c_int, [_p, _c_int, _c_int, _p, _p, _p, _p, _c_int, _p]),
+        "a3d_gbuffer_fwd": (_c_int, [_p, _p, _p, ctypes.c_int64, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _c_int, _p, _p, _p, _p]),
+        "a3d_cover_gbuffer_fwd": (_c_int, [_p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, ctypes.c_int64, _p, _p, _p, _p, _p, _c_int, _p, _p, _c_int,
+                                           _p, _p, _p, _p]),
+        "a3d_gbuffer_bwd": (_c_int, [_p, _p, _p, _p, ctypes.c_int64, _p, _p, _p, _c_int, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _c_int,
+                                     _c_int, _p, _c_int, _p, _p, _p]),
+        "a3d_gbuffer_prior_grad": (_c_int, [_p, _c_int, _c_int, _p, _p]),
+        "a3d_gemm_nn_relumask": (_c_int, [_p, _p, _p, ctypes.c_int64, _c_int, _c_int, _p, _p]),
+        "a3d_harmonic_embed_fwd": (_c_int, [_p, _p, _c_int, _c_int, _c_int, ctypes.c_int64, _p, _p]),
+        "a3d_harmonic_embed_bwd": (_c_int, [_p, _p, _p, _c_int, _c_int, _c_int, ctypes.c_int64, _p, _p]),
+        "a3d_recon_losses_scratch_bytes": (_c_size_t, [_c_int, _c_int, _c_int]),
+        "a3d_recon_losses_mask_bytes": (_c_size_t, [_c_int, _c_int, _c_int]),
+        "a3d_recon_losses_columns": (_c_int, []),
+        "a3d_recon_losses_fwd": (_c_int, [_p, _p, _c_int, _c_int, _p, _p, _p, _p, _p, ctypes.c_int64, _p, _c_int, _c_int, _c_int, _p, _p, _p, _p]),
+        "a3d_recon_losses_bwd": (_c_int, [_p, _p, _p, _c_int, _c_int, _c_int, _p, _p, _p, _p, _p, ctypes.c_int64, _p, _c_int, _c_int, _c_int, _p, _p, _p, _p]),
+        "a3d_flow_loss_scratch_bytes": (_c_size_t, [_c_int, _c_int, _c_int, _c_int]),
+        "a3d_flow_loss_fwd": (_c_int, [_p, _c_int, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p]),
+        "a3d_flow_loss_bwd": (_c_int, [_p, _p, _p, _c_int, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p]),
+        "a3d_rows_segsum": (_c_int, [_p, _p, ctypes.c_int64, _c_int, _c_int, _p, _p]),
+        "a3d_rows_add_relu_fwd": (_c_int, [_p, _p, _p, ctypes.c_int64, _c_int, _c_int, _p]),
+        "a3d_rows_add_relu_bwd": (_c_int, [_p, _p, _p, ctypes.c_int64, _c_int, _c_int, _p, _p, _p]),
+        "a3d_aa_hash_bytes": (_c_size_t, [_c_int]),
+        "a3d_aa_shards": (_c_int, []),
+        "a3d_aa_capacity": (_c_int, [_c_int, _c_int, _c_int]),
+        "a3d_aa_topology": (_c_int, [_p, _c_int, _c_int, _p, _p, _p]),
+        "a3d_aa_topology_from_lists": (_c_int, [_p, _c_int, _p, _p, _p, _c_int, _p]),
+        "a3d_aa_analyze": (_c_int, [_p, _p, _c_int, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _c_int, _p, _c_int, _p, _p, _c_int, _p]),
+        "a3d_aa_fwd": (_c_int, [_p, _c_int, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p]),
+        "a3d_aa_bwd": (_c_int, [_p, _p, _c_int, _p, _p, _c_int, _p, _c_int, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _p]),
+        "a3d_composite_aa_fwd": (_c_int, [_p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p]),
+        "a3d_mask_aa_fwd": (_c_int, [_p, _c_int, _p, _c_int, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p]),
+        "a3d_mask_aa_bwd": (_c_int, [_p, _p, _c_int, _p, _c_int, _p, _p, _c_int, _p, _c_int, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _c_int, _p]),
+        "a3d_composite_aa_bwd": (_c_int, [_p, _p, _p, ctypes.c_int64, _p, _p, _p, _c_int, _p, _c_int, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _p]),
+        "a3d_texture_fwd": (_c_int, [_p, _p, _p, _p, _c_int, _c_int, _c_int, _p, _p]),
+        "a3d_texture_bwd": (_c_int, [_p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _p, _p, _p, _p]),
+        "a3d_texture_mip_fwd": (_c_int, [_p, _p]),
+        "a3d_texture_mip_bwd": (_c_int, [_p, _p]),
+        "a3d_cubemap_diffuse_fwd": (_c_int, [_p, _p]),
+        "a3d_cubemap_diffuse_bwd": (_c_int, [_p, _p]),
+        "a3d_cubemap_specular_bounds": (_c_int, [_p, _p]),
+        "a3d_cubemap_specular_fwd": (_c_int, [_p, _p]),
+        "a3d_cubemap_specular_bwd": (_c_int, [_p, _p]),
+    }, {"a3d_dmtet_order": DmtetOrder, "a3d_dmtet_emit_opts": DmtetEmitOpts, "a3d_estimate_bones_args": EstimateBonesArgs,
+        "a3d_shade_params": ShadeParams, "a3d_rast_opts": RastOpts, "a3d_gb_aux": GbAux, "a3d_aa_ride": AaRide, "a3d_ca_shade": CaShade,
+        "a3d_ca_buffer": CaBuffer, "a3d_tex_desc": TexDesc, "a3d_env_desc": EnvDesc}, {}),
+    Surface("a3d_bsdf.h", {
+        "a3d_bsdf_rows": (ctypes.c_int64, [_p]),
+        "a3d_bsdf_fwd": (_c_int, [_p, _p]),
+        "a3d_bsdf_bwd": (_c_int, [_p, _p]),
+        "a3d_image_loss_fwd": (_c_int, [_p, _p]),
+        "a3d_image_loss_bwd": (_c_int, [_p, _p]),
+    }, {"a3d_bsdf_desc": BsdfDesc}, {"A3D_BSDF_TILE": BSDF_TILE, "A3D_BSDF_MAX_DIMS": BSDF_MAX_DIMS}),
+    Surface("a3d_deriv.h", {
+        "a3d_rast_db_fwd": (_c_int, [_p, _c_int, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p]),
+        "a3d_rast_db_bwd": (_c_int, [_p, _p, _c_int, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p]),
+        "a3d_interp_da_fwd": (_c_int, [_p, _c_int, _c_int, _p, _c_int, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p]),
+        "a3d_interp_da_bwd": (_c_int, [_p, _p, _c_int, _c_int, _p, _c_int, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _p]),
+    }, {}, {"A3D_DERIV_MAX_SELECTED": DERIV_MAX_SELECTED}),
+    Surface("a3d_tangent.h", {
+        "a3d_shading_normal_rows": (ctypes.c_int64, [_p]),
+        "a3d_shading_normal_fwd": (_c_int, [_p, _p]),
+        "a3d_shading_normal_bwd": (_c_int, [_p, _p]),
+        "a3d_tangents_fwd": (_c_int, [_p, _p, ctypes.c_int64, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p]),
+        "a3d_tangents_bwd": (_c_int, [_p, _p, _p, ctypes.c_int64, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p]),
+    }, {}, {"A3D_SHADING_NORMAL": SHADING_NORMAL_OP}),
+    Surface("a3d_reg.h", {
+        "a3d_edge_topology": (_c_int, [_p, _c_int, _c_int, _p, _p, _c_int, _p, _p, _p]),
+        "a3d_reg_partials": (_c_size_t, [_c_int, _c_int]),
+        "a3d_laplace_fwd": (_c_int, [_p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p]),
+        "a3d_laplace_bwd": (_c_int, [_p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p]),
+        "a3d_normal_consistency_fwd": (_c_int, [_p, _p, _p, _p, _c_int, _c_int, _c_int, _p, _p, _p, _p]),
+        "a3d_normal_consistency_bwd": (_c_int, [_p, _p, _p, _p, _p, _p, _p, _c_int, _p, _c_int, _c_int, _c_int, _p, _p, _p]),
+        "a3d_edge_length_fwd": (_c_int, [_p, _p, _p, _p, _c_int, _c_int, _c_int, _p, _p, _p]),
+        "a3d_edge_length_bwd": (_c_int, [_p, _p, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p]),
+    }, {}, {"A3D_EDGE_REPRESENTATIVE": EDGE_REPRESENTATIVE, "A3D_EDGE_WINNER": EDGE_WINNER, "A3D_EDGE_STAND_IN": EDGE_STAND_IN}),
+    Surface("a3d_envshade.h", {
+        "a3d_env_shade_fwd": (_c_int, [_p, _p]),
+        "a3d_env_shade_bwd": (_c_int, [_p, _p]),
+    }, {"a3d_env_shade_desc": EnvShadeDesc}, {"A3D_ENV_SHADE_INPUTS": ENV_SHADE_INPUTS}),
+    Surface("a3d_sdfreg.h", {
+        "a3d_sdf_bce_fwd": (_c_int, [_p, _c_int, _p, _c_int, _p, _p, _p, _p]),
+        "a3d_sdf_bce_bwd": (_c_int, [_p, _p, _c_int, _p, _c_int, _p, _p, _p, _p, _p]),
+    }, {}, {"A3D_SDF_BCE_BLOCK_EDGES": SDF_BCE_BLOCK_EDGES, "A3D_SDF_BCE_PARTIAL_WORDS": SDF_BCE_PARTIAL_WORDS}),
+    Surface("a3d_edt.h", {
+        "a3d_edt_scratch_bytes": (_c_size_t, [_c_int, _c_int, _c_int]),
+        "a3d_edt_fwd": (_c_int, [_p, _c_int, _c_float, _c_float, _c_int, _c_int, _c_int, ctypes.c_double, _p, _p, _p, _p, _p]),
+    }, {}, {"A3D_EDT_MAX_SIDE": EDT_MAX_SIDE, "A3D_EDT_SRC_U8": EDT_SRC_U8, "A3D_EDT_SRC_F32": EDT_SRC_F32}),
+    Surface("a3d_fields.h", {
+        "a3d_field_head_scratch_bytes": (_c_size_t, [ctypes.c_int64, _c_int]),
+        "a3d_field_head_fwd": (_c_int, [_p, _p, _p, _p, _c_int, ctypes.c_int64, _c_int, _p, _p, _p]),
+        "a3d_field_head_bwd": (_c_int, [_p, _p, _p, _p, _p, _c_int, ctypes.c_int64, _c_int, _p, _p, _p, _p]),
+    }, {}, {"A3D_FIELD_HEAD_WIDTH": FIELD_HEAD_WIDTH, "A3D_FIELD_HEAD_MAX_C": FIELD_HEAD_MAX_C, "A3D_FIELD_HEAD_WG_ROWS": FIELD_HEAD_WG_ROWS,
+            "A3D_FIELD_HEAD_ACT_NONE": FIELD_HEAD_ACT_NONE, "A3D_FIELD_HEAD_ACT_SIGMOID": FIELD_HEAD_ACT_SIGMOID}),
+    Surface("a3d_eval.h", {
+        "a3d_vertex_visibility_fwd": (_c_int, [_p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _p]),
+        "a3d_nearest_visible_vertex_scratch_bytes": (_c_size_t, [_c_int, _c_int]),
+        "a3d_nearest_visible_vertex_slab": (_c_int, [_c_int, _c_int]),
+        "a3d_nearest_visible_vertex_fwd": (_c_int, [_p, _p, _p, _c_int, _c_int, _c_int, _p, _p, _p]),
+    }, {}, {"A3D_NVV_THREADS": NVV_THREADS, "A3D_NVV_MAX_TRIPS": NVV_MAX_TRIPS, "A3D_NVV_KEYPOINT_TILE": NVV_KEYPOINT_TILE}),
+)
+SIGNATURES = {name: sig for s in SURFACES for name, sig in s.signatures.items()}  # every entry point of the library: what lib() binds
+assert len(SIGNATURES) == sum(len(s.signatures) for s in SURFACES), "an entry point is registered in two surfaces"
 
 ABI_VERSION = 404  # a3d_version() of the library these signatures belong to (include/a3d.h)
 _lib = None
@@ -325,7 +302,7 @@ def lib():
                 "(or __graft_entry__.build()).  There is no CPU fallback for the HIP hot path."
             )
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(BSDF_SIGNATURES.items()) + list(DERIV_SIGNATURES.items()) + list(TANGENT_SIGNATURES.items()) + list(REG_SIGNATURES.items()) + list(ENVSHADE_SIGNATURES.items()) + list(SDFREG_SIGNATURES.items()) + list(EDT_SIGNATURES.items()) + list(FIELDS_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()):
+        for name, (res, args) in SIGNATURES.items():
             fn = getattr(handle, name)  # AttributeError here == ABI drift
             fn.restype, fn.argtypes = res, args
         if handle.a3d_version() != ABI_VERSION:  # same symbols, other argument lists: a stale build must not be called

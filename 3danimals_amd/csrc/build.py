@@ -3,8 +3,11 @@
     python 3danimals_amd/csrc/build.py [--force] [--profile]
 
 One object per .hip file, linked into 3danimals_amd/lib/liba3d_hip.so (in-tree, git-ignored, travels to the
-GPU box with the snapshot).  raster/dmtet/antialias/normals (and shade, embed, xfm, texture, envlight, bsdf, deriv, tangent, regularizer, envshade, sdfreg, edt, fieldhead, keypoints) are compiled with -ffp-contract=off: their arithmetic is
-specified operation by operation (oracle/raster_ref.c, reference dmtet.py:124-131, mesh.py:276-304).
+GPU box with the snapshot).  SOURCES gives each file its extra flags.  The rule for -ffp-contract=off: a file gets it when its
+arithmetic is specified operation by operation, that is when its bits or its sign tests must agree with a statement elsewhere -- the
+oracle, the torch statement it restates, another translation unit that shares its device code (oracle/raster_ref.c, reference
+dmtet.py:124-131, mesh.py:276-304) -- so the compiler may not contract a multiply and an add on its own.  A file without the flag makes
+no such promise; a new file that makes one takes the flag with it.
 """
 import os
 import subprocess
@@ -73,9 +76,10 @@ def build(force=False, verbose=True, profile=False):
     os.makedirs(LIB_DIR, exist_ok=True)
     os.makedirs(obj_dir, exist_ok=True)
     hipcc = _hipcc()
-    # every header of csrc/ (a kernel's object is stale when ANY of them is newer: a header left out of a hand-kept list once kept a
-    # stale interp.o in the library), the public header and this script
-    headers = sorted(os.path.join(HERE, f) for f in os.listdir(HERE) if f.endswith(".h")) + [os.path.join(os.path.dirname(PKG), "include", h) for h in ("a3d.h", "a3d_bsdf.h", "a3d_deriv.h", "a3d_tangent.h", "a3d_reg.h", "a3d_envshade.h", "a3d_sdfreg.h", "a3d_edt.h", "a3d_fields.h", "a3d_eval.h")] + [os.path.abspath(__file__)]
+    # every header of csrc/ and of include/, listed from the directories (a kernel's object is stale when ANY of them is newer: a header
+    # left out of a hand-kept list once kept a stale interp.o in the library), and this script
+    include = os.path.join(os.path.dirname(PKG), "include")
+    headers = sorted(os.path.join(d, f) for d in (HERE, include) for f in os.listdir(d) if f.endswith(".h")) + [os.path.abspath(__file__)]
     jobs = []
     objs = []
     for src, extra in SOURCES.items():

@@ -1,5 +1,5 @@
 """Shading BSDFs and HDR image loss without a GPU: the public names and signatures, the torch twins in float64 against the reference's
-float64 goldens, the second ABI surface (include/a3d_bsdf.h against _lib.BSDF_SIGNATURES / BsdfDesc), argument validation before any
+float64 goldens, the op and loss codes of ops.py against include/a3d_bsdf.h, argument validation before any
 launch, the call plan of ops.bsdf (merged dimensions, strides, runs), and known answers of the twins."""
 import ctypes
 import importlib
@@ -7,15 +7,15 @@ import inspect
 import json
 import math
 import os
-import re
 import sys
 
 import pytest
 import torch
 
-from conftest import GOLDEN, ROOT, golden
+from conftest import GOLDEN, golden
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_check as A  # noqa: E402
 import bsdf_cases as C  # noqa: E402
 
 NAMES = ("lambert", "frostbite_diffuse", "pbr_specular", "pbr_bsdf", "image_loss", "_fresnel_shlick", "_ndf_ggx", "_lambda_ggx", "_masking_smith")
@@ -82,65 +82,17 @@ def test_float64_image_loss_twin_reproduces_the_goldens(loss, tm):
     assert bool(((a - b).abs() >= 1e-3 * 0.999).all()) and float(a.min()) >= 0.05  # the conditioning the builder promises
 
 
-def _prototypes(path):
-    """name -> (return kind, [parameter kinds]) of the a3d_* prototypes of a header (the small parser of test_host_cpu.py, restated)."""
-    header = open(path).read()
-    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    header = re.sub(r"//[^\n]*", "", header)
-    header = re.sub(r"^\s*#[^\n]*", "", header, flags=re.M)
-    header = re.sub(r"typedef struct.*?\}\s*\w+;", "", header, flags=re.S)
-
-    def kind(decl):
-        decl = decl.strip()
-        if "*" in decl or re.search(r"\ba3d_stream_t\b", decl):
-            return "char_p" if re.match(r"const\s+char\s*\*$", decl) else "ptr"
-        base = re.sub(r"\b(const|unsigned)\b", "", decl).split()
-        return {"int": "int", "int32_t": "int", "int64_t": "int64", "float": "float", "size_t": "size_t"}.get(base[0] if base else "", "?" + decl)
-
-    protos = {}
-    for m in re.finditer(r"([A-Za-z_][A-Za-z0-9_\s\*]*?)\b(a3d_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", header):
-        ret, name, params = re.sub(r"\b(extern|\"C\")\b", "", m.group(1)).strip(), m.group(2), m.group(3).strip()
-        plist = [] if params in ("", "void") else [kind(re.sub(r"\b[A-Za-z_][A-Za-z0-9_]*\s*$", "", p.strip()) if not p.strip().endswith("*") else p)
-                                                   for p in params.split(",")]
-        protos[name] = (kind(ret), plist)
-    return protos
-
-
 def test_second_header_matches_the_second_table_and_the_first_surface_is_untouched():
-    L = importlib.import_module("3danimals_amd._lib")
-    protos = _prototypes(os.path.join(ROOT, "include", "a3d_bsdf.h"))
-    assert set(protos) == set(L.BSDF_SIGNATURES) and set(ENTRIES) < set(protos), set(protos) ^ set(L.BSDF_SIGNATURES)
-    ck = {ctypes.c_void_p: "ptr", ctypes.c_int: "int", ctypes.c_int64: "int64", ctypes.c_float: "float", ctypes.c_size_t: "size_t"}
-    for name, (res, args) in L.BSDF_SIGNATURES.items():
-        assert protos[name] == (ck[res], [ck[a] for a in args]), (name, protos[name])
-        assert hasattr(L.lib(), name), name
-    # the check bites
-    assert protos["a3d_bsdf_fwd"] != ("int", ["ptr"]) and protos["a3d_bsdf_rows"][0] == "int64"
-    # a3d.h, SIGNATURES and the version are as they were
-    first = _prototypes(os.path.join(ROOT, "include", "a3d.h"))
-    assert set(first) == set(L.SIGNATURES) and not set(first) & set(protos) and len(L.SIGNATURES) == 92
-    assert L.lib().a3d_version() == L.ABI_VERSION == 404
-    # the descriptor, field for field
-    text = open(os.path.join(ROOT, "include", "a3d_bsdf.h")).read()
-    body = re.sub(r"/\*.*?\*/", "", re.search(r"typedef struct a3d_bsdf_desc \{(.*?)\} a3d_bsdf_desc;", text, flags=re.S).group(1), flags=re.S)
-    kinds = {"uint32_t": ctypes.c_uint32, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float}
-    want = []
-    for decl in [d.strip() for d in body.split(";") if d.strip()]:
-        m = re.match(r"(.*?)\s*(\*?)\s*(\w+)(?:\[(\d+)\])?$", decl)
-        base = ctypes.c_void_p if m.group(2) else kinds[m.group(1).replace("const", "").strip()]
-        want.append((m.group(3), base * int(m.group(4)) if m.group(4) else base))
-    got = [(n, t) for n, t in L.BsdfDesc._fields_]
-    assert [n for n, _ in got] == [n for n, _ in want] and want[0] == ("size", ctypes.c_uint32)
-    for (n, a), (_, b) in zip(got, want):
-        assert ctypes.sizeof(a) == ctypes.sizeof(b) and getattr(a, "_length_", 0) == getattr(b, "_length_", 0), n
-    assert int(re.search(r"#define A3D_BSDF_TILE (\d+)", text).group(1)) == L.BSDF_TILE
-    assert int(re.search(r"#define A3D_BSDF_MAX_DIMS (\d+)", text).group(1)) == L.BSDF_MAX_DIMS
+    """What is this surface's own (tests/test_abi_cpu.py holds its table, BsdfDesc and the constants to include/a3d_bsdf.h as it does
+    for every surface): the entry points the tests below call, and the op / loss codes of ops.py against the header's macros."""
+    assert set(ENTRIES) < set(A.prototypes("a3d_bsdf.h"))
+    macros = A.defines("a3d_bsdf.h")
     ops = importlib.import_module("3danimals_amd.ops")
     for name, (code, _, _) in ops.BSDF_OPS.items():
         macro = {"lambert": "LAMBERT", "frostbite_diffuse": "FROSTBITE", "pbr_specular": "PBR_SPECULAR", "pbr_bsdf": "PBR", "image_loss": "IMAGE_LOSS"}[name]
-        assert int(re.search(r"#define A3D_BSDF_%s (\d+)" % macro, text).group(1)) == code
+        assert macros["A3D_BSDF_" + macro] == code
     for name, code in ops.IMAGE_LOSSES.items():
-        assert int(re.search(r"#define A3D_LOSS_%s (\d+)" % name.upper(), text).group(1)) == code
+        assert macros["A3D_LOSS_" + name.upper()] == code
 
 
 def _desc(L, **kw):

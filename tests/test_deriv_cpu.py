@@ -1,8 +1,7 @@
-"""Image-space derivatives without a GPU: the third ABI surface (include/a3d_deriv.h against _lib.DERIV_SIGNATURES), argument validation
+"""Image-space derivatives without a GPU: the entry points of include/a3d_deriv.h, argument validation
 before any launch, the float64 restatement (tests/deriv_ref.py) against finite differences of the barycentrics, the torch fp32 path
 against that restatement on every pixel of every scene of the GPU test (the measurement its bounds come from), and the sensitivity of
 those bounds to one dropped pixel."""
-import ctypes
 import importlib
 import os
 import sys
@@ -10,11 +9,9 @@ import sys
 import pytest
 import torch
 
-from conftest import ROOT
-
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_check as A  # noqa: E402
 import deriv_ref as R  # noqa: E402
-from test_bsdf_cpu import _prototypes  # noqa: E402  (the small header parser)
 from test_deriv_gpu import PARENT_UNITS  # noqa: E402
 
 ENTRIES = ("a3d_rast_db_fwd", "a3d_rast_db_bwd", "a3d_interp_da_fwd", "a3d_interp_da_bwd")
@@ -29,21 +26,10 @@ def _ops():
 
 
 def test_third_header_matches_the_third_table_and_the_other_surfaces_are_untouched():
-    L = _L()
-    protos = _prototypes(os.path.join(ROOT, "include", "a3d_deriv.h"))
-    assert set(protos) == set(L.DERIV_SIGNATURES) == set(ENTRIES), set(protos) ^ set(L.DERIV_SIGNATURES)
-    ck = {ctypes.c_void_p: "ptr", ctypes.c_int: "int", ctypes.c_int64: "int64", ctypes.c_float: "float", ctypes.c_size_t: "size_t"}
-    for name, (res, args) in L.DERIV_SIGNATURES.items():
-        assert protos[name] == (ck[res], [ck[a] for a in args]), (name, protos[name])
-        assert hasattr(L.lib(), name), name
-    assert protos["a3d_rast_db_fwd"] != ("int", ["ptr"]) and len(protos["a3d_interp_da_bwd"][1]) == 17  # the check bites
-    assert not set(protos) & set(L.SIGNATURES) and not set(protos) & set(L.BSDF_SIGNATURES)
-    first = _prototypes(os.path.join(ROOT, "include", "a3d.h"))
-    assert set(first) == set(L.SIGNATURES) and len(L.SIGNATURES) == 92 and L.lib().a3d_version() == L.ABI_VERSION == 404
-    text = open(os.path.join(ROOT, "include", "a3d_deriv.h")).read()
-    import re
-
-    assert int(re.search(r"#define A3D_DERIV_MAX_SELECTED (\d+)", text).group(1)) == L.DERIV_MAX_SELECTED
+    """What is this surface's own (tests/test_abi_cpu.py holds every surface's table and constants to its header)."""
+    protos = A.prototypes("a3d_deriv.h")
+    assert set(protos) == set(ENTRIES)
+    assert protos["a3d_rast_db_fwd"] != ("int", ["ptr"]) and len(protos["a3d_interp_da_bwd"][1]) == 17
 
 
 def test_invalid_arguments_are_refused_before_anything_is_launched():

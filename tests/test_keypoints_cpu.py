@@ -1,7 +1,5 @@
-"""Keypoint-transfer evaluation without a GPU: the tenth ABI surface (include/a3d_eval.h against _lib.EVAL_SIGNATURES) with the other
-nine untouched, argument validation before any launch, the restatement (tests/keypoints_ref.py) against what was recorded of the
+"""Keypoint-transfer evaluation without a GPU: the entry points of include/a3d_eval.h, argument validation before any launch, the restatement (tests/keypoints_ref.py) against what was recorded of the
 reference (tests/golden/keypoints.npz, tests/golden/make_golden_keypoints.py), and the CPU side of 3danimals_amd/evaluation.py."""
-import ctypes
 import importlib
 import os
 import sys
@@ -10,12 +8,12 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT, golden
+from conftest import golden
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_check as A  # noqa: E402
 import keypoints_cases as C  # noqa: E402
 import keypoints_ref as R  # noqa: E402
-from test_bsdf_cpu import _prototypes  # noqa: E402
 
 ENTRIES = ("a3d_vertex_visibility_fwd", "a3d_nearest_visible_vertex_scratch_bytes", "a3d_nearest_visible_vertex_slab", "a3d_nearest_visible_vertex_fwd")
 FAKE = 0x1000  # non-NULL, 16-byte aligned, never dereferenced
@@ -35,24 +33,11 @@ def G():
 
 
 def test_tenth_header_matches_the_tenth_table_and_the_other_surfaces_are_untouched():
-    L = _L()
-    path = os.path.join(ROOT, "include", "a3d_eval.h")
-    protos = _prototypes(path)
-    assert set(protos) == set(L.EVAL_SIGNATURES) == set(ENTRIES), set(protos) ^ set(L.EVAL_SIGNATURES)
-    ck = {ctypes.c_void_p: "ptr", ctypes.c_int: "int", ctypes.c_int64: "int64", ctypes.c_float: "float", ctypes.c_size_t: "size_t"}
-    for name, (res, args) in L.EVAL_SIGNATURES.items():
-        assert protos[name] == (ck[res], [ck[a] for a in args]), (name, protos[name])
-        assert hasattr(L.lib(), name), name
+    """What is this surface's own (tests/test_abi_cpu.py holds every surface's table and constants to its header)."""
+    protos = A.prototypes("a3d_eval.h")
+    assert set(protos) == set(ENTRIES)
     assert len(protos["a3d_vertex_visibility_fwd"][1]) == 10 and len(protos["a3d_nearest_visible_vertex_fwd"][1]) == 9
-    others = (L.SIGNATURES, L.BSDF_SIGNATURES, L.DERIV_SIGNATURES, L.TANGENT_SIGNATURES, L.REG_SIGNATURES, L.ENVSHADE_SIGNATURES, L.SDFREG_SIGNATURES,
-              L.EDT_SIGNATURES, L.FIELDS_SIGNATURES)
-    assert tuple(len(t) for t in others) == (92, 5, 4, 5, 8, 2, 2, 2, 3)
-    for other in others:
-        assert not set(protos) & set(other)
-    assert L.lib().a3d_version() == L.ABI_VERSION == 404
-    text = open(path).read()
-    for name, value in (("A3D_NVV_THREADS", L.NVV_THREADS), ("A3D_NVV_MAX_TRIPS", L.NVV_MAX_TRIPS), ("A3D_NVV_KEYPOINT_TILE", L.NVV_KEYPOINT_TILE)):
-        assert "#define %s %d\n" % (name, value) in text
+    text = open(os.path.join(A.INCLUDE, "a3d_eval.h")).read()
     assert "visualize_results.py:238-246" in text and "evaluate.py:461-472" in text  # the reference lines are cited
     overlay = importlib.import_module("3danimals_amd.overlay")
     assert not any("evaluation" in m for m in overlay.MODULES)

@@ -1,8 +1,6 @@
-"""The mesh regularisers without a GPU: the fifth ABI surface (include/a3d_reg.h against _lib.REG_SIGNATURES) with the other four
-untouched, argument validation before any launch, the restatement's edge tables against the reference's recorded ones, the module's
+"""The mesh regularisers without a GPU: the entry points of include/a3d_reg.h, argument validation before any launch, the restatement's edge tables against the reference's recorded ones, the module's
 torch statements against the reference's goldens (float32) and against the restatement (float64, values and gradients), and known
 answers of the corrected Laplacian."""
-import ctypes
 import importlib
 import math
 import os
@@ -11,12 +9,12 @@ import sys
 import pytest
 import torch
 
-from conftest import ROOT, golden
+from conftest import golden
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_check as A  # noqa: E402
 import regularizer_cases as C  # noqa: E402
 import regularizer_ref as R  # noqa: E402
-from test_bsdf_cpu import _prototypes  # noqa: E402
 
 ENTRIES = ("a3d_edge_topology", "a3d_reg_partials", "a3d_laplace_fwd", "a3d_laplace_bwd", "a3d_normal_consistency_fwd",
            "a3d_normal_consistency_bwd", "a3d_edge_length_fwd", "a3d_edge_length_bwd")
@@ -32,23 +30,10 @@ def _M():
 
 
 def test_fifth_header_matches_the_fifth_table_and_the_other_surfaces_are_untouched():
-    L = _L()
-    protos = _prototypes(os.path.join(ROOT, "include", "a3d_reg.h"))
-    assert set(protos) == set(L.REG_SIGNATURES) == set(ENTRIES), set(protos) ^ set(L.REG_SIGNATURES)
-    ck = {ctypes.c_void_p: "ptr", ctypes.c_int: "int", ctypes.c_int64: "int64", ctypes.c_float: "float", ctypes.c_size_t: "size_t"}
-    for name, (res, args) in L.REG_SIGNATURES.items():
-        assert protos[name] == (ck[res], [ck[a] for a in args]), (name, protos[name])
-        assert hasattr(L.lib(), name), name
-    assert protos["a3d_reg_partials"][0] == "size_t" and len(protos["a3d_normal_consistency_bwd"][1]) == 15  # the check bites
-    first = _prototypes(os.path.join(ROOT, "include", "a3d.h"))
-    assert set(first) == set(L.SIGNATURES) and len(L.SIGNATURES) == 92
-    assert len(L.BSDF_SIGNATURES) == 5 and len(L.DERIV_SIGNATURES) == 4 and len(L.TANGENT_SIGNATURES) == 5
-    for other in (L.SIGNATURES, L.BSDF_SIGNATURES, L.DERIV_SIGNATURES, L.TANGENT_SIGNATURES):
-        assert not set(protos) & set(other)
-    assert L.lib().a3d_version() == L.ABI_VERSION == 404
-    text = open(os.path.join(ROOT, "include", "a3d_reg.h")).read()
-    for word, bit in (("REPRESENTATIVE", L.EDGE_REPRESENTATIVE), ("WINNER", L.EDGE_WINNER), ("STAND_IN", L.EDGE_STAND_IN)):
-        assert "#define A3D_EDGE_%s %d " % (word, bit) in text
+    """What is this surface's own (tests/test_abi_cpu.py holds every surface's table and constants to its header)."""
+    protos = A.prototypes("a3d_reg.h")
+    assert set(protos) == set(ENTRIES)
+    assert protos["a3d_reg_partials"][0] == "size_t" and len(protos["a3d_normal_consistency_bwd"][1]) == 15
     overlay = importlib.import_module("3danimals_amd.overlay")
     assert len(overlay.MODULES) == 9 and not any("regularizer" in str(m) for m in overlay.MODULES)  # imported directly (INTEGRATION.md)
     assert _M().HIP_REGULARIZERS is True

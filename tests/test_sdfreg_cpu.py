@@ -1,8 +1,6 @@
-"""The SDF sign-agreement regulariser without a GPU: the seventh ABI surface (include/a3d_sdfreg.h against _lib.SDFREG_SIGNATURES) with
-the other six untouched, argument validation before any launch, the module's torch statements against the reference's goldens (float32,
+"""The SDF sign-agreement regulariser without a GPU: the entry points of include/a3d_sdfreg.h, argument validation before any launch, the module's torch statements against the reference's goldens (float32,
 bit for bit) and against the float64 restatement (tests/sdfreg_ref.py), the routing of sdf_bce_reg_loss, and the builder of the
 vertex -> (edge, side) list the backward kernel walks."""
-import ctypes
 import importlib
 import math
 import os
@@ -11,11 +9,11 @@ import sys
 import pytest
 import torch
 
-from conftest import ROOT, golden
+from conftest import golden
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_check as A  # noqa: E402
 import sdfreg_cases as C  # noqa: E402
-from test_bsdf_cpu import _prototypes  # noqa: E402
 
 ENTRIES = ("a3d_sdf_bce_fwd", "a3d_sdf_bce_bwd")
 FAKE = 0x1000  # non-NULL, 16-byte aligned, never dereferenced
@@ -34,25 +32,11 @@ def _ops():
 
 
 def test_seventh_header_matches_the_seventh_table_and_the_other_surfaces_are_untouched():
-    L = _L()
-    path = os.path.join(ROOT, "include", "a3d_sdfreg.h")
-    protos = _prototypes(path)
-    assert set(protos) == set(L.SDFREG_SIGNATURES) == set(ENTRIES), set(protos) ^ set(L.SDFREG_SIGNATURES)
-    ck = {ctypes.c_void_p: "ptr", ctypes.c_int: "int", ctypes.c_int64: "int64", ctypes.c_float: "float", ctypes.c_size_t: "size_t"}
-    for name, (res, args) in L.SDFREG_SIGNATURES.items():
-        assert protos[name] == (ck[res], [ck[a] for a in args]), (name, protos[name])
-        assert hasattr(L.lib(), name), name
-    assert len(protos["a3d_sdf_bce_fwd"][1]) == 8 and len(protos["a3d_sdf_bce_bwd"][1]) == 10 and protos["a3d_sdf_bce_fwd"][1][1] == "int"  # the check bites
-    first = _prototypes(os.path.join(ROOT, "include", "a3d.h"))
-    assert set(first) == set(L.SIGNATURES) and len(L.SIGNATURES) == 92
-    assert (len(L.BSDF_SIGNATURES), len(L.DERIV_SIGNATURES), len(L.TANGENT_SIGNATURES), len(L.REG_SIGNATURES), len(L.ENVSHADE_SIGNATURES)) == (5, 4, 5, 8, 2)
-    for other in (L.SIGNATURES, L.BSDF_SIGNATURES, L.DERIV_SIGNATURES, L.TANGENT_SIGNATURES, L.REG_SIGNATURES, L.ENVSHADE_SIGNATURES):
-        assert not set(protos) & set(other)
-    assert L.lib().a3d_version() == L.ABI_VERSION == 404
-    text = open(path).read()
-    assert "#define A3D_SDF_BCE_BLOCK_EDGES %d\n" % L.SDF_BCE_BLOCK_EDGES in text
-    assert "#define A3D_SDF_BCE_PARTIAL_WORDS %d\n" % L.SDF_BCE_PARTIAL_WORDS in text
-    assert "dmtet.py:161-169" in text  # the reference lines are cited
+    """What is this surface's own (tests/test_abi_cpu.py holds every surface's table and constants to its header)."""
+    protos = A.prototypes("a3d_sdfreg.h")
+    assert set(protos) == set(ENTRIES)
+    assert len(protos["a3d_sdf_bce_fwd"][1]) == 8 and len(protos["a3d_sdf_bce_bwd"][1]) == 10 and protos["a3d_sdf_bce_fwd"][1][1] == "int"
+    assert "dmtet.py:161-169" in open(os.path.join(A.INCLUDE, "a3d_sdfreg.h")).read()  # the reference lines are cited
     overlay = importlib.import_module("3danimals_amd.overlay")
     assert "model.geometry.dmtet" in overlay.MODULES and "sdf_bce_reg_loss" in overlay.exported_names("model.geometry.dmtet")
     assert _M().HIP_SDF_REG is True

@@ -1,5 +1,4 @@
-"""The tangent frame without a GPU: the fourth ABI surface (include/a3d_tangent.h against _lib.TANGENT_SIGNATURES), the other three
-surfaces untouched, argument validation before any launch, the repository's torch statements and the tests' float64 restatement
+"""The tangent frame without a GPU: the entry points of include/a3d_tangent.h and the op code of ops.py, argument validation before any launch, the repository's torch statements and the tests' float64 restatement
 against the reference's recorded goldens, and the share of pixels the kink mask leaves out on the committed inputs."""
 import ctypes
 import importlib
@@ -9,12 +8,12 @@ import sys
 import pytest
 import torch
 
-from conftest import ROOT, golden
+from conftest import golden
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_check as A  # noqa: E402
 import tangent_cases as C  # noqa: E402
 import tangent_ref as R  # noqa: E402
-from test_bsdf_cpu import _prototypes  # noqa: E402
 
 ENTRIES = ("a3d_shading_normal_rows", "a3d_shading_normal_fwd", "a3d_shading_normal_bwd", "a3d_tangents_fwd", "a3d_tangents_bwd")
 FAKE = 0x1000  # non-NULL, never dereferenced
@@ -29,24 +28,12 @@ def _ru():
 
 
 def test_fourth_header_matches_the_fourth_table_and_the_other_surfaces_are_untouched():
+    """What is this surface's own (tests/test_abi_cpu.py holds every surface's table and constants to its header)."""
     L = _L()
-    protos = _prototypes(os.path.join(ROOT, "include", "a3d_tangent.h"))
-    assert set(protos) == set(L.TANGENT_SIGNATURES) == set(ENTRIES), set(protos) ^ set(L.TANGENT_SIGNATURES)
-    ck = {ctypes.c_void_p: "ptr", ctypes.c_int: "int", ctypes.c_int64: "int64", ctypes.c_float: "float", ctypes.c_size_t: "size_t"}
-    for name, (res, args) in L.TANGENT_SIGNATURES.items():
-        assert protos[name] == (ck[res], [ck[a] for a in args]), (name, protos[name])
-        assert hasattr(L.lib(), name), name
-    assert protos["a3d_shading_normal_rows"][0] == "int64" and len(protos["a3d_tangents_bwd"][1]) == 17  # the check bites
-    # the other three surfaces and the version are as they were
-    first = _prototypes(os.path.join(ROOT, "include", "a3d.h"))
-    assert set(first) == set(L.SIGNATURES) and len(L.SIGNATURES) == 92
-    assert len(L.BSDF_SIGNATURES) == 5 and len(L.DERIV_SIGNATURES) == 4
-    for other in (L.SIGNATURES, L.BSDF_SIGNATURES, L.DERIV_SIGNATURES):
-        assert not set(protos) & set(other)
-    assert L.lib().a3d_version() == L.ABI_VERSION == 404
-    text = open(os.path.join(ROOT, "include", "a3d_tangent.h")).read()
-    assert "#define A3D_SHADING_NORMAL %d\n" % L.SHADING_NORMAL_OP in text and L.SHADING_NORMAL_OP == 5
-    assert "A3D_SHADING_NORMAL" not in open(os.path.join(ROOT, "include", "a3d_bsdf.h")).read()
+    protos = A.prototypes("a3d_tangent.h")
+    assert set(protos) == set(ENTRIES)
+    assert protos["a3d_shading_normal_rows"][0] == "int64" and len(protos["a3d_tangents_bwd"][1]) == 17
+    assert L.SHADING_NORMAL_OP == 5 and "A3D_SHADING_NORMAL" not in open(os.path.join(A.INCLUDE, "a3d_bsdf.h")).read()
     ops = importlib.import_module("3danimals_amd.ops")
     assert ops.TANGENT_OPS["shading_normal"] == (5, (3,) * 6, 3) and "shading_normal" not in ops.BSDF_OPS
 
