@@ -16,4 +16,4 @@ HIP device.
 from . import evaluation, synthetic, tetgrid  # noqa: F401  (pure numpy/torch helpers; evaluation loads the native code at its first call on CUDA tensors)
 
 __all__ = ["evaluation", "synthetic", "tetgrid"]
-__version__ = "0.6.0"  # round 6 (C ABI: a3d_version() = 404)
+__version__ = "0.6.0"  # round 6 (C ABI: a3d_version() = 405)

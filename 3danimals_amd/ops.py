@@ -848,9 +848,7 @@ def _cover_counted(rast, tile):
         scratch = torch.empty(_lib.lib().a3d_cover_scratch_bytes(B, H, W) // 4, dtype=torch.int32, device=rast.device)
         call("a3d_cover_count", ptr(rast), B, H, W, tile, ptr(scratch), stream())
     nb = _lib.lib().a3d_cover_blocks(B, H, W)
-    tail = _lib.read_back(scratch[nb:nb + _lib.lib().a3d_cover_groups(B, H, W) * _lib.lib().a3d_cover_group_stride()])  # THE read-back: one sum per group of 64 blocks, one per 64-byte line; words 1, 2 of the first line: the binned rasteriser's status
-    if tail.shape[0] > 2 and int(tail[1]) > 0:
-        _rast_bins_grow((rast.device, B, H, W), int(tail[1]), int(tail[2]))
+    tail = _lib.read_back(scratch[nb:nb + _lib.lib().a3d_cover_groups(B, H, W) * _lib.lib().a3d_cover_group_stride()])  # THE read-back: one sum per group of 64 blocks, one per 64-byte line; the other words of a line are never part of the sums
     return scratch, int(tail[::_lib.lib().a3d_cover_group_stride()].sum())
 
 
@@ -949,31 +947,6 @@ def drop_pending_resolve(rast):
     """A deferred raster buffer whose consumer failed before it ran: resolve it now (keys re-armed, nothing left pinned)."""
     ensure_resolved(rast)
 
-# the binned path (a3d_rast_opts.bins: per-tile triangle lists + a fine pass, no memory-side atomics): its scratch is kept per (device,
-# stream, frame) like the key buffer (the fine pass leaves the tile counts at zero), the capacity of a tile list per (device, frame):
-# 1024 entries to start with, 4 x the largest count ever reported above half the capacity (the covered-pixel read-back carries the
-# report).  An overflowing tile is still rasterised exactly -- by the slow route inside the fine pass -- so the capacity is a matter of
-# speed only; memory is not a constraint (1024 entries: 67 MB at B = 16, 256 x 256).
-# OFF by default (round 5, measured inside the bench step on one box): bin launch 18.3 us + fine pass 36-60 us against 23.6 + 9.0 us for
-# the triangle-parallel atomics + resolve.  Same fragment tests in total, but dealt out by SCREEN position: under a head-on camera
-# nearly all of the mesh's 12k triangles fall into a dozen 256-pixel blocks (1400 list entries each, six chunks of dependent gathers
-# in ONE work-group) and the launch ends when that work-group does; the atomic form deals the same work out by triangle and does not
-# care where on screen it lands (DESIGN.md, "Rasteriser: the binned form").
-RASTER_BINNED = os.environ.get("A3D_RASTER_BINNED", "0") == "1"
-RASTER_BIN_CAP0 = 1024
-_rast_bins = {}
-_rast_bin_caps = {}
-rast_bin_events = dict(grown=0, overflowed_blocks=0)
-
-
-def _rast_bins_grow(key, max_count, overflowed):
-    cap = _rast_bin_caps.get(key, RASTER_BIN_CAP0)
-    want = 1 << max(4, int(4 * max_count - 1).bit_length())
-    rast_bin_events["overflowed_blocks"] += overflowed
-    if want > cap and want <= (1 << 16):
-        _rast_bin_caps[key] = want
-        rast_bin_events["grown"] += 1
-
 
 class _Rasterize(torch.autograd.Function):
     @staticmethod
@@ -991,20 +964,10 @@ class _Rasterize(torch.autograd.Function):
         cover = None
         if H % 8 == 0 and W % 8 == 0 and (H * W) % 256 == 0 and F > 0:
             cover = torch.empty(_lib.lib().a3d_cover_scratch_bytes(B, H, W) // 4, dtype=torch.int32, device=clip.device)
-        # binned path (per-tile triangle lists, no key buffer) when the frame qualifies; otherwise the atomic path and its key buffer
-        bins = None
-        if RASTER_BINNED and cover is not None and prev is None:
-            cap = _rast_bin_caps.get((clip.device, B, H, W), RASTER_BIN_CAP0)
-            bins = _rast_bins.pop(key, None)
-            if bins is None or bins[1] != cap:
-                nbytes = _lib.lib().a3d_rast_bins_bytes(B, H, W, cap)
-                bins = (torch.empty(nbytes, dtype=torch.uint8, device=clip.device), cap, False) if nbytes else None
-        scratch, clean = None, False
-        if bins is None:
-            scratch = _rast_keys.pop(key, None)
-            clean = scratch is not None
-            if scratch is None:
-                scratch = torch.empty(_lib.lib().a3d_rast_scratch_bytes(B, H, W), dtype=torch.uint8, device=clip.device)
+        scratch = _rast_keys.pop(key, None)
+        clean = scratch is not None
+        if scratch is None:
+            scratch = torch.empty(_lib.lib().a3d_rast_scratch_bytes(B, H, W), dtype=torch.uint8, device=clip.device)
         # ... and so does what the silhouette analysis of this frame needs first (pixel-space vertex positions, zeroed append counters):
         # AAAnalysis picks them up when it is built for this raster buffer and this clip tensor
         aa_screen = aa_count = None
@@ -1034,17 +997,11 @@ class _Rasterize(torch.autograd.Function):
             opts.normals_off, opts.normals_adj = ptr(job.adjacency.off), ptr(job.adjacency.adj)
             opts.normals_acc_a, opts.normals_a, opts.normals_acc_b, opts.normals_b = ptr(job.acc_a), ptr(job.nrm_a), ptr(job.acc_b), ptr(job.nrm_b)
         opts.lists_stride = stride
-        if bins is not None:
-            opts.bins, opts.bin_cap, opts.bins_clean = ptr(bins[0]), bins[1], int(bins[2])
-        defer = bool(defer) and DEFER_RESOLVE and cover is not None and bins is None and prev is None and F > 0
+        defer = bool(defer) and DEFER_RESOLVE and cover is not None and prev is None and F > 0
         defer = defer and not torch.cuda.is_current_stream_capturing() and dispatch_order_ok(clip.device)  # (probed once per device)
         opts.defer_resolve = int(defer)
         call("a3d_rast_fwd", ptr(clip), clip.shape[0], ptr(tri32), B, V, F, H, W, ptr(rast), ptr(scratch), int(clean), ctypes.addressof(opts), stream(),
              tag=("" if job is None else f"[N{opts.normals_B_a}+{opts.normals_B_b}]") + ("[defer]" if defer else ""))
-        if bins is not None:
-            if len(_rast_bins) >= 4:
-                _rast_bins.clear()
-            _rast_bins[key] = (bins[0], bins[1], bool(bins[2]) or F > 0)  # (after a successful call its fine pass left every tile count at zero; F == 0 launches nothing)
         if job is not None:
             job.done = True
         if opp is not None:
@@ -1058,7 +1015,7 @@ class _Rasterize(torch.autograd.Function):
             _rast_keys.clear()
         if defer:  # the keys are full until a resolve has consumed them: they travel with the raster buffer, not back into the cache
             _pending_resolve.put(rast.detach(), dict(clip=clip, tri32=tri32, keys=scratch, key=key, rast=rast, cover=cover))
-        elif scratch is not None and (F > 0 or clean):  # only after a successful call whose resolve re-armed the keys (F == 0 returns before touching
+        elif F > 0 or clean:  # only after a successful call whose resolve re-armed the keys (F == 0 returns before touching
             _rast_keys[key] = scratch  # them: a fresh torch.empty buffer must not come back as "clean"; a failed call leaves the buffer out too)
         ctx.save_for_backward(clip, tri32, rast)
         return rast

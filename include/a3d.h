@@ -31,7 +31,7 @@ extern "C" {
 
 typedef void* a3d_stream_t;
 
-int a3d_version(void); /* 404 = this header */
+int a3d_version(void); /* 405 = this header */
 const char* a3d_last_error(void);
 
 /* Box fingerprint for the benchmark line (no reference counterpart: the reference's meter, /root/reference/model/utils/meters.py:119, reports
@@ -320,6 +320,8 @@ int a3d_shade_bwd_rows(const float* g_shaded, const float* gb, const a3d_shade_p
  * scratch (a3d_cover_scratch_bytes) = int block_count[a3d_cover_blocks] (covered pixels per 256 list positions) followed by
  * int group_sum[a3d_cover_groups * a3d_cover_group_stride] (sums of 64 consecutive blocks, every stride-th word; the rest zero).  a3d_cover_count fills both -- or a3d_rast_fwd's resolve already did
  * (cover_scratch, tile = 8 and H*W a multiple of 256).  The caller reads the group sums back and adds them up: the length of the list.
+ * Words 1 and 2 of the group-sum area are unused words, which a3d_rast_fwd's triangle launch zeroes with the rest of the area; word 3 is the
+ * status word of a3d_rast_resolve_gbuffer_fwd's look-back (below).
  * emit writes pix (every work-group derives its own offset from the group sums and block counts before it: no scan launch) and, when
  * given, the inverse map inv[B*H*W] (entry of the list per pixel, -1 = uncovered) that a3d_composite_aa_* reads.
  */
@@ -376,22 +378,11 @@ typedef struct a3d_rast_opts {
     float* normals_b;
     int32_t normals_B_a;
     int32_t normals_B_b;
-    /* (402) the BINNED path -- the triangle launch appends every triangle to the list of each 8x8 tile its pixel box touches, a second
-     * launch (one work-group per 256-pixel block) runs the fragment tests per tile with the depth test in LDS and writes the texels: no
-     * memory-side atomics on the frame, no key buffer, no resolve pass; the same triangle ids bit for bit.  Taken when bins != NULL,
-     * cover_scratch != NULL, prev_rast == NULL and a3d_rast_bins_bytes(B, H, W, bin_cap) != 0; `scratch` may then be NULL.  A tile whose
-     * list overflows bin_cap is rasterised exactly all the same (its block takes every triangle); the third word of the group-sum area
-     * of cover_scratch counts such blocks and the second holds the largest tile count above bin_cap / 2 (0 = none), for the caller to
-     * size the lists by.  bins_clean: the tile counts are zero (as the previous call on the same stream left them). */
-    void* bins;                    /* a3d_rast_bins_bytes(B, H, W, bin_cap) bytes */
-    int32_t bin_cap;               /* entries per tile list (>= 16) */
-    int32_t bins_clean;
     /* (402) defer_resolve: only the triangle launch runs (cover_scratch required; its look-back flags are zeroed); `rast` is written by the
      * caller's next call -- a3d_rast_resolve_gbuffer_fwd (resolve + covered-pixel list + G-buffer rows in one launch) or a3d_rast_resolve. */
     int32_t defer_resolve;
     int32_t reserved;
 } a3d_rast_opts;
-size_t a3d_rast_bins_bytes(int B, int H, int W, int bin_cap); /* 0: the frame cannot take the binned path */
 /* The second half of a3d_rast_fwd(defer_resolve = 1) on the same `scratch` (keys) and `cover_scratch`:
  * a3d_rast_resolve = the resolve launch alone (texels + block counts + group sums);
  * a3d_rast_resolve_gbuffer_fwd = resolve AND a3d_cover_gbuffer_fwd in ONE launch: every 256-pixel block counts its covered pixels from the

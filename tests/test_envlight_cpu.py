@@ -26,7 +26,7 @@ def test_envlight_prototypes_are_declared_bound_and_exported():
         assert re.search(r"\bint\s+%s\s*\(\s*const a3d_env_desc\*\s*desc,\s*a3d_stream_t\s+stream\)" % name, header), name
         assert L.SIGNATURES[name] == (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]), name
         assert hasattr(L.lib(), name), name
-    assert L.ABI_VERSION == 404
+    assert L.ABI_VERSION == 405
     assert ctypes.sizeof(L.EnvDesc) == 16 + 4 * 8
 
 

@@ -132,14 +132,12 @@ def test_covered_pixels_of_hand_made_buffers(shape, which, dev, ops):
 
 # ------------------------------------------------------------------------------------------------ rasteriser
 @pytest.mark.parametrize("n_small,n_big", [(3, 0), (65, 3), (300, 65), (0, 256)])
-@pytest.mark.parametrize("binned", [False, True])
-def test_rasterize_candidate_and_tile_scans(binned, n_small, n_big, dev, ops, monkeypatch):
-    """Sites: raster.hip rs_tri_kernel (the tile counts of a work-group's big boxes: a3d_block_excl_scan<4>) and rs_fine_kernel (the
-    candidate counts of a chunk of a tile's list).  64 x 64 frame; ``n_small`` triangles stacked inside one 8x8 tile at different
-    depths -- its list is 3 (a part of wave 0), 65 (lane 63 and the next lane 0) or 300 entries (a second, partly filled chunk) long --
-    and ``n_big`` triangles whose boxes span most of the frame (above 512 pixels and above four tiles: the tile stage of either path;
-    the binned launch holds 256 triangles per work-group, so 65 of them sit on both sides of a wave seam).  Bit-exact against
-    oracle/raster_ref.c."""
+def test_rasterize_candidate_and_tile_scans(n_small, n_big, dev, ops):
+    """Site: raster.hip rs_tri_kernel (the prefix of a wave's box sizes that pools the candidate pixels, and the tile counts of a
+    work-group's big boxes: a3d_block_excl_scan<4>).  64 x 64 frame; ``n_small`` triangles stacked inside one 8x8 tile at different
+    depths -- 3 (a part of one wave's slice), 65 (one more than the 64 of a work-group) or 300 (several work-groups) -- and ``n_big``
+    triangles whose boxes span most of the frame (above 512 pixels: the tile stage; none, a few beside small ones, and work-groups
+    that hold nothing else).  Bit-exact against oracle/raster_ref.c."""
     from oracle import raster_ref
 
     H = W = 64
@@ -152,11 +150,8 @@ def test_rasterize_candidate_and_tile_scans(binned, n_small, n_big, dev, ops, mo
     w = 0.5 + torch.rand(n, 3, 1, generator=g)
     clip = torch.cat([xy * w, z * w, w], -1).reshape(1, 3 * n, 4).contiguous()
     tri = torch.arange(3 * n, dtype=torch.int32).reshape(n, 3)[torch.randperm(n, generator=g)].contiguous()
-    monkeypatch.setattr(ops, "RASTER_BINNED", binned)
-    ops._rast_bins.clear()
     ref = raster_ref.rasterize(clip, tri, (H, W))
     out = ops.rasterize(clip.to(dev), tri.to(dev), (H, W)).cpu()
-    assert bool(ops._rast_bins) == binned  # (the path asked for is the path taken)
     assert np.array_equal(out[..., 3].numpy(), ref[..., 3].numpy())
     assert np.array_equal(out.numpy(), ref.numpy())
     assert float((ref[..., 3] > 0).float().sum()) > 0

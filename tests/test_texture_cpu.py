@@ -25,7 +25,7 @@ def test_texture_prototypes_are_declared_and_bound():
         assert re.search(r"\bint\s+%s\s*\(" % name, header), name
         assert name in L.SIGNATURES, name
         assert hasattr(L.lib(), name), name
-    assert L.ABI_VERSION == 404
+    assert L.ABI_VERSION == 405
 
 
 def test_tex_desc_matches_the_header_field_for_field():
