@@ -240,6 +240,8 @@ __global__ __launch_bounds__(64 * G3_WAVES, 1) void gm_nn3_kernel(const float* _
     }
 }
 
+inline bool gm_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 }  // namespace
 
 extern "C" int a3d_gemm_nn_relumask(const float* A, const float* B, const float* X, int64_t M, int N, int K, float* C, a3d_stream_t stream) {
@@ -247,6 +249,7 @@ extern "C" int a3d_gemm_nn_relumask(const float* A, const float* B, const float*
     A3D_CHECK_ARG(X == nullptr || K >= 256);  // the mask is gathered over the first 8 K chunks
     if (M == 0) return A3D_OK;
     A3D_CHECK_ARG(A && B && C);
+    A3D_CHECK_ARG(gm_aligned16(A) && gm_aligned16(B) && gm_aligned16(X));  // read as 16-byte vectors (K % 32 == 0, N = 256: every row starts on one)
     hipStream_t s = (hipStream_t)stream;
     if (K == 256) {  // persistent, weight half resident in LDS
         // per device ordinal (a process may drive more than one GPU); idempotent values, so a race between threads is harmless

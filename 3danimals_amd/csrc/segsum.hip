@@ -22,7 +22,7 @@ __global__ __launch_bounds__(256) void ss_kernel(const float* __restrict__ g, co
         }
         return v;
     };
-    // VEC floats at element offset i (16-byte aligned when VEC == 4: C % 4 == 0 and torch allocations are 256 B aligned)
+    // VEC floats at element offset i (16-byte aligned when VEC == 4: C % 4 == 0 and the entry points refuse a misaligned g, y or g_pre)
     auto add_group = [&](long long i, float* acc) {
         if constexpr (VEC == 4) {
             float4 v, t;
@@ -90,7 +90,10 @@ __global__ __launch_bounds__(256) void ss_kernel(const float* __restrict__ g, co
     }
 }
 
-// y[p,:] = max(y[p,:] + rows[img[p],:], 0) in place: a per-image addend folded into the ReLU pass that follows a GEMM.
+// torch.relu: a NaN stays a NaN (fmaxf would return the 0 and hide a diverged field from the next layer), -0.0 becomes +0.0
+__device__ __forceinline__ float ss_relu(float v) { return v <= 0.f ? 0.f : v; }
+
+// y[p,:] = relu(y[p,:] + rows[img[p],:]) in place: a per-image addend folded into the ReLU pass that follows a GEMM.
 // Pure streaming (read + write of y); rows[B,C] stays in L2.  One thread per 16 B (or per float when C % 4 != 0).
 __global__ __launch_bounds__(256) void ss_add_relu4_kernel(float4* __restrict__ y, const float4* __restrict__ rows,
                                                            const long long* __restrict__ img, unsigned n, unsigned CV, int B) {
@@ -103,7 +106,7 @@ __global__ __launch_bounds__(256) void ss_add_relu4_kernel(float4* __restrict__ 
         const float4 a = rows[(unsigned)b * CV + c];
         v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w;
     }
-    v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+    v.x = ss_relu(v.x); v.y = ss_relu(v.y); v.z = ss_relu(v.z); v.w = ss_relu(v.w);
     y[i] = v;
 }
 
@@ -114,13 +117,17 @@ __global__ __launch_bounds__(256) void ss_add_relu1_kernel(float* __restrict__ y
     const long long p = i / C;
     const long long b = img[p];
     const float add = (unsigned long long)b < (unsigned long long)B ? rows[b * C + (i - p * C)] : 0.f;
-    y[i] = fmaxf(y[i] + add, 0.f);
+    y[i] = ss_relu(y[i] + add);
 }
 
+static inline bool ss_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+static inline int ss_vec(int C) { return (C % 4 == 0 && C >= 64) ? 4 : 1; }  // floats per column-lane: the vector path reads and writes 16 bytes
+
 static int ss_launch(const float* g, const int64_t* img, int64_t P, int C, int B, float* out, const float* y, float* g_pre, hipStream_t s) {
+    const int vec = ss_vec(C);
     A3D_HIP(hipMemsetAsync(out, 0, sizeof(float) * (size_t)B * C, s));
     if (P == 0) return A3D_OK;
-    const int vec = (C % 4 == 0 && C >= 64) ? 4 : 1;
     int CP = 1;
     while (CP < C / vec && CP < 256) CP <<= 1;
     const int rows = SS_ROWS;
@@ -142,6 +149,7 @@ static int ss_launch(const float* g, const int64_t* img, int64_t P, int C, int B
 extern "C" int a3d_rows_segsum(const float* g, const int64_t* img, int64_t P, int C, int B, float* out, a3d_stream_t stream) {
     A3D_CHECK_ARG(out && B > 0 && C > 0 && P >= 0);
     A3D_CHECK_ARG(P == 0 || (g && img));
+    A3D_CHECK_ARG(ss_vec(C) == 1 || ss_aligned16(g));
     return ss_launch(g, img, P, C, B, out, nullptr, nullptr, (hipStream_t)stream);
 }
 
@@ -149,6 +157,7 @@ extern "C" int a3d_rows_add_relu_fwd(float* y, const float* rows, const int64_t*
     A3D_CHECK_ARG(B > 0 && C > 0 && P >= 0);
     if (P == 0) return A3D_OK;
     A3D_CHECK_ARG(y && rows && img);
+    A3D_CHECK_ARG(C % 4 != 0 || (ss_aligned16(y) && ss_aligned16(rows)));  // read and written as float4
     const long long n = (long long)P * C;
     if (C % 4 == 0 && n / 4 < 0xffffffffll && (long long)B * C / 4 < 0xffffffffll)
         hipLaunchKernelGGL(ss_add_relu4_kernel, dim3(a3d_div_up(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, (float4*)y, (const float4*)rows,
@@ -163,5 +172,6 @@ extern "C" int a3d_rows_add_relu_bwd(const float* g, const float* y, const int64
                                      a3d_stream_t stream) {
     A3D_CHECK_ARG(g_rows && B > 0 && C > 0 && P >= 0);
     A3D_CHECK_ARG(P == 0 || (g && y && img && g_pre));
+    A3D_CHECK_ARG(ss_vec(C) == 1 || (ss_aligned16(g) && ss_aligned16(y) && ss_aligned16(g_pre)));
     return ss_launch(g, img, P, C, B, g_rows, y, g_pre, (hipStream_t)stream);
 }

@@ -1539,7 +1539,9 @@ CHECK_SORTED_INDEX = False  # debugging aid: device-side assert (no host sync) t
 
 def _assert_sorted(img):
     """The per-image segment sums (csrc/segsum.hip) treat a 128-row block whose first and last rows belong to the same image as
-    single-image: the index must be non-decreasing (the render path's is: pixel lists are image-major, padding rows repeat an image)."""
+    single-image: the index must be non-decreasing (the render path's is: pixel lists are image-major, padding rows repeat the LAST
+    image).  A list that breaks the contract is summed wrongly without a sign -- one of at most 128 rows that starts and ends in image 0
+    with other images in between goes to image 0 whole -- and this check, when switched on, is what reports it."""
     if CHECK_SORTED_INDEX and img is not None and img.numel() > 1:
         torch._assert_async((img[1:] >= img[:-1]).all(), "point -> image index must be non-decreasing")
 
@@ -1576,14 +1578,31 @@ class _RowsAddReLU(torch.autograd.Function):
         return g_pre, g_rows, None
 
 
+def _rows_args(what, y, rows, img, in_place=True):
+    """Shapes and types of a point list y [P,C], per-image rows [B,C] (or B itself) and the point -> image index: the entry points take
+    raw pointers, so what they would misread is refused here -- shapes and types first (ValueError), then the device (A3DError)."""
+    b = rows if isinstance(rows, int) else (rows.shape[0] if rows.dim() == 2 else -1)
+    if y.dim() != 2 or y.shape[1] < 1 or b < 1 or (not isinstance(rows, int) and rows.shape[1] != y.shape[1]):
+        raise ValueError(f"{what}: expected a point list [P,C] with C >= 1 and B >= 1 per-image rows [B,C], got {list(y.shape)} and "
+                         f"{rows if isinstance(rows, int) else list(rows.shape)}")
+    if img.dtype != torch.int64 or img.dim() != 1 or img.shape[0] != y.shape[0] or not img.is_contiguous():
+        raise ValueError(f"{what}: the point -> image index must be int64, contiguous and [P] = [{y.shape[0]}], got {img.dtype} {list(img.shape)} "
+                         f"with strides {list(img.stride())}")
+    if in_place and (y.dtype != torch.float32 or not y.is_contiguous()):
+        raise ValueError(f"{what}: the point list is written in place and must be float32 and contiguous, got {y.dtype} with strides {list(y.stride())}")
+    require_device(y, None if isinstance(rows, int) else rows, img, what=what)
+
+
 def rows_add_relu_raw_(y, rows, img):
     """In place, no autograd: y[p] = relu(y[p] + rows[img[p]]) (used inside hostnets' stack Function)."""
+    _rows_args("rows_add_relu_raw_", y, rows, img)
     call("a3d_rows_add_relu_fwd", ptr(y), ptr(f32h(rows)), ptr(img), y.shape[0], y.shape[1], rows.shape[0], stream(), tag=f"[C{y.shape[1]}]")
     return y
 
 
 def rows_segsum_raw(g, img, b):
     """[B,C] per-image sums of g [P,C] (no autograd); img non-decreasing."""
+    _rows_args("rows_segsum_raw", g, int(b), img, in_place=False)
     _assert_sorted(img)
     g = f32c(g)
     out = torch.empty((b, g.shape[1]), dtype=torch.float32, device=g.device)
@@ -1593,6 +1612,7 @@ def rows_segsum_raw(g, img, b):
 
 def rows_add_relu_(y, rows, img):
     """In place: y[p] = relu(y[p] + rows[img[p]]);  y [P,C] fresh GEMM output, rows [B,C], img int64 [P], non-decreasing."""
+    _rows_args("rows_add_relu_", y, rows, img)
     _assert_sorted(img)
     return _RowsAddReLU.apply(y, rows, img)
 
@@ -2023,17 +2043,25 @@ class _HarmonicEmbed(torch.autograd.Function):
 def harmonic_embed(x, freq, symmetrize=False, ones=False):
     """[P,3] -> [P, 3 + 6n (+1)] = [x (|x_0| if symmetrize), sin(x_c f_k), cos(x_c f_k), (1)] (csrc/embed.hip).  First-order
     differentiable only (double backward raises): the SDF regulariser, which differentiates the field twice, takes the torch path."""
-    return _HarmonicEmbed.apply(x, freq, symmetrize, ones)
+    if x.dim() != 2 or x.shape[1] != 3 or freq.dim() != 1 or freq.shape[0] < 1:
+        raise ValueError(f"harmonic_embed: expected x [P,3] and n >= 1 frequencies [n], got {list(x.shape)} and {list(freq.shape)}")
+    if not (x.is_floating_point() and freq.is_floating_point()):
+        raise ValueError(f"harmonic_embed: x and freq must be floating point, got {x.dtype} and {freq.dtype}")
+    return _HarmonicEmbed.apply(x, freq, bool(symmetrize), bool(ones))
 
 
 # ---------------------------------------------------------------------------------------------- fp32 MFMA GEMM + ReLU adjoint
 def gemm_nn_relumask(a, b, x=None):
     """(a [M,K] @ b [K,256]) * (x [M,256] > 0)  (x None: plain product) -- csrc/gemm.hip, fp32 MFMA.  No autograd: it is the
-    input-gradient GEMM inside hostnets' stack backward."""
-    require_device(a, b, what="gemm_nn_relumask")
+    input-gradient GEMM inside hostnets' stack backward.  The mask is read in place: float32, contiguous, and only for K >= 256."""
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] < 32 or a.shape[1] % 32 or tuple(b.shape) != (a.shape[1], 256):
+        raise ValueError(f"gemm_nn_relumask: expected a [M,K] and b [K,256] with K a positive multiple of 32, got {list(a.shape)} and {list(b.shape)}")
+    if x is not None and (tuple(x.shape) != (a.shape[0], 256) or x.dtype != torch.float32 or not x.is_contiguous() or a.shape[1] < 256):
+        raise ValueError(f"gemm_nn_relumask: the mask must be float32, contiguous and [M,256] = [{a.shape[0]},256], with K >= 256; got {x.dtype} "
+                         f"{list(x.shape)} with strides {list(x.stride())} and K = {a.shape[1]}")
+    require_device(a, b, x, what="gemm_nn_relumask")
     a, b = f32c(a), f32c(b)
     M, K = a.shape
-    assert b.shape == (K, 256) and K % 32 == 0 and (x is None or (x.shape == (M, 256) and x.is_contiguous() and x.dtype == torch.float32))
     c = torch.empty((M, 256), dtype=torch.float32, device=a.device)
     call("a3d_gemm_nn_relumask", ptr(a), ptr(b), ptr(x), M, 256, K, ptr(c), stream())
     return c
