@@ -36,7 +36,8 @@ class AaRide(ctypes.Structure):
 class CaBuffer(ctypes.Structure):
     _fields_ = [("size", ctypes.c_uint32), ("C", ctypes.c_int32), ("vals", _p), ("bg", _p), ("out", _p), ("g_out", _p), ("g_vals", _p),
                 ("bg_batch", ctypes.c_int32), ("reserved", ctypes.c_int32), ("bg_channels", ctypes.c_int32), ("g_stride", ctypes.c_int32),
-                ("g_channels", ctypes.c_int32), ("out_channels", ctypes.c_int32), ("vals_rows", ctypes.c_int64)]
+                ("g_channels", ctypes.c_int32), ("out_channels", ctypes.c_int32), ("vals_rows", ctypes.c_int64),
+                ("spp", ctypes.c_int32), ("aa", ctypes.c_int32), ("cover_rast", _p), ("null_vals", _p), ("g_null", _p)]
 
 
 class CaShade(ctypes.Structure):

@@ -12,6 +12,8 @@
 //              for every colour buffer it antialiases (render.py:311-315).
 //   fwd/bwd  : out = color (+) blends over the work list; backward adds colour gradients and sends
 //              d(alpha)/d(clip) to the two vertices of the crossing edge.
+//   spp > 1  : the compositor's supersampled mode (ms_* kernels, a3d_ca_buffer.spp): blocks of s x s samples composited, blended with the
+//              full-resolution records and averaged on the shading grid, without a full-resolution image.
 // HBM traffic: analyze reads 16 B/pixel; fwd/bwd copy 4C B/pixel in and out; the work list is a few thousand
 // 16-byte records per image.  Compiled with -ffp-contract=off so sign tests agree with the oracle.
 #include "a3d_common.h"
@@ -656,6 +658,185 @@ __global__ __launch_bounds__(256) void ca_bwd_kernel(CaJob ja, CaJob jb, const A
     A3D_STAMP(3, 5);
 }
 
+// ---- the compositor in supersampled mode (a3d_ca_buffer.spp = s > 1) -----------------------------------------------------------------------
+// render_mesh(spp = s, msaa) of the reference shades at the nearest-minified raster (texel (y s, x s) of every s x s block), replicates
+// [value, 1] over the block, composites with the FULL-resolution coverage, antialiases at full resolution and averages the blocks
+// (render.py:217-219, 258-268, 318).  None of the full-resolution images exists here: a block with k covered samples is
+// (k [v, 1] + (s^2 - k) [bg, 0]) / s^2, written once on the shading grid, and every crossing record of the full-resolution work list adds
+// alpha (pre(p1) - pre(p0)) / s^2 to the block of its destination sample.  v is the block's point row, or -- the block's shading sample is
+// uncovered but another sample is not -- the image's `null` row: what shade() returns for all-zero attributes, which is the colour the
+// reference gives such samples.
+struct MsJob {
+    const float* vals;       // [>= P, C]
+    const float* null_vals;  // [B, C]
+    const float* bg;         // [bg_batch, h, w, bgC] or null
+    int bg_shared, bgC, C, aa;
+    float* out;              // forward: [B, h, w, oC]
+    int oC;
+    const float* g_out;      // backward: [B, h, w, gS], gC leading channels have a gradient
+    int gS, gC;
+    float* g_vals;           // backward: [vals_rows, C]
+    float* g_null;           // backward: [B, C]
+    long long vals_rows;
+};
+
+struct MsGrid {
+    const int* inv;       // [B h w] point row of a block's shading sample, -1 = uncovered
+    const float4* cover;  // [B, h s, w s] full-resolution raster texels
+    int s, h, w, B;
+};
+
+// covered samples of block q (only the id channel's dword of each 16-byte texel)
+__device__ __forceinline__ int ms_block_count(const MsGrid& g, unsigned q) {
+    const unsigned hw = (unsigned)g.h * (unsigned)g.w, b = q / hw, rem = q - b * hw;
+    const unsigned y = rem / (unsigned)g.w, x = rem - y * (unsigned)g.w;
+    const long long W = (long long)g.w * g.s;
+    const float* t = reinterpret_cast<const float*>(g.cover + (((long long)b * g.h + y) * g.s * W + (long long)x * g.s)) + 3;
+    int k = 0;
+    for (int i = 0; i < g.s; ++i)
+        for (int j = 0; j < g.s; ++j) k += t[(i * W + j) * 4] > 0.f ? 1 : 0;
+    return k;
+}
+
+struct MsSample {
+    unsigned q;  // block (flat index on the shading grid)
+    int b;
+    bool covered;
+};
+
+__device__ __forceinline__ MsSample ms_sample(const MsGrid& g, unsigned p) {  // p: flat full-resolution sample
+    const unsigned W = (unsigned)g.w * (unsigned)g.s, HW = (unsigned)g.h * (unsigned)g.s * W;
+    const unsigned b = p / HW, rem = p - b * HW, y = rem / W, x = rem - y * W;
+    MsSample m;
+    m.q = (b * (unsigned)g.h + y / (unsigned)g.s) * (unsigned)g.w + x / (unsigned)g.s;
+    m.b = (int)b;
+    m.covered = reinterpret_cast<const float*>(g.cover + p)[3] > 0.f;
+    return m;
+}
+
+// channel c of pre(sample): [v, 1] covered, [bg, 0] not (row = inv of the sample's block)
+__device__ __forceinline__ float ms_pre(const MsJob& j, const MsSample& m, int row, int c, unsigned hw) {
+    if (m.covered) return c < j.C ? (row >= 0 ? j.vals[(long long)row * j.C + c] : j.null_vals[(long long)m.b * j.C + c]) : 1.f;
+    if (!j.bg || c >= j.bgC) return 0.f;
+    return j.bg[(long long)(j.bg_shared ? m.q % hw : m.q) * j.bgC + c];
+}
+
+// 256 blocks per work-group: count and point row of every block through LDS, then the blocks' oC floats as one contiguous run
+__global__ __launch_bounds__(256) void ms_compose_kernel(MsJob ja, MsJob jb, MsGrid g, unsigned n_blk) {
+    __shared__ int s_row[256], s_k[256];
+    const MsJob& job = blockIdx.y ? jb : ja;
+    const unsigned base = blockIdx.x * 256u, q = base + threadIdx.x, hw = (unsigned)g.h * (unsigned)g.w;
+    if (q < n_blk) {
+        s_k[threadIdx.x] = ms_block_count(g, q);
+        s_row[threadIdx.x] = g.inv[q];
+    }
+    __syncthreads();
+    const unsigned C1 = (unsigned)job.oC, nloc = min(256u, n_blk - base) * C1;
+    const int n = g.s * g.s;
+    float* o = job.out + (long long)base * C1;
+    for (unsigned j = threadIdx.x; j < nloc; j += 256u) {
+        const unsigned pl = j / C1;
+        const int c = (int)(j - pl * C1), k = s_k[pl], row = s_row[pl];
+        const unsigned qq = base + pl;
+        float v = 0.f, bgv = 0.f;
+        if (k > 0) v = c < job.C ? (row >= 0 ? job.vals[(long long)row * job.C + c] : job.null_vals[(long long)(qq / hw) * job.C + c]) : 1.f;
+        if (k < n && job.bg && c < job.bgC) bgv = job.bg[(long long)(job.bg_shared ? qq % hw : qq) * job.bgC + c];
+        o[j] = k == n ? v : (k == 0 ? bgv : ((float)k * v + (float)(n - k) * bgv) / (float)n);
+    }
+}
+
+__global__ __launch_bounds__(256) void ms_blend_kernel(MsJob ja, MsJob jb, MsGrid g, const AaRec* __restrict__ work, const int* __restrict__ count,
+                                                       int capacity) {
+    __shared__ int s_off[AA_SHARDS + 1];
+    const MsJob& job = blockIdx.y ? jb : ja;
+    const int n = aa_segment_offsets(count, capacity, s_off);
+    if (!job.aa) return;
+    const unsigned C1 = (unsigned)job.oC, total = (unsigned)n * C1, hw = (unsigned)g.h * (unsigned)g.w;
+    const unsigned W = (unsigned)g.w * (unsigned)g.s;
+    const float nn = (float)(g.s * g.s);
+    for (unsigned idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
+        const unsigned ru = idx / C1;
+        const int c = (int)(idx - ru * C1);
+        const AaRec rec = work[aa_record_slot((int)ru, s_off, capacity)];
+        const unsigned p0 = (unsigned)rec.pix0, p1 = p0 + ((rec.flags & 1) ? W : 1u);
+        const MsSample m0 = ms_sample(g, p0), m1 = ms_sample(g, p1);
+        const float d = ms_pre(job, m1, g.inv[m1.q], c, hw) - ms_pre(job, m0, g.inv[m0.q], c, hw);
+        const unsigned dst = rec.alpha > 0.f ? m0.q : m1.q;
+        if (d != 0.f) atomicAdd(job.out + (long long)dst * C1 + c, rec.alpha * d / nn);
+    }
+}
+
+// backward, one pass over the shading grid: g_vals[row] = (k / s^2) g_out[block] WRITTEN (a row belongs to exactly one block), the same
+// term of the blocks without a row added to the image's g_null; the rows past P zeroed
+__global__ __launch_bounds__(256) void ms_gather_kernel(MsJob ja, MsJob jb, MsGrid g, unsigned n_blk, long long P) {
+    __shared__ int s_row[256], s_k[256];
+    const MsJob& job = blockIdx.y ? jb : ja;
+    const int C = job.C, gC = job.gC, gS = job.gS, n = g.s * g.s;
+    {
+        const long long z1 = job.vals_rows * C, stride = (long long)gridDim.x * 256;
+        for (long long i = P * C + (long long)blockIdx.x * 256 + threadIdx.x; i < z1; i += stride) job.g_vals[i] = 0.f;
+    }
+    const unsigned base = blockIdx.x * 256u, q = base + threadIdx.x, hw = (unsigned)g.h * (unsigned)g.w;
+    if (base >= n_blk) return;
+    if (q < n_blk) {
+        s_k[threadIdx.x] = ms_block_count(g, q);
+        s_row[threadIdx.x] = g.inv[q];
+    }
+    __syncthreads();
+    const unsigned nloc = min(256u, n_blk - base) * (unsigned)C;
+    for (unsigned j = threadIdx.x; j < nloc; j += 256u) {
+        const unsigned pl = j / (unsigned)C;
+        const int c = (int)(j - pl * (unsigned)C), k = s_k[pl], row = s_row[pl];
+        if (k == 0) continue;  // (then the block has no row either)
+        const unsigned qq = base + pl;
+        const float go = c < gC ? job.g_out[(long long)qq * gS + c] : 0.f;
+        const float t = k == n ? go : ((float)k * go) / (float)n;
+        if (row >= 0) job.g_vals[(long long)row * C + c] = t;
+        else if (t != 0.f) atomicAdd(job.g_null + (long long)(qq / hw) * C + c, t);
+    }
+}
+
+// ca_bwd_kernel on the full-resolution records: colour adjoints to the point row (or the null row) of each sample's block, the edge
+// adjoint scaled by 1 / s^2
+__global__ __launch_bounds__(256) void ms_bwd_kernel(MsJob ja, MsJob jb, MsGrid g, const AaRec* __restrict__ work, const int* __restrict__ count,
+                                                     int capacity, const float4* __restrict__ clip, int clip_batch, const int* __restrict__ tri,
+                                                     int V, float* __restrict__ g_clip) {
+    __shared__ int s_off[AA_SHARDS + 1];
+    const MsJob& job = blockIdx.y ? jb : ja;
+    const int n = aa_segment_offsets(count, capacity, s_off);
+    if (!job.aa) return;
+    const int H = g.h * g.s, W = g.w * g.s;
+    const float xh = 0.5f * W, yh = 0.5f * H, nn = (float)(g.s * g.s);
+    const unsigned hw = (unsigned)g.h * (unsigned)g.w;
+    const int C = job.C, C1 = min(C + 1, job.gC), gS = job.gS;
+    const int sub = threadIdx.x & 31, groups = (gridDim.x * blockDim.x) >> 5;
+    for (int r = (blockIdx.x * blockDim.x + threadIdx.x) >> 5; r < n; r += groups) {
+        const AaRec rec = work[aa_record_slot(r, s_off, capacity)];
+        const int d = rec.flags & 1, di = (rec.flags >> 1) & 3;
+        const bool use1 = rec.flags & 8, clamped = rec.flags & 16;
+        const unsigned p0 = (unsigned)rec.pix0, p1 = p0 + (d ? (unsigned)W : 1u);
+        const MsSample m0 = ms_sample(g, p0), m1 = ms_sample(g, p1);
+        const int row0 = g.inv[m0.q], row1 = g.inv[m1.q];
+        const unsigned dst = rec.alpha > 0.f ? m0.q : m1.q;
+        float* t0 = row0 >= 0 ? job.g_vals + (long long)row0 * C : job.g_null + (long long)m0.b * C;
+        float* t1 = row1 >= 0 ? job.g_vals + (long long)row1 * C : job.g_null + (long long)m1.b * C;
+        float dd = 0.f;
+        for (int c = sub; c < C1; c += 32) {
+            const float gd = job.g_out[(long long)dst * gS + c] / nn;
+            if (gd != 0.f) {
+                if (c < C) {
+                    if (m1.covered) atomicAdd(t1 + c, rec.alpha * gd);
+                    if (m0.covered) atomicAdd(t0 + c, -rec.alpha * gd);
+                }
+                dd += gd * (ms_pre(job, m1, row1, c, hw) - ms_pre(job, m0, row0, c, hw));
+            }
+        }
+        dd = a3d_group_sum<32>(dd);  // (a record's 32 lanes are in the same trip)
+        if (sub != 0 || clamped || dd == 0.f) continue;
+        aa_edge_adjoint(rec, p0, d, di, use1, dd, clip, clip_batch, tri, V, H, W, xh, yh, g_clip);
+    }
+}
+
 extern "C" size_t a3d_aa_hash_bytes(int F) { return (size_t)aa_slots(F < 1 ? 1 : F) * (8 + 4 * AA_VALS); }
 
 extern "C" int a3d_aa_topology(const int32_t* tri, int F, int V, void* hash, int32_t* opp, a3d_stream_t stream) {
@@ -811,10 +992,85 @@ static int ca_ride(const a3d_aa_ride* r, const float* rast_override, void* work,
     return A3D_OK;
 }
 
+// ---- supersampled mode: the fields appended to a3d_ca_buffer are read only from a struct whose `size` covers them; a caller built against
+// the header without them (size = the offset of `spp`) gets the spp 1 compositor.  No header ever ended between the two sizes.
+static bool ca_size_ok(const a3d_ca_buffer* b) { return b->size == offsetof(a3d_ca_buffer, spp) || b->size >= sizeof(a3d_ca_buffer); }
+static int ca_spp(const a3d_ca_buffer* b) { return b->size >= sizeof(a3d_ca_buffer) ? b->spp : 0; }
+
+static MsJob ms_job(const a3d_ca_buffer* b, long long P) {
+    MsJob j;
+    j.vals = b->vals; j.null_vals = b->null_vals; j.bg = b->bg; j.bg_shared = b->bg_batch == 1; j.C = b->C; j.aa = b->aa != 0;
+    j.bgC = b->bg_channels > 0 ? b->bg_channels : b->C + 1;
+    j.out = b->out; j.oC = b->out_channels > 0 ? b->out_channels : b->C + 1;
+    j.g_out = b->g_out; j.gS = b->g_stride > 0 ? b->g_stride : b->C + 1; j.gC = b->g_channels > 0 ? b->g_channels : b->C + 1;
+    j.g_vals = b->g_vals; j.g_null = b->g_null; j.vals_rows = b->vals_rows > P ? b->vals_rows : P;
+    return j;
+}
+
+// what both directions check: the two buffers agree on the mode, the frame divides into s x s blocks, the per-buffer sources are there
+static int ms_check(const a3d_ca_buffer* first, const a3d_ca_buffer* second, const int32_t* inv, const void* work, const int32_t* count, int capacity,
+                    int B, int H, int W, bool spp1_only_options, MsGrid* g) {
+    const int s = ca_spp(first);
+    A3D_CHECK_ARG(!spp1_only_options);  // (the riding analysis and the on-the-fly shading are spp 1 only)
+    A3D_CHECK_ARG(s >= 2 && s <= 8 && (!second || ca_spp(second) == s));
+    A3D_CHECK_ARG(inv && work && count && capacity > 0 && B > 0 && H > 0 && W > 0 && H % s == 0 && W % s == 0);
+    A3D_CHECK_ARG((long long)B * H * W < 0x7FFFFFFFll);
+    for (const a3d_ca_buffer* b : {first, second}) {
+        if (!b) continue;
+        A3D_CHECK_ARG(b->C > 0 && b->C + 1 <= 4096 && ca_ext_ok(b) && b->cover_rast && b->null_vals && (!b->bg || b->bg_batch == 1 || b->bg_batch == B));
+        A3D_CHECK_ARG(b->cover_rast == first->cover_rast);
+    }
+    g->inv = inv; g->cover = (const float4*)first->cover_rast; g->s = s; g->h = H / s; g->w = W / s; g->B = B;
+    return A3D_OK;
+}
+
+static int ms_fwd(const a3d_ca_buffer* first, const a3d_ca_buffer* second, const int32_t* inv, const void* work, const int32_t* count, int capacity,
+                  int B, int H, int W, bool spp1_only_options, a3d_stream_t stream) {
+    MsGrid g;
+    if (int rc = ms_check(first, second, inv, work, count, capacity, B, H, W, spp1_only_options, &g)) return rc;
+    A3D_CHECK_ARG(first->out && (!second || second->out));
+    const MsJob ja = ms_job(first, 0), jb = second ? ms_job(second, 0) : ja;
+    const unsigned n_blk = (unsigned)B * (unsigned)g.h * (unsigned)g.w, rows = second ? 2u : 1u;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(ms_compose_kernel, dim3(a3d_div_up(n_blk, 256), rows), dim3(256), 0, s, ja, jb, g, n_blk);
+    A3D_LAUNCH_CHECK();
+    if (!ja.aa && !jb.aa) return A3D_OK;
+    hipLaunchKernelGGL(ms_blend_kernel, dim3(512, rows), dim3(256), 0, s, ja, jb, g, (const AaRec*)work, count, capacity);
+    A3D_LAUNCH_CHECK();
+    return A3D_OK;
+}
+
+static int ms_bwd(const a3d_ca_buffer* first, const a3d_ca_buffer* second, int64_t P, const int32_t* inv, const void* work, const int32_t* count,
+                  int capacity, const float* clip, int clip_batch, const int32_t* tri, int B, int V, int F, int H, int W, float* g_clip,
+                  bool spp1_only_options, a3d_stream_t stream) {
+    MsGrid g;
+    if (int rc = ms_check(first, second, inv, work, count, capacity, B, H, W, spp1_only_options, &g)) return rc;
+    A3D_CHECK_ARG(clip && g_clip && V > 0 && P >= 0 && (clip_batch == 1 || clip_batch == B));
+    hipStream_t s = (hipStream_t)stream;
+    for (const a3d_ca_buffer* b : {first, second}) {
+        if (!b) continue;
+        A3D_CHECK_ARG(b->g_out && b->g_null && (b->g_vals || (P == 0 && b->vals_rows == 0)) && (P == 0 || b->vals));
+        A3D_HIP(hipMemsetAsync(b->g_null, 0, sizeof(float) * (size_t)B * b->C, s));
+    }
+    A3D_HIP(hipMemsetAsync(g_clip, 0, sizeof(float) * 4 * (size_t)clip_batch * V, s));
+    const MsJob ja = ms_job(first, (long long)P), jb = second ? ms_job(second, (long long)P) : ja;
+    const unsigned n_blk = (unsigned)B * (unsigned)g.h * (unsigned)g.w, rows = second ? 2u : 1u;
+    hipLaunchKernelGGL(ms_gather_kernel, dim3(a3d_div_up(n_blk, 256), rows), dim3(256), 0, s, ja, jb, g, n_blk, (long long)P);
+    A3D_LAUNCH_CHECK();
+    if (F == 0 || (!ja.aa && !jb.aa)) return A3D_OK;
+    A3D_CHECK_ARG(tri);
+    hipLaunchKernelGGL(ms_bwd_kernel, dim3(1024, rows), dim3(256), 0, s, ja, jb, g, (const AaRec*)work, count, capacity, (const float4*)clip,
+                       clip_batch, tri, V, g_clip);
+    A3D_LAUNCH_CHECK();
+    return A3D_OK;
+}
+
 extern "C" int a3d_composite_aa_fwd(const a3d_ca_buffer* first, const a3d_ca_buffer* second_or_null, const int32_t* inv, void* work,
                                     int32_t* count, int capacity, int B, int H, int W, const a3d_aa_ride* analyze_or_null,
                                     const a3d_ca_shade* shade_or_null, a3d_stream_t stream) {
-    A3D_CHECK_ARG(first && first->size >= sizeof(a3d_ca_buffer) && (!second_or_null || second_or_null->size >= sizeof(a3d_ca_buffer)));
+    A3D_CHECK_ARG(first && ca_size_ok(first) && (!second_or_null || ca_size_ok(second_or_null)));
+    if (ca_spp(first) > 1 || (second_or_null && ca_spp(second_or_null) > 1))
+        return ms_fwd(first, second_or_null, inv, work, count, capacity, B, H, W, analyze_or_null != nullptr || shade_or_null != nullptr, stream);
     const float *vals = first->vals, *bg_or_null = first->bg, *vals2_or_null = second_or_null ? second_or_null->vals : nullptr;
     const float* bg2_or_null = second_or_null ? second_or_null->bg : nullptr;
     const int C = first->C, bg_batch = first->bg_batch, C2 = second_or_null ? second_or_null->C : 0, bg2_batch = second_or_null ? second_or_null->bg_batch : 0;
@@ -849,7 +1105,9 @@ extern "C" int a3d_composite_aa_bwd(const a3d_ca_buffer* first, const a3d_ca_buf
                                     const int32_t* inv, const void* work, const int32_t* count, int capacity, const float* clip, int clip_batch,
                                     const int32_t* tri, int B, int V, int F, int H, int W, float* g_clip, const a3d_ca_shade* shade_or_null,
                                     a3d_stream_t stream) {
-    A3D_CHECK_ARG(first && first->size >= sizeof(a3d_ca_buffer) && (!second_or_null || second_or_null->size >= sizeof(a3d_ca_buffer)));
+    A3D_CHECK_ARG(first && ca_size_ok(first) && (!second_or_null || ca_size_ok(second_or_null)));
+    if (ca_spp(first) > 1 || (second_or_null && ca_spp(second_or_null) > 1))
+        return ms_bwd(first, second_or_null, P, inv, work, count, capacity, clip, clip_batch, tri, B, V, F, H, W, g_clip, shade_or_null != nullptr, stream);
     const float *g_out = first->g_out, *vals = first->vals, *bg_or_null = first->bg;
     const int C = first->C, bg_batch = first->bg_batch;
     float* g_vals = first->g_vals;

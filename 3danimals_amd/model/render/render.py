@@ -41,6 +41,11 @@ DEFER_ANALYSIS = os.environ.get("A3D_DEFER_ANALYSIS", "1") != "0"  # the silhoue
 FUSED_FLOW_DELTA = os.environ.get("A3D_FUSED_FLOW_DELTA", "1") != "0"  # 'flow': the per-vertex motion to the next frame as one launch each way (ops.flow_delta)
 FUSED_MASK_RENDER = True  # a render without material, light and feature field whose only mode is 'shaded' skips the G-buffer: ops.mask_antialias
 FUSED_SHADING = True
+# spp > 1 with msaa: shade the covered shading samples only, composite + antialias + average in the compositor's supersampled mode
+# (_render_mesh_msaa; the reference's result also where a block's shading sample is uncovered, which the generic path does not give).
+# OFF unless A3D_FUSED_MSAA=1: 2.1x / 1.8x on the 10-frame training shape, but the forward of a single 256 x 256 image is launch-bound and
+# the extra shade() call for the null rows makes it 0.85x ("Supersampled rendering"; tools/bench_msaa.py)
+FUSED_MSAA = os.environ.get("A3D_FUSED_MSAA", "0") not in ("0", "")
 ALIAS_POSITIONS = os.environ.get("A3D_ALIAS_POSITIONS", "1") != "0"  # the clip transform's node feeds the G-buffer's position attribute too (one accumulation launch less)
 FIELD_INPUTS_FROM_GBUFFER = os.environ.get("A3D_FIELD_INPUTS", "1") != "0"  # the fields' padded input rows + image index written by the G-buffer launch (round 6)
 SHADE_IN_COMPOSITOR = os.environ.get("A3D_SHADE_IN_COMPOSITOR", "1") != "0"  # no a3d_shade_fwd launch when only the composited colour reads its output  # shading normal + camera normal + directional light of the covered pixels in one HIP kernel (csrc/shade.hip)
@@ -478,6 +483,13 @@ def render_mesh(ctx, mesh, mtx_in, w2c, view_pos, material, lgt, resolution, spp
     if num_layers != 1:  # depth peeling: never used by a config (AnimalModel.py:247); the general, dense path
         return _render_mesh_layers(mesh, clip_f, tri, w2c, view_pos, material, lgt, resolution, spp, num_layers, msaa, background, bsdf, feat,
                                    render_modes, prior_mesh, two_sided_shading, dino_net, class_vector, delta_xy)
+    if (FUSED_MSAA and msaa and 2 <= spp <= 8 and FUSED_GBUFFER and FUSED_COVER_GBUFFER and FUSED_COMPOSITE and SHADE_COVERED_ONLY and PIXEL_TILE == 8
+            and clip_f.is_cuda and mesh.v_pos.dtype == torch.float32 and v_pos_clip.dtype == torch.float32 and not torch.is_autocast_enabled()
+            and not ({"tangent", "depth"} & set(render_modes)) and clip_f.shape[0] == mesh.v_pos.shape[0]
+            and mesh.t_nrm_idx.data_ptr() == mesh.t_pos_idx.data_ptr() and resolution[0] % 8 == 0 and resolution[1] % 8 == 0
+            and (delta_xy is None or delta_xy.shape[-1] <= 3) and (background is None or not background.requires_grad)):
+        return _render_mesh_msaa(mesh, clip_f, tri, w2c, view_pos, material, lgt, resolution, spp, background, bsdf, feat, render_modes, prior_mesh,
+                                 two_sided_shading, dino_net, class_vector, delta_xy)
     job = mesh.normals_job() if hasattr(mesh, "normals_job") else None  # pending auto_normals: extra work-groups of the triangle launch
     mask_only = (FUSED_MASK_RENDER and FUSED_COMPOSITE and material is None and lgt is None and dino_net is None and list(render_modes) == ["shaded"]
                  and spp == 1 and (background is None or not background.requires_grad))
@@ -607,6 +619,77 @@ def render_mesh(ctx, mesh, mtx_in, w2c, view_pos, material, lgt, resolution, spp
             out = out[..., :-1]
         out_buffers.append(out.permute(0, 3, 1, 2))
     return out_buffers
+
+
+_msaa_shift = {}
+
+
+def _render_mesh_msaa(mesh, clip_f, tri, w2c, view_pos, material, lgt, resolution, spp, background, bsdf, feat, render_modes, prior_mesh,
+                      two_sided_shading, dino_net, class_vector, delta_xy):
+    """render_mesh(spp = s > 1, msaa = True, num_layers = 1) with the reference's semantics (render.py:170-171, 217-219, 258-268, 318) and
+    none of its full-resolution images.  The reference shades at the nearest-minified raster -- texel (y s, x s) of every s x s block -- ALL
+    low-resolution pixels with alpha 1, replicates the result over the block, composites with the full-resolution coverage, antialiases
+    at full resolution and averages the blocks.  Here the covered shading samples are shaded as a point list (the spp 1 kernels on
+    rast[:, ::s, ::s]), a block whose shading sample is uncovered takes the image's `null` row -- shade() on all-zero attributes, which is
+    what the reference evaluates there -- and ops.msaa_composite_antialias does the rest on the shading grid."""
+    s, (h, w) = int(spp), resolution
+    dev = clip_f.device
+    job = mesh.normals_job() if hasattr(mesh, "normals_job") else None
+    rast = ops.rasterize(clip_f, tri, [h * s, w * s], normals_job=job)
+    if job is not None:
+        mesh.take_normals(job, graph_pos=None)
+    LAST_RAST[0] = rast.detach()
+    LAST_POINTS[0] = None
+    rast_s = rast.detach()[:, ::s, ::s].contiguous()
+    # the G-buffer's backward re-derives the centre of shading pixel x as (x + 0.5) 2 / w - 1; the sample it was taken at, full-resolution
+    # texel x s, lies (1 - 1/s) / w to the left of that: the geometry is handed over shifted by as much (autograd carries it back to clip)
+    key = (dev, s, h, w)
+    if key not in _msaa_shift:  # (kept per shape: building it is a host-to-device copy, which blocks)
+        _msaa_shift[key] = torch.tensor([(1.0 - 1.0 / s) / w, (1.0 - 1.0 / s) / h, 0.0, 0.0], dtype=torch.float32, device=dev)
+    clip_s = torch.addcmul(clip_f, clip_f[..., 3:4], _msaa_shift[key])
+    rendered = render_layer(rast_s, None, mesh, w2c, view_pos, material, lgt, resolution, 1, True, bsdf, feat=feat, render_modes=render_modes,
+                            prior_mesh=prior_mesh, two_sided_shading=two_sided_shading, delta_xy=delta_xy, dino_net=dino_net,
+                            class_vector=class_vector, clip=clip_s, sparse=True)
+    assert isinstance(rendered, SparseBuffers) and rendered.inv is not None
+    B = rast.shape[0]
+    zero = torch.zeros(B, 1, 1, 3, dtype=torch.float32, device=dev)
+    flow0 = torch.zeros(B, 1, 1, rendered.peek("flow").shape[-1], dtype=torch.float32, device=dev) if "flow" in render_modes else None
+    null = shade(zero, zero, zero, None, zero, w2c, view_pos, lgt, material, bsdf, feat=feat, render_modes=render_modes,
+                 two_sided_shading=two_sided_shading, delta_xy_interp=flow0, dino_net=dino_net if "dino_pred" in render_modes else None,
+                 class_vector=class_vector, cover=None)
+    analysis = ops.AAAnalysis(rast, clip_f, ops.aa_topology(ops.tri_int32(tri), clip_f.shape[1]))
+
+    def bg_of(k):
+        if background is None or k not in ("shaded", "geo_normal", "shading"):
+            return None
+        # ('shading': the last two channels of the background with its zero alpha appended, render.py:254-256, 307-308)
+        return torch.cat((background[..., 2:3], torch.zeros_like(background[..., 0:1])), dim=-1) if k == "shading" else background
+
+    keep_of = {"kd": 3, "ks": 3, "normal": 3, "geo_normal": 3, "shading": 1, "flow": 2, "dino_pred": -1}
+    vals_of = lambda k: rendered.peek(k) if dict.__contains__(rendered, k) else rendered[k]
+    null_of = lambda k: null[k][:, 0, 0, :-1].expand(B, -1)
+
+    def keep(k, vals):
+        n = keep_of.get(k)
+        return None if n is None else (vals.shape[-1] if n == -1 else n)
+
+    keys = [k for k in dict.fromkeys(render_modes) if k in rendered]
+    done = {}
+    for aa in (True, False):
+        group = [k for k in keys if (k in ANTIALIASED_MODES) == aa]
+        for i in range(0, len(group), 2):
+            ka, kb = group[i], (group[i + 1] if i + 1 < len(group) else None)
+            va, vb = vals_of(ka), (None if kb is None else vals_of(kb))
+            res = ops.msaa_composite_antialias(va, null_of(ka), rendered.pix, rendered.inv, rast, bg_of(ka), clip_f, analysis, s, antialias=aa,
+                                               vals2=vb, null_vals2=None if kb is None else null_of(kb), background2=None if kb is None else bg_of(kb),
+                                               keep=keep(ka, va), keep2=None if kb is None else keep(kb, vb))
+            if kb is None:
+                done[ka] = res
+            else:
+                done[ka], done[kb] = res
+    if LAST_POINTS[0] is not None:
+        LAST_POINTS[0]["clip"] = clip_f.detach()
+    return [done[k].permute(0, 3, 1, 2) if k in done else None for k in render_modes]
 
 
 def _slice_mode(key, out):

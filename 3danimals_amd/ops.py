@@ -1869,6 +1869,97 @@ def shade_composite_antialias(recipe, pix, inv, background, clip, analysis, vals
     return o1 if vals2 is None else (o1, o2)
 
 
+class _MsaaCompositeAntialias(torch.autograd.Function):
+    """The compositor in supersampled mode (a3d_ca_buffer.spp > 1, csrc/antialias.hip): one or two buffers given as rows on the SHADING grid
+    [B,h,w], composited with the full-resolution coverage, antialiased with the full-resolution crossing records and averaged per
+    s x s block -- without any full-resolution image.  Gradients: the rows, the per-image null rows, the clip positions."""
+
+    @staticmethod
+    def forward(ctx, vals, null_vals, vals2, null_vals2, clip, pix, inv, rast_full, bg, bg2, analysis, spp, aa, keep, keep2):
+        require_device(vals, null_vals, vals2, null_vals2, pix, inv, rast_full, what="msaa_composite_antialias")
+        a = analysis.ensure()  # (the riding analysis is an spp 1 optimisation)
+        s = int(spp)
+        assert 2 <= s <= 8 and a.H % s == 0 and a.W % s == 0
+        h, w = a.H // s, a.W // s
+        P = pix.shape[0]
+        rast_full = f32c(rast_full.detach())
+        assert rast_full.shape == (a.B, a.H, a.W, 4) and pix.dtype == torch.int64 and inv.shape == (a.B * h * w,) and inv.dtype == torch.int32
+        dev = pix.device
+
+        def prep(v, nv, g, k):
+            if v is None:
+                return None, None, None, 0, None
+            v, nv = f32c(v), f32c(nv)
+            C = v.shape[1]
+            assert v.shape[0] >= P and nv.shape == (a.B, C)
+            if g is not None:
+                g = f32c(g)
+                assert g.shape[1:3] == (h, w) and g.shape[3] <= C + 1 and g.shape[0] in (1, a.B)
+            k = C + 1 if k is None else int(k)
+            assert 1 <= k <= C + 1
+            return v, nv, g, C, torch.empty((a.B, h, w, k), dtype=torch.float32, device=dev)
+
+        vals, null_vals, bg, C, out = prep(vals, null_vals, bg, keep)
+        vals2, null_vals2, bg2, C2, out2 = prep(vals2, null_vals2, bg2, keep2)
+        tag = f"[spp{s}][C{C + 1}]" if vals2 is None else f"[spp{s}][C{C + 1}+C{C2 + 1}]"
+        buf = lambda v, nv, c, g, o: _lib.CaBuffer(size=ctypes.sizeof(_lib.CaBuffer), C=c, vals=ptr(v), bg=ptr(g), out=ptr(o), bg_batch=0 if g is None else g.shape[0],
+                                                   bg_channels=0 if g is None else g.shape[3], out_channels=o.shape[3], spp=s, aa=int(bool(aa)),
+                                                   cover_rast=ptr(rast_full), null_vals=ptr(nv))
+        first, second = buf(vals, null_vals, C, bg, out), (buf(vals2, null_vals2, C2, bg2, out2) if vals2 is not None else None)
+        call("a3d_composite_aa_fwd", ctypes.addressof(first), None if second is None else ctypes.addressof(second), ptr(inv), ptr(a.work), ptr(a.count),
+             a.capacity, a.B, a.H, a.W, None, None, stream(), tag=tag)
+        ctx.save_for_backward(vals, null_vals, vals2, null_vals2, pix, inv, rast_full, bg, bg2)
+        ctx.analysis, ctx.tag, ctx.spp, ctx.aa = a, tag, s, int(bool(aa))
+        ctx.set_materialize_grads(False)
+        return out, out2
+
+    @staticmethod
+    def backward(ctx, g_out, g_out2=None):
+        vals, null_vals, vals2, null_vals2, pix, inv, rast_full, bg, bg2 = ctx.saved_tensors
+        a, s = ctx.analysis, ctx.spp
+        h, w = a.H // s, a.W // s
+        P, dev = pix.shape[0], pix.device
+        two = vals2 is not None
+        C, C2 = vals.shape[1], (vals2.shape[1] if two else 0)
+        if g_out is None:
+            g_out = torch.zeros((a.B, h, w, C + 1), dtype=torch.float32, device=dev)
+        if two and g_out2 is None:
+            g_out2 = torch.zeros((a.B, h, w, C2 + 1), dtype=torch.float32, device=dev)
+        g_out, gs, gc = _image_gradient_in_place(g_out, h, w)
+        if two:
+            g_out2, gs2, gc2 = _image_gradient_in_place(g_out2, h, w)
+        g_vals, g_null = torch.empty_like(vals), torch.empty_like(null_vals)
+        g_vals2, g_null2 = (torch.empty_like(vals2), torch.empty_like(null_vals2)) if two else (None, None)
+        g_clip = torch.empty_like(a.clip)
+        buf = lambda v, nv, c, g, go, gst, gch, gv, gn: _lib.CaBuffer(size=ctypes.sizeof(_lib.CaBuffer), C=c, vals=ptr(v), bg=ptr(g), g_out=ptr(go), g_vals=ptr(gv),
+                                                                      bg_batch=0 if g is None else g.shape[0], bg_channels=0 if g is None else g.shape[3],
+                                                                      g_stride=gst, g_channels=gch, vals_rows=v.shape[0], spp=s, aa=ctx.aa,
+                                                                      cover_rast=ptr(rast_full), null_vals=ptr(nv), g_null=ptr(gn))
+        first = buf(vals, null_vals, C, bg, g_out, gs, gc, g_vals, g_null)
+        second = buf(vals2, null_vals2, C2, bg2, g_out2, gs2, gc2, g_vals2, g_null2) if two else None
+        call("a3d_composite_aa_bwd", ctypes.addressof(first), None if second is None else ctypes.addressof(second), ptr(pix), P, ptr(inv), ptr(a.work),
+             ptr(a.count), a.capacity, ptr(a.clip), a.clip.shape[0], ptr(a.topo.tri), a.B, a.clip.shape[1], a.topo.tri.shape[0], a.H, a.W, ptr(g_clip),
+             None, stream(), tag=ctx.tag)
+        return (g_vals, g_null, g_vals2, g_null2, g_clip) + (None,) * 10
+
+
+def msaa_composite_antialias(vals, null_vals, pix, inv, rast_full, background, clip, analysis, spp, antialias=True, vals2=None, null_vals2=None,
+                             background2=None, keep=None, keep2=None):
+    """render_mesh(spp = s > 1, msaa = True) of the reference behind the shading (render.py:217-219, 258-268, 318) for a buffer given as
+    rows ``vals`` [>= P,C] at the covered texels ``pix`` of the shading-sample raster rast_full[:, ::s, ::s] (``inv`` [B*h*w] its pixel ->
+    row map) and ``null_vals`` [B,C], the value of a shading sample that is NOT covered: avg_pool(antialias(lerp(background, up([v, 1]),
+    coverage of ``rast_full``))) as [B,h,w,C+1].  ``analysis``: the AAAnalysis of (rast_full, clip), full resolution.  ``background``
+    [1|B,h,w,<= C+1] on the shading grid (its nearest up-scale is what the reference composites over) or None; no gradient.
+    ``antialias`` False: composite and average only.  A second buffer and ``keep`` / ``keep2`` as in composite_antialias."""
+    assert background is None or not background.requires_grad
+    assert background2 is None or not background2.requires_grad
+    if clip.dim() == 2:
+        clip = clip[None]
+    o1, o2 = _MsaaCompositeAntialias.apply(vals, null_vals, vals2, null_vals2, clip, pix, inv, rast_full, background, background2, analysis, spp,
+                                           antialias, keep, keep2)
+    return o1 if vals2 is None else (o1, o2)
+
+
 def antialias(color, rast, clip, tri, analysis=None):
     """dr.antialias semantics; pass ``analysis`` (AAAnalysis) to share the geometry pass between buffers."""
     if clip.dim() == 2:

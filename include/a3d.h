@@ -602,6 +602,19 @@ typedef struct a3d_ca_buffer {
     int32_t out_channels;/* forward: leading channels of the composited image that are MATERIALISED: out is [B,H,W,out_channels] (default C+1).
                           * A mode whose alpha channel the caller cuts off anyway (dino_pred, flow: render.py:326-331) is written without it. */
     int64_t vals_rows;   /* backward: rows of g_vals to write (default P; >= P: the rows past P -- padding rows of a field's point list -- zero) */
+    /* Supersampled mode.  Appended without a version bump (a3d_version() stays 405) and size-gated: these fields are read only when `size`
+     * covers them; a caller whose `size` ends at vals_rows gets the behaviour above, bit for bit.  With spp = s in 2..8 the call's H, W and
+     * the crossing records (work / count / capacity) are those of the FULL-resolution frame, while inv, bg, out, g_out and pix live on the
+     * shading grid h = H / s, w = W / s (inv = the point row of texel (y s, x s), the reference's nearest-minified raster).  A block with
+     * k covered samples is (k [v, 1] + (s^2 - k) [bg, 0]) / s^2 with v = its point row, or null_vals[b] when its shading sample is
+     * uncovered; every record adds alpha (pre(p1) - pre(p0)) / s^2 to the block of its destination sample (pre = [v, 1] of a covered
+     * sample's block, [bg, 0] of an uncovered one's): render.py:217-219, 258-268, 318 without any full-resolution image.  Both buffers of
+     * a call carry the same spp and cover_rast; analyze_or_null and shade_or_null must be NULL (A3D_EINVAL otherwise). */
+    int32_t spp;         /* 0 or 1: the behaviour above */
+    int32_t aa;          /* spp > 1: 0 = composite and average only (the modes the reference does not antialias: kd, ks, normal, geo_normal) */
+    const float* cover_rast; /* [B,H,W,4] full-resolution raster texels (covered <=> id channel > 0) */
+    const float* null_vals;  /* [B,C] value of a block whose shading sample is uncovered */
+    float* g_null;       /* backward: [B,C], fully written */
 } a3d_ca_buffer;
 int a3d_composite_aa_fwd(const a3d_ca_buffer* first, const a3d_ca_buffer* second_or_null, const int32_t* inv, void* work, int32_t* count,
                          int capacity, int B, int H, int W, const a3d_aa_ride* analyze_or_null, const a3d_ca_shade* shade_or_null,
