@@ -42,7 +42,9 @@ class CaBuffer(ctypes.Structure):
 
 class CaShade(ctypes.Structure):
     _fields_ = [("size", ctypes.c_uint32), ("kd_stride", ctypes.c_int32), ("gb", _p), ("par", _p), ("kd", _p), ("clear", _p),
-                ("n_clear", ctypes.c_int32), ("two_sided", ctypes.c_int32), ("params", _p), ("shaded_out", _p)]
+                ("n_clear", ctypes.c_int32), ("two_sided", ctypes.c_int32), ("params", _p), ("shaded_out", _p),
+                ("depth_gb", _p), ("depth_w2c_row", _p), ("depth_w2c_stride", ctypes.c_int64), ("depth_pix", _p), ("depth_rows", ctypes.c_int64),
+                ("depth_state", _p), ("depth_out", _p), ("g_depth_gb", _p), ("g_depth_slots", _p)]
 
 
 class ShadeParams(ctypes.Structure):

@@ -218,6 +218,25 @@ __device__ __forceinline__ T a3d_group_sum(T v) {
 }
 __device__ __forceinline__ float a3d_wave_sum(float v) { return a3d_group_sum<64>(v); }
 
+// minimum / maximum over the wave, in every lane of it (the same butterfly; neither depends on the order).  Floats go through
+// a3d_ordered_key first: an unsigned key that orders like the float (negative values and -0 < +0 included), so that integer atomicMin /
+// atomicMax can finish across waves what these start.  NaN is not ordered: callers keep it out.
+__device__ __forceinline__ unsigned a3d_wave_min(unsigned v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, (unsigned)__shfl_xor((int)v, o, 64));
+    return v;
+}
+__device__ __forceinline__ unsigned a3d_wave_max(unsigned v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, o, 64));
+    return v;
+}
+__device__ __forceinline__ unsigned a3d_ordered_key(float f) {
+    const unsigned u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float a3d_ordered_value(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
+
 // sum over the work-group, in every thread, in a fixed order: the butterfly per wave, then red[0] + red[1] + .. + red[WAVES-1] from the
 // left.  (Starting from red[0] and not from zero: a sum whose terms are all -0 stays -0.)  Two barriers -- one BEFORE red is written,
 // so the WAVES words of red may be handed to the next call right away, and one behind.

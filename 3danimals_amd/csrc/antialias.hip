@@ -417,6 +417,9 @@ struct CaJob {
     int gHW;             // backward, a3d_mask_aa_bwd only: > 0 = the gradient is channels-FIRST, [B,gS,H,W] with gHW = H W (0: channels-last)
     float* g_vals;       // backward: [vals_rows >= P, C], rows past P zero
     long long vals_rows;
+    float* g_slots;      // backward, C == 1 only (the depth source): [P,4] the blend adjoints of a point by its role in the record -- first / second
+                         // pixel of a right / lower pair, at most one record each -- as plain stores instead of float atomics on g_vals: their
+                         // sum in a fixed order (dp_bwd_kernel) repeats bit for bit
 };
 
 // 256 pixels per work-group: the pixel -> source map goes through LDS once, then the work-group writes the pixels' C+1 floats as one
@@ -644,7 +647,10 @@ __global__ __launch_bounds__(256) void ca_bwd_kernel(CaJob ja, CaJob jb, const A
             // (channels-first: pixel dst = image b, pixel q  ->  (b gS + c) gHW + q = dst + b (gS - 1) gHW + c gHW)
             const float gd = job.gHW ? g_out[(long long)dst + ((long long)(dst / (unsigned)job.gHW) * (gS - 1) + c) * job.gHW] : g_out[(long long)dst * gS + c];
             if (gd != 0.f) {
-                if (c < C && g_vals) {  // (a constant colour has no adjoint)
+                if (c < C && job.g_slots) {
+                    if (q1 >= 0) job.g_slots[4ll * q1 + 2 + d] = rec.alpha * gd;
+                    if (q0 >= 0) job.g_slots[4ll * q0 + d] = -rec.alpha * gd;
+                } else if (c < C && g_vals) {  // (a constant colour has no adjoint)
                     if (q1 >= 0) atomicAdd(g_vals + (long long)q1 * C + c, rec.alpha * gd);
                     if (q0 >= 0) atomicAdd(g_vals + (long long)q0 * C + c, -rec.alpha * gd);
                 }
@@ -837,6 +843,153 @@ __global__ __launch_bounds__(256) void ms_bwd_kernel(MsJob ja, MsJob jb, MsGrid 
     }
 }
 
+// ---- the 'depth' render mode on the point list (a3d_ca_shade.depth_*) --------------------------------------------------------------------
+// The reference computes camera-space z of the interpolated position for EVERY pixel of the frame (an uncovered pixel has position 0, so
+// z = row[3]), normalises with the per-image amin / amax and composites the result over zeros (render.py:98-104, 258-268): only the
+// covered pixels' values survive, and the uncovered ones matter through the range alone.  Here: a segmented min / max over the point list
+// (point -> image = pix / (H W), non-decreasing), row[3] joining the range of an image that has an uncovered pixel, then one value per point.
+// z comes from dp_z in every kernel, forward and backward: the same bits, so "attains the extreme" is z == m.
+#define DP_WORDS 8  // words of depth_state per image: min key, max key, points, points attaining m, points attaining M
+#define DP_BWD_THREADS 1024
+
+struct DpJob {
+    const float* gb;       // [P,12]
+    const float* row;      // row 2 of image 0's w2c
+    long long stride;      // floats between two images' rows
+    const long long* pix;  // [P]
+    long long P;
+    unsigned hw;
+    int B;
+    unsigned* state;       // [B, DP_WORDS]
+    float* out;            // [P]
+};
+
+__device__ __forceinline__ float dp_z(const float* __restrict__ g, const float* __restrict__ w) {
+    return __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(g[0], w[0]), __fmul_rn(g[1], w[1])), __fmul_rn(g[2], w[2])), w[3]);
+}
+
+struct DpRange { float m, M; };
+__device__ __forceinline__ DpRange dp_range(const unsigned* __restrict__ st, float t, unsigned hw) {
+    DpRange r;
+    r.m = a3d_ordered_value(st[0]);
+    r.M = a3d_ordered_value(st[1]);
+    if (st[2] < hw) { r.m = fminf(r.m, t); r.M = fmaxf(r.M, t); }  // (an uncovered pixel exists: its z is in the range)
+    return r;
+}
+
+__global__ __launch_bounds__(256) void dp_init_kernel(unsigned* __restrict__ state, int B) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * DP_WORDS) return;
+    state[i] = (i % DP_WORDS) == 0 ? 0xFFFFFFFFu : 0u;
+}
+
+// One point per lane.  A wave whose points all belong to one image (the rule) reduces with the butterflies and sends three atomics; a wave
+// that holds the end of one image and the start of the next sends its lanes' own.  Integer min / max / add: no order, the same bits every run.
+__global__ __launch_bounds__(256) void dp_range_kernel(DpJob j) {
+    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+    const bool on = p < j.P;
+    const long long pc = on ? p : j.P - 1;  // (the lanes past the end repeat the last point: the same extremes; they are not counted)
+    const unsigned b = (unsigned)((unsigned long long)j.pix[pc] / j.hw);
+    const bool ok = b < (unsigned)j.B;  // (a pixel index outside the frame is not a point of any image: skipped, the whole wave stays in step)
+    const unsigned bi = ok ? b : 0u;
+    const unsigned k = a3d_ordered_key(dp_z(j.gb + 12 * pc, j.row + (long long)bi * j.stride));
+    const unsigned b0 = (unsigned)__shfl((int)b, 0);
+    unsigned* st = j.state + (long long)bi * DP_WORDS;
+    if (__all(ok && b == b0)) {
+        const unsigned kmin = a3d_wave_min(k), kmax = a3d_wave_max(k);
+        const int n = __popcll(__ballot(on));
+        if (a3d_lane_id() == 0) {
+            atomicMin(st, kmin);
+            atomicMax(st + 1, kmax);
+            atomicAdd(st + 2, (unsigned)n);
+        }
+    } else if (on && ok) {
+        atomicMin(st, k);
+        atomicMax(st + 1, k);
+        atomicAdd(st + 2, 1u);
+    }
+}
+
+__global__ __launch_bounds__(256) void dp_norm_kernel(DpJob j) {
+    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= j.P) return;
+    const unsigned b = (unsigned)((unsigned long long)j.pix[p] / j.hw);
+    if (b >= (unsigned)j.B) { j.out[p] = 0.f; return; }
+    const float* w = j.row + (long long)b * j.stride;
+    unsigned* st = j.state + (long long)b * DP_WORDS;
+    const float z = dp_z(j.gb + 12 * p, w);
+    const DpRange r = dp_range(st, w[3], j.hw);
+    j.out[p] = (z - r.m) / (r.M - r.m);
+    if (z == r.m) atomicAdd(st + 3, 1u);  // (one point per image unless values tie)
+    if (z == r.M) atomicAdd(st + 4, 1u);
+}
+
+// One work-group per image: its points are the run [sum of the earlier images' counts, + its own count) of the list.  The two sums over the
+// run -- d(loss)/dm and d(loss)/dM before the factor 1 / (M - m) -- in double, every thread over its strided share and the work-group in the
+// fixed order of a3d_block_sum (the convention of sdfreg.hip: no float atomics); then the rows.
+// d(loss)/d(depth row p): what the compositor's gather wrote plus the four blend adjoints by role, always in this order
+__device__ __forceinline__ float dp_g(const float* __restrict__ g_d, const float* __restrict__ g_slots, long long p) {
+    const float4 s = reinterpret_cast<const float4*>(g_slots)[p];
+    return (((g_d[p] + s.x) + s.y) + s.z) + s.w;
+}
+
+__global__ __launch_bounds__(DP_BWD_THREADS) void dp_bwd_kernel(DpJob j, const float* __restrict__ g_d, const float* __restrict__ g_slots,
+                                                                float* __restrict__ g_gb) {
+    __shared__ long long s_redl[DP_BWD_THREADS / 64];
+    __shared__ double s_red[DP_BWD_THREADS / 64];
+    const int b = blockIdx.x;
+    const unsigned* st = j.state + (long long)b * DP_WORDS;
+    long long before = 0;
+    for (int i = threadIdx.x; i < b; i += DP_BWD_THREADS) before += j.state[(long long)i * DP_WORDS + 2];
+    const long long start = a3d_block_sum<DP_BWD_THREADS / 64>(before, s_redl);
+    const long long n = st[2];
+    if (n == 0 || start + n > j.P) return;  // (no point, or a state that is not this list's)
+    const float* w = j.row + (long long)b * j.stride;
+    const float t = w[3];
+    const DpRange r = dp_range(st, t, j.hw);
+    const float rinv = 1.f / (r.M - r.m);
+    double sm = 0.0, sM = 0.0;
+    for (long long p = start + threadIdx.x; p < start + n; p += DP_BWD_THREADS) {
+        const double g = dp_g(g_d, g_slots, p), d = j.out[p];
+        sm += g * (d - 1.0);
+        sM += g * d;
+    }
+    sm = a3d_block_sum<DP_BWD_THREADS / 64>(sm, s_red);
+    sM = a3d_block_sum<DP_BWD_THREADS / 64>(sM, s_red);
+    // every pixel that attains an extreme takes an equal share of its gradient (torch.amin / amax); the uncovered ones' is w2c's: dropped
+    const bool open = (unsigned long long)n < j.hw;
+    const double n_m = (double)st[3] + ((open && t == r.m) ? (double)(j.hw - n) : 0.0);
+    const double n_M = (double)st[4] + ((open && t == r.M) ? (double)(j.hw - n) : 0.0);
+    const float share_m = n_m > 0.0 ? (float)((double)rinv * sm / n_m) : 0.f;
+    const float share_M = n_M > 0.0 ? (float)(-(double)rinv * sM / n_M) : 0.f;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (long long p = start + threadIdx.x; p < start + n; p += DP_BWD_THREADS) {
+        const float z = dp_z(j.gb + 12 * p, w);
+        float gz = rinv * dp_g(g_d, g_slots, p);
+        if (z == r.m) gz += share_m;
+        if (z == r.M) gz += share_M;
+        float4* o = reinterpret_cast<float4*>(g_gb + 12 * p);  // (48-byte rows of a 16-byte aligned array)
+        o[0] = make_float4(gz * w[0], gz * w[1], gz * w[2], 0.f);
+        o[1] = zero;
+        o[2] = zero;
+    }
+}
+
+// the depth source of a compositor call's first buffer: checked like ca_shade's, nothing launched
+static bool ca_has_depth(const a3d_ca_shade* sh) { return sh && sh->size >= sizeof(a3d_ca_shade) && sh->depth_gb; }
+static int ca_depth(const a3d_ca_shade* sh, int C, const float* vals, int64_t P_or_minus1, int B, int H, int W, bool forward, DpJob* d) {
+    A3D_CHECK_ARG(C == 1 && !vals);
+    A3D_CHECK_ARG(!sh->gb && !sh->par && !sh->params && !sh->kd && !sh->shaded_out && !sh->clear && sh->n_clear == 0);  // (not on a shaded buffer)
+    A3D_CHECK_ARG(sh->depth_w2c_row && sh->depth_state && sh->depth_rows >= 0 && sh->depth_w2c_stride >= 0 && B <= 65535);
+    A3D_CHECK_ARG(sh->depth_rows == 0 || (sh->depth_pix && sh->depth_out));
+    A3D_CHECK_ARG(P_or_minus1 < 0 || P_or_minus1 == sh->depth_rows);
+    A3D_CHECK_ARG(forward || sh->depth_rows == 0 || (sh->g_depth_gb && ((uintptr_t)sh->g_depth_gb & 15) == 0));
+    A3D_CHECK_ARG(forward || sh->depth_rows == 0 || (sh->g_depth_slots && ((uintptr_t)sh->g_depth_slots & 15) == 0));
+    d->gb = sh->depth_gb; d->row = sh->depth_w2c_row; d->stride = sh->depth_w2c_stride; d->pix = (const long long*)sh->depth_pix;
+    d->P = sh->depth_rows; d->hw = (unsigned)H * (unsigned)W; d->B = B; d->state = (unsigned*)sh->depth_state; d->out = sh->depth_out;
+    return A3D_OK;
+}
+
 extern "C" size_t a3d_aa_hash_bytes(int F) { return (size_t)aa_slots(F < 1 ? 1 : F) * (8 + 4 * AA_VALS); }
 
 extern "C" int a3d_aa_topology(const int32_t* tri, int F, int V, void* hash, int32_t* opp, a3d_stream_t stream) {
@@ -941,7 +1094,7 @@ static CaJob ca_job(const float* vals, int C, const int32_t* inv, const float* b
     j.s.vals = vals; j.s.inv = inv; j.s.rast = nullptr; j.s.sh_gb = nullptr; j.s.sh_par = ShPar{}; j.s.sh_kd = nullptr; j.s.sh_kd_stride = 0; j.s.sh_out = nullptr;
     j.s.sh_two_sided = 0; j.s.bg = bg; j.s.bg_shared = bg_batch == 1; j.s.C = C; j.s.hw = (unsigned)H * (unsigned)W;
     j.s.bgC = (ext && ext->bg_channels > 0) ? ext->bg_channels : C + 1;
-    j.out = out; j.g_out = g_out; j.g_vals = g_vals; j.clear = nullptr; j.n_clear = 0; j.gHW = 0;
+    j.out = out; j.g_out = g_out; j.g_vals = g_vals; j.clear = nullptr; j.n_clear = 0; j.gHW = 0; j.g_slots = nullptr;
     j.oC = (ext && ext->out_channels > 0) ? ext->out_channels : C + 1;
     j.gS = (ext && ext->g_stride > 0) ? ext->g_stride : C + 1;
     j.gC = (ext && ext->g_channels > 0) ? ext->g_channels : C + 1;
@@ -957,7 +1110,9 @@ static bool ca_ext_ok(const a3d_ca_buffer* b) {
 // the deferred shading of a compositor call's first buffer (a3d_ca_shade): the job's values come from sh_forward instead of vals
 static int ca_shade(const a3d_ca_shade* sh, int C, const float* vals, CaJob* j, bool forward) {
     if (!sh) return A3D_OK;
-    A3D_CHECK_ARG(sh->size >= sizeof(a3d_ca_shade));
+    // (the depth source was appended: a caller built against the header without it has size = the offset of depth_gb; none ever ended between)
+    A3D_CHECK_ARG(sh->size == offsetof(a3d_ca_shade, depth_gb) || sh->size >= sizeof(a3d_ca_shade));
+    if (ca_has_depth(sh)) return A3D_OK;  // (ca_depth checks that one)
     A3D_CHECK_ARG(!vals && C == 3 && sh->gb && (sh->par || sh->params) && sh->kd && sh->kd_stride >= 3 && sh->n_clear >= 0 && (sh->n_clear == 0 || sh->clear));
     if (sh->params) {
         const a3d_shade_params* q = sh->params;
@@ -1087,6 +1242,19 @@ extern "C" int a3d_composite_aa_fwd(const a3d_ca_buffer* first, const a3d_ca_buf
     A3D_CHECK_ARG(ca_ext_ok(first) && (!second_or_null || ca_ext_ok(second_or_null)));
     CaJob ja = ca_job(vals, C, inv, bg_or_null, bg_batch, H, W, out, nullptr, nullptr, first);
     if (int rc = ca_shade(shade_or_null, C, vals, &ja, true)) return rc;
+    if (ca_has_depth(shade_or_null)) {  // the first buffer's rows do not exist yet: range, values, then composited like any `vals`
+        DpJob dj;
+        if (int rc = ca_depth(shade_or_null, C, vals, -1, B, H, W, true, &dj)) return rc;
+        hipLaunchKernelGGL(dp_init_kernel, dim3(a3d_div_up((long long)B * DP_WORDS, 256)), dim3(256), 0, s, dj.state, B);
+        A3D_LAUNCH_CHECK();
+        if (dj.P > 0) {
+            hipLaunchKernelGGL(dp_range_kernel, dim3(a3d_div_up(dj.P, 256)), dim3(256), 0, s, dj);
+            A3D_LAUNCH_CHECK();
+            hipLaunchKernelGGL(dp_norm_kernel, dim3(a3d_div_up(dj.P, 256)), dim3(256), 0, s, dj);
+            A3D_LAUNCH_CHECK();
+        }
+        ja.s.vals = dj.out;
+    }
     const CaJob jb = two ? ca_job(vals2_or_null, C2, inv, bg2_or_null, bg2_batch, H, W, out2_or_null, nullptr, nullptr, second_or_null) : ja;
     const unsigned n_pix = (unsigned)B * ja.s.hw;
     const unsigned nb_compose = (unsigned)a3d_div_up(n_pix, 256), rows = two ? 2u : 1u;
@@ -1125,6 +1293,15 @@ extern "C" int a3d_composite_aa_bwd(const a3d_ca_buffer* first, const a3d_ca_buf
     A3D_CHECK_ARG(ca_ext_ok(first) && (!second_or_null || ca_ext_ok(second_or_null)));
     CaJob ja = ca_job(vals, C, inv, bg_or_null, bg_batch, H, W, nullptr, g_out, g_vals, first, (long long)P);
     if (int rc = ca_shade(shade_or_null, C, vals, &ja, false)) return rc;
+    DpJob dj = DpJob{};
+    const bool depth = ca_has_depth(shade_or_null);
+    if (depth) {  // the rows the forward kept are this buffer's values; its g_vals [P,1] feed the adjoint launch at the end
+        if (int rc = ca_depth(shade_or_null, C, vals, P, B, H, W, false, &dj)) return rc;
+        A3D_CHECK_ARG(F == 0 || tri);
+        ja.s.vals = dj.out;
+        ja.g_slots = shade_or_null->g_depth_slots;
+        if (dj.P > 0) A3D_HIP(hipMemsetAsync(ja.g_slots, 0, sizeof(float) * 4 * (size_t)dj.P, s));
+    }
     const CaJob jb = two ? ca_job(vals2, C2, inv, bg2_or_null, bg2_batch, H, W, nullptr, g_out2_or_null, g_vals2, second_or_null, (long long)P) : ja;
     {
         const long long nz = 4ll * clip_batch * V;
@@ -1133,11 +1310,17 @@ extern "C" int a3d_composite_aa_bwd(const a3d_ca_buffer* first, const a3d_ca_buf
         hipLaunchKernelGGL(ca_gather_kernel, dim3((unsigned)blocks, two ? 2 : 1), dim3(256), 0, s, ja, jb, (const long long*)pix, (long long)P, g_clip, nz);
         A3D_LAUNCH_CHECK();
     }
-    if (F == 0) return A3D_OK;
-    A3D_CHECK_ARG(tri);
-    hipLaunchKernelGGL(ca_bwd_kernel, dim3(1024, two ? 2 : 1), dim3(256), 0, s, ja, jb, (const AaRec*)work, count, capacity, (const float4*)clip,
-                       clip_batch, tri, V, H, W, g_clip);
-    A3D_LAUNCH_CHECK();
+    if (F != 0) {
+        A3D_CHECK_ARG(tri);
+        hipLaunchKernelGGL(ca_bwd_kernel, dim3(1024, two ? 2 : 1), dim3(256), 0, s, ja, jb, (const AaRec*)work, count, capacity, (const float4*)clip,
+                           clip_batch, tri, V, H, W, g_clip);
+        A3D_LAUNCH_CHECK();
+    }
+    if (depth && dj.P > 0) {
+        hipLaunchKernelGGL(dp_bwd_kernel, dim3(B), dim3(DP_BWD_THREADS), 0, s, dj, (const float*)g_vals, (const float*)shade_or_null->g_depth_slots,
+                           shade_or_null->g_depth_gb);
+        A3D_LAUNCH_CHECK();
+    }
     return A3D_OK;
 }
 

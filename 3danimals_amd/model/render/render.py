@@ -5,7 +5,7 @@ inside shade like the reference, render.py:127-128), same arithmetic; underneath
 
 * one triangle-parallel rasterisation pass (csrc/raster.hip: 64-bit atomicMin on depth|id, then a resolve) instead of the OpenGL
   depth peeler (layers > 0 peel behind the previous layer's (depth, id): render_mesh(num_layers > 1) takes the general dense path);
-* on the training path (spp 1, no tangent/depth mode) ONE fused kernel builds the G-buffer of the covered pixels only
+* on the training path (spp 1; 'tangent' / 'depth' where _fused_depth_tangent allows) ONE fused kernel builds the G-buffer of the covered pixels only
   (csrc/cover.hip + csrc/gbuffer.hip: world position, face normal, smooth normal, canonical position; its backward also carries
   the rasteriser's gradient), ONE kernel does the shading arithmetic (csrc/shade.hip), and the texture / DINO fields see the
   covered pixels only -- output-identical, because uncovered pixels are composited with alpha 0 (render.py:261-262);
@@ -46,6 +46,10 @@ FUSED_SHADING = True
 # OFF unless A3D_FUSED_MSAA=1: 2.1x / 1.8x on the 10-frame training shape, but the forward of a single 256 x 256 image is launch-bound and
 # the extra shade() call for the null rows makes it 0.85x ("Supersampled rendering"; tools/bench_msaa.py)
 FUSED_MSAA = os.environ.get("A3D_FUSED_MSAA", "0") not in ("0", "")
+# 'depth' and 'tangent' on the fused path (spp 1, one layer): the tangent rides through the G-buffer launch as its extra attribute, the
+# depth is computed by the compositor from the G-buffer rows (ops.depth_composite_antialias); off = both modes switch the whole call to
+# the generic path, as they always do where _fused_depth_tangent's conditions fail (tools/bench_render_modes.py)
+FUSED_DEPTH_TANGENT = os.environ.get("A3D_FUSED_DEPTH_TANGENT", "1") not in ("0", "")
 ALIAS_POSITIONS = os.environ.get("A3D_ALIAS_POSITIONS", "1") != "0"  # the clip transform's node feeds the G-buffer's position attribute too (one accumulation launch less)
 FIELD_INPUTS_FROM_GBUFFER = os.environ.get("A3D_FIELD_INPUTS", "1") != "0"  # the fields' padded input rows + image index written by the G-buffer launch (round 6)
 SHADE_IN_COMPOSITOR = os.environ.get("A3D_SHADE_IN_COMPOSITOR", "1") != "0"  # no a3d_shade_fwd launch when only the composited colour reads its output  # shading normal + camera normal + directional light of the covered pixels in one HIP kernel (csrc/shade.hip)
@@ -225,9 +229,11 @@ class SparseBuffers(dict):
         super().__init__()
         self.pix, self.bhw, self.inv = pix, bhw, inv  # inv: pixel -> row (int32 [B*H*W], -1 = uncovered) when the list came with it
         self.shade_recipe = None  # ops.ShadeRecipe: self['shaded'] has not been computed (the fused compositor does it on the fly)
+        self.depth_recipe = None  # (gb, w2c): 'depth' has no rows here -- the compositor computes range and values (ops.depth_composite_antialias)
 
     def __contains__(self, mode):
-        return super().__contains__(mode) or (mode == "shaded" and self.shade_recipe is not None)
+        return (super().__contains__(mode) or (mode == "shaded" and self.shade_recipe is not None)
+                or (mode == "depth" and self.depth_recipe is not None))
 
     def __getitem__(self, mode):
         # a caller that indexes the colour directly (outside render_mesh, which hands the recipe to the compositor) gets the stand-alone
@@ -289,19 +295,22 @@ def _shade_points(pos, geo, nrm, tng, tex_pos, flow, pix, bhw, w2c, view_pos, lg
     modes = render_modes if render_modes is not None else ["shaded"]
     view = view_pos.reshape(-1, 3)
     light_rows = lgt(feat) if lgt is not None and not env else None  # DirectionalLight.forward: [B,5] = direction(3), ambient, diffuse (light.py:176-184)
+    # 'depth' is not shaded here: the fused compositor computes it from the G-buffer rows (render_layer lets the mode in only on that path)
+    depth_recipe = (gb, w2c) if "depth" in modes else None
+    assert depth_recipe is None or (gb is not None and sparse and inv is not None)
 
     # ---- the fused training path: nothing is computed here.  The compositor computes the colour on the fly and its backward node runs
     # the shading adjoint (ops.ShadeRecipe / ops.shade_composite_antialias): no [B,17] table, no kd / ks / row slices, no launch.
     if (gb is not None and FUSED_SHADING and SHADE_IN_COMPOSITOR and sparse and inv is not None and lgt is not None and not env and material is not None
-            and w2c.dim() == 3 and all(m in ("shaded", "dino_pred", "flow", "kd", "ks") for m in modes)):
+            and w2c.dim() == 3 and all(m in ("shaded", "dino_pred", "flow", "kd", "ks", "depth") for m in modes)):  # (the modes it can serve)
         recipe = ops.ShadeRecipe(gb, w2c, view, light_rows, all_tex, two_sided_shading, img_rows)
         LAST_POINTS[0] = dict(pix=pix, gb=gb.detach(), all_tex=all_tex.detach(), dino=None if dino_rows is None else dino_rows.detach(),
                               light=light_rows.detach(), flow=None if flow is None else flow.detach())
         out = SparseBuffers(pix, (b, h, w), inv)
-        out.shade_recipe = recipe
+        out.shade_recipe, out.depth_recipe = recipe, depth_recipe
         lazy = {"dino_pred": dino_rows, "flow": flow, "kd": lambda: all_tex[:n_pts, :3], "ks": lambda: all_tex[:n_pts, 3:6]}
         for mode in modes:
-            if mode == "shaded":
+            if mode in ("shaded", "depth"):
                 continue
             val = lazy[mode]
             if val is None:
@@ -349,7 +358,10 @@ def _shade_points(pos, geo, nrm, tng, tex_pos, flow, pix, bhw, w2c, view_pos, lg
                               flow=None if flow is None else flow.detach())
     buffers = _collect(render_modes, shaded_col, kd, ks, nrm, geo, tng, shading, flow, dino_pred, None)
     out = SparseBuffers(pix, (b, h, w), inv)
+    out.depth_recipe = depth_recipe
     for mode in modes:
+        if mode == "depth" and depth_recipe is not None:
+            continue
         out[mode] = buffers[mode]  # KeyError for an unknown / unavailable mode, like the reference (render.py:127-128)
     return out if sparse else {mode: out.dense(mode) for mode in out}
 
@@ -368,16 +380,48 @@ def _covered_pixels(rast):
     return ops.covered_pixels(rast, tile=PIXEL_TILE)
 
 
-FUSED_GBUFFER_MODES = frozenset(("shaded", "kd", "ks", "normal", "geo_normal", "shading", "dino_pred", "flow"))
+FUSED_GBUFFER_MODES = frozenset(("shaded", "kd", "ks", "normal", "geo_normal", "shading", "dino_pred", "flow", "depth", "tangent"))
+_GENERIC_ONLY = frozenset(("tangent", "depth"))  # ... the last two only where _fused_depth_tangent allows them
+
+
+def _fused_depth_tangent(render_modes, mesh, w2c, spp, num_layers, background):
+    """Which of 'depth' / 'tangent' the fused path serves in this call: all that are asked for, or none (one of them on the generic path
+    takes the whole call there).  Both: FUSED_DEPTH_TANGENT, spp 1, one layer, no autocast.  'depth': w2c a [B,4,4] float32 device tensor
+    that does not require grad (the compositor gives it none), and the fused compositor available (no differentiable background).
+    'tangent': per-vertex tangents [B,V,3] float32 on the device whose index buffer is the position one -- and no 'flow' in the same
+    call: the G-buffer launch carries ONE extra attribute of at most 3 columns, and a call that wants both keeps the generic path."""
+    asked = _GENERIC_ONLY & set(render_modes)
+    if not asked or not FUSED_DEPTH_TANGENT or spp != 1 or num_layers != 1 or torch.is_autocast_enabled() or not mesh.v_pos.is_cuda:
+        return frozenset()
+    if "depth" in asked:
+        if not (torch.is_tensor(w2c) and w2c.is_cuda and w2c.dtype == torch.float32 and w2c.dim() == 3 and w2c.shape[1:] == (4, 4)
+                and w2c.shape[0] == mesh.v_pos.shape[0] and not w2c.requires_grad and FUSED_COMPOSITE
+                and (background is None or not background.requires_grad)):
+            return frozenset()
+    if "tangent" in asked:
+        if "flow" in render_modes:
+            return frozenset()
+        # (tangents still pending come out in the positions' shape and dtype; asking for them here would run the vertex normals before the
+        # rasteriser's launch could carry them)
+        pending = getattr(mesh, "_v_tng", 0) is None and getattr(mesh, "_lazy_tng", False) and mesh.v_tex is not None
+        tng = mesh.v_pos if pending else mesh.v_tng
+        if not (tng is not None and tng.is_cuda and tng.dtype == torch.float32 and tng.dim() == 3 and tng.shape[-1] == 3
+                and tng.shape[:2] == mesh.v_pos.shape[:2] and mesh.t_tng_idx is not None
+                and mesh.t_tng_idx.data_ptr() == mesh.t_pos_idx.data_ptr()):
+            return frozenset()
+    return frozenset(asked)
 
 
 def render_layer(rast, rast_deriv, mesh, w2c, view_pos, material, lgt, resolution, spp, msaa, bsdf, feat, render_modes=None, prior_mesh=None,
-                 two_sided_shading=True, delta_xy=None, dino_net=None, class_vector=None, clip=None, sparse=False, v_pos_attr=None):
+                 two_sided_shading=True, delta_xy=None, dino_net=None, class_vector=None, clip=None, sparse=False, v_pos_attr=None,
+                 fused_depth_tangent=frozenset()):
     """G-buffer interpolation + shading of one depth layer (reference render.py:139-221).
 
     ``clip`` (the [B,V,4] clip-space vertices, not in the reference signature) enables the fused path: one HIP kernel builds
     the G-buffer of the covered pixels and its backward also carries the rasteriser's gradient (csrc/gbuffer.hip).  Without
-    it, or for modes that need other attributes (flow, tangent, depth) or spp > 1, the generic interpolate path runs.
+    it, or for modes that need other attributes or spp > 1, the generic interpolate path runs.  ``fused_depth_tangent``: which of
+    'depth' / 'tangent' the caller has cleared for the fused path (_fused_depth_tangent; render_mesh only -- 'depth' leaves as a recipe for
+    the compositor, which needs ``sparse``).
     """
     full_res = [resolution[0] * spp, resolution[1] * spp]
     if prior_mesh is None:
@@ -386,30 +430,37 @@ def render_layer(rast, rast_deriv, mesh, w2c, view_pos, material, lgt, resolutio
     tri = mesh.t_pos_idx[0]
     assert mesh.v_nrm is not None
 
-    fused = (clip is not None and SHADE_COVERED_ONLY and spp == 1 and not ({"tangent", "depth"} & set(render_modes))
+    fused = (clip is not None and SHADE_COVERED_ONLY and spp == 1 and not ((_GENERIC_ONLY - fused_depth_tangent) & set(render_modes))
              and clip.shape[0] == mesh.v_pos.shape[0] and mesh.t_nrm_idx.data_ptr() == mesh.t_pos_idx.data_ptr())
     if fused:
         b, h, w = rast.shape[:3]
         flow = None
         flow_fused = "flow" in render_modes and delta_xy.shape[-1] <= 3  # the one extra attribute of the sequence models rides in the same kernels
+        # ... or the per-vertex tangents, for the 'tangent' mode (never both: _fused_depth_tangent)
+        tng_fused = "tangent" in render_modes and "tangent" in fused_depth_tangent and not flow_fused
+        extra = delta_xy if flow_fused else (mesh.v_tng if tng_fused else None)
+        assert not ("tangent" in render_modes and not tng_fused)
         if FUSED_COVER_GBUFFER and PIXEL_TILE == 8 and h % 8 == 0 and w % 8 == 0:
             # the covered-pixel list and its G-buffer rows from ONE launch (one host sync before it: the number of covered pixels)
             # (... and what the fields take from it -- canonical positions as dense rows, point -> image index, padded -- from the same launch)
             res = ops.covered_gbuffer(clip, mesh.v_pos if v_pos_attr is None else v_pos_attr, mesh.v_nrm, prior_mesh.v_pos, rast, tri,
-                                      extra=delta_xy if flow_fused else None,
+                                      extra=extra,
                                       field_inputs=POINT_BUCKET if FIELD_INPUTS_FROM_GBUFFER else None)
-            (gb, flow, pix, inv), rest = (res[:4], res[4:]) if flow_fused else ((res[0], None, res[1], res[2]), res[3:])
+            (gb, flow, pix, inv), rest = (res[:4], res[4:]) if extra is not None else ((res[0], None, res[1], res[2]), res[3:])
             tex_in, img_p = rest if rest else (None, None)
         else:
             tex_in = img_p = None
             pix, inv = ops.covered_pixels(rast, tile=PIXEL_TILE, return_inverse=True)  # one host sync for the number of covered pixels
-            if flow_fused:
-                gb, flow = ops.gbuffer(clip, mesh.v_pos, mesh.v_nrm, prior_mesh.v_pos, rast, tri, pix, extra=delta_xy)  # [P,12], [P,2]
+            if extra is not None:
+                gb, flow = ops.gbuffer(clip, mesh.v_pos, mesh.v_nrm, prior_mesh.v_pos, rast, tri, pix, extra=extra)  # [P,12], [P,2] (tangent: [P,3])
             else:
                 gb = ops.gbuffer(clip, mesh.v_pos, mesh.v_nrm, prior_mesh.v_pos, rast, tri, pix)  # [P,12]
         if "flow" in render_modes and not flow_fused:
             flow = interpolate(delta_xy, rast, tri)[0].reshape(b * h * w, -1).index_select(0, pix)
-        return _shade_points(gb[:, 0:3], gb[:, 3:6], gb[:, 6:9], None, gb[:, 9:12], flow, pix, (b, h, w), w2c, view_pos, lgt, material, bsdf, feat,
+        tng = None
+        if tng_fused:
+            tng, flow = flow, None
+        return _shade_points(gb[:, 0:3], gb[:, 3:6], gb[:, 6:9], tng, gb[:, 9:12], flow, pix, (b, h, w), w2c, view_pos, lgt, material, bsdf, feat,
                              render_modes, two_sided_shading, dino_net, class_vector, sparse=sparse, gb=gb, inv=inv, tex_in=tex_in, img_p=img_p)
 
     rast_s = util.scale_img_nhwc(rast, resolution, mag="nearest", min="nearest") if (spp > 1 and msaa) else rast
@@ -480,6 +531,7 @@ def render_mesh(ctx, mesh, mtx_in, w2c, view_pos, material, lgt, resolution, spp
 
     tri = mesh.t_pos_idx[0]
     clip_f = v_pos_clip.float()
+    fused_dt = _fused_depth_tangent(render_modes, mesh, w2c, spp, num_layers, background) if clip_f.shape[0] == mesh.v_pos.shape[0] else frozenset()
     if num_layers != 1:  # depth peeling: never used by a config (AnimalModel.py:247); the general, dense path
         return _render_mesh_layers(mesh, clip_f, tri, w2c, view_pos, material, lgt, resolution, spp, num_layers, msaa, background, bsdf, feat,
                                    render_modes, prior_mesh, two_sided_shading, dino_net, class_vector, delta_xy)
@@ -496,7 +548,7 @@ def render_mesh(ctx, mesh, mtx_in, w2c, view_pos, material, lgt, resolution, spp
     # when render_layer's fused path is certain to come next, the rasteriser's resolve waits for it: ONE launch then writes the texels,
     # the covered-pixel list and the G-buffer rows (ops.DEFER_RESOLVE; the conditions are render_layer's own)
     defer = (DEFER_RESOLVE and not mask_only and FUSED_GBUFFER and FUSED_COVER_GBUFFER and SHADE_COVERED_ONLY and PIXEL_TILE == 8 and spp == 1
-             and not ({"tangent", "depth"} & set(render_modes)) and clip_f.shape[0] == mesh.v_pos.shape[0]
+             and not ((_GENERIC_ONLY - fused_dt) & set(render_modes)) and clip_f.shape[0] == mesh.v_pos.shape[0]
              and mesh.t_nrm_idx.data_ptr() == mesh.t_pos_idx.data_ptr() and full_res[0] % 8 == 0 and full_res[1] % 8 == 0)
     rast = ops.rasterize(clip_f, tri, full_res, normals_job=job, defer_resolve=defer)
     if job is not None:
@@ -515,7 +567,8 @@ def render_mesh(ctx, mesh, mtx_in, w2c, view_pos, material, lgt, resolution, spp
     try:
         rendered = render_layer(rast, None, mesh, w2c, view_pos, material, lgt, resolution, spp, msaa, bsdf, feat=feat, render_modes=render_modes,
                                 prior_mesh=prior_mesh, two_sided_shading=two_sided_shading, delta_xy=delta_xy, dino_net=dino_net,
-                                class_vector=class_vector, clip=clip_f if FUSED_GBUFFER else None, sparse=True, v_pos_attr=v_pos_attr)
+                                class_vector=class_vector, clip=clip_f if FUSED_GBUFFER else None, sparse=True, v_pos_attr=v_pos_attr,
+                                fused_depth_tangent=fused_dt)
     except BaseException:
         if defer:  # the consumer the deferred resolve was promised failed: nothing may be left pending (keys pinned, texels unwritten)
             ops.drop_pending_resolve(rast)
@@ -558,6 +611,14 @@ def render_mesh(ctx, mesh, mtx_in, w2c, view_pos, material, lgt, resolution, spp
         recipe = getattr(rendered, "shade_recipe", None)
         # (the antialiasing differentiates w.r.t. the clip positions: it takes them as the clip transform's OTHER clip output, same storage)
         clip_of_aa = clip_f if clip_aa is None or clip_aa.dtype != clip_f.dtype else clip_aa
+        # 'depth' from the G-buffer rows: like the colour shaded on the fly it can only be the FIRST buffer of a call, so it gets a call of
+        # its own behind the others -- with the buffer that would have gone alone as its second one
+        depth_rec = getattr(rendered, "depth_recipe", None) if "depth" in fuse_keys else None
+        depth_partner = None
+        if depth_rec is not None:
+            fuse_keys.remove("depth")
+            if len(fuse_keys) % 2 == 1 and not (fuse_keys[-1] == "shaded" and recipe is not None and not dict.__contains__(rendered, "shaded")):
+                depth_partner = fuse_keys.pop()
         for i in range(0, len(fuse_keys), 2):
             ka, kb = fuse_keys[i], (fuse_keys[i + 1] if i + 1 < len(fuse_keys) else None)
             vb = rendered.peek(kb) if (kb is not None and not (kb == "shaded" and recipe is not None)) else (rendered[kb] if kb is not None else None)
@@ -572,8 +633,21 @@ def render_mesh(ctx, mesh, mtx_in, w2c, view_pos, material, lgt, resolution, spp
                 fused[ka] = res
             else:
                 fused[ka], fused[kb] = res
+        if depth_rec is not None:
+            kb = depth_partner
+            vb = None if kb is None else rendered.peek(kb)
+            res, depth_rows = ops.depth_composite_antialias(depth_rec[0], depth_rec[1], rendered.pix, rendered.inv, clip_of_aa, analysis, vals2=vb,
+                                                            background2=None if kb is None else bg_of(kb), keep2=None if kb is None else keep(kb, vb),
+                                                            return_rows=True)
+            if kb is None:
+                fused["depth"] = res
+            else:
+                fused["depth"], fused[kb] = res
+            if LAST_POINTS[0] is not None:
+                LAST_POINTS[0]["depth"] = depth_rows
     if LAST_POINTS[0] is not None:
         LAST_POINTS[0]["clip"] = clip_f.detach()
+    assert getattr(rendered, "depth_recipe", None) is None or "depth" in fused  # (_fused_depth_tangent admits 'depth' only where the compositor runs)
     out_buffers = []
     for key in render_modes:
         if key not in rendered:

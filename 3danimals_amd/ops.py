@@ -1869,6 +1869,109 @@ def shade_composite_antialias(recipe, pix, inv, background, clip, analysis, vals
     return o1 if vals2 is None else (o1, o2)
 
 
+class _DepthCompositeAntialias(torch.autograd.Function):
+    """The 'depth' render mode as the first buffer of a compositor call (a3d_ca_shade.depth_*, csrc/antialias.hip): per-image range over
+    the point list, one normalised value per point, composited over zeros and antialiased by the same call; the backward node runs the
+    compositor's gather and blend adjoints and then the range / normalisation adjoint -> g_gb [P,12] (position columns only).  A second
+    buffer rides as in _CompositeAntialias.  Returns (image [B,H,W,1], second image or None, the [P] depth rows -- not differentiable)."""
+
+    @staticmethod
+    def forward(ctx, gb, vals2, clip, w2c, pix, inv, bg2, analysis, keep2):
+        require_device(gb, vals2, w2c, pix, inv, what="depth_composite_antialias")
+        a = analysis
+        P = pix.shape[0]
+        dev = pix.device
+        assert pix.dtype == torch.int64 and inv.shape == (a.B * a.H * a.W,) and inv.dtype == torch.int32
+        gb, w2c = f32c(gb), f32c(w2c)
+        assert gb.shape == (P, 12) and w2c.dim() == 3 and w2c.shape[1:] == (4, 4) and w2c.shape[0] in (1, a.B)
+        out2 = None
+        C2 = 0
+        if vals2 is not None:
+            vals2 = f32c(vals2)
+            assert vals2.shape[0] >= P
+            C2 = vals2.shape[1]
+            if bg2 is not None:
+                bg2 = f32c(bg2)
+                assert bg2.shape[1:3] == (a.H, a.W) and bg2.shape[3] <= C2 + 1 and bg2.shape[0] in (1, a.B)
+            k2 = C2 + 1 if keep2 is None else int(keep2)
+            assert 1 <= k2 <= C2 + 1
+            out2 = torch.empty((a.B, a.H, a.W, k2), dtype=torch.float32, device=dev)
+        out = torch.empty((a.B, a.H, a.W, 1), dtype=torch.float32, device=dev)  # (the mode is cut to 1 channel, render.py:324-325: alpha never written)
+        rows = torch.empty((P,), dtype=torch.float32, device=dev)
+        state = torch.empty((a.B, 8), dtype=torch.int32, device=dev)
+        ride = a.ride_args()
+        sh = _depth_source(gb, w2c, pix, state, rows, None)
+        first = _lib.CaBuffer(size=ctypes.sizeof(_lib.CaBuffer), C=1, vals=None, bg=None, out=ptr(out), bg_batch=0, out_channels=1)
+        second = None if vals2 is None else _lib.CaBuffer(size=ctypes.sizeof(_lib.CaBuffer), C=C2, vals=ptr(vals2), bg=ptr(bg2), out=ptr(out2),
+                                                          bg_batch=0 if bg2 is None else bg2.shape[0], bg_channels=0 if bg2 is None else bg2.shape[3],
+                                                          out_channels=out2.shape[3])
+        tag = "[depth]" if vals2 is None else f"[depth+C{C2 + 1}]"
+        call("a3d_composite_aa_fwd", ctypes.addressof(first), None if second is None else ctypes.addressof(second), ptr(inv), ptr(a.work), ptr(a.count),
+             a.capacity, a.B, a.H, a.W, None if ride is None else ctypes.addressof(ride), ctypes.addressof(sh), stream(),
+             tag=tag + ("[+analysis]" if ride is not None else ""))
+        if ride is not None:
+            a.pending = False
+        ctx.save_for_backward(gb, vals2, w2c, pix, inv, bg2, rows, state)
+        ctx.analysis, ctx.tag = a, tag
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(rows)
+        return out, out2, rows
+
+    @staticmethod
+    def backward(ctx, g_out, g_out2=None, _g_rows=None):
+        gb, vals2, w2c, pix, inv, bg2, rows, state = ctx.saved_tensors
+        a = ctx.analysis
+        P = pix.shape[0]
+        dev = pix.device
+        two = vals2 is not None
+        C2 = vals2.shape[1] if two else 0
+        if g_out is None:
+            g_out = torch.zeros((a.B, a.H, a.W, 1), dtype=torch.float32, device=dev)
+        if two and g_out2 is None:
+            g_out2 = torch.zeros((a.B, a.H, a.W, C2 + 1), dtype=torch.float32, device=dev)
+        g_out, gs, gc = _image_gradient_in_place(g_out, a.H, a.W)
+        if two:
+            g_out2, gs2, gc2 = _image_gradient_in_place(g_out2, a.H, a.W)
+        g_rows = torch.empty((P, 1), dtype=torch.float32, device=dev)
+        g_vals2 = torch.empty_like(vals2) if two else None
+        g_clip = torch.empty_like(a.clip)
+        g_gb = torch.empty_like(gb)
+        slots = torch.empty((P, 4), dtype=torch.float32, device=dev)  # (cleared by the call)
+        sh = _depth_source(gb, w2c, pix, state, rows, g_gb, slots)
+        first = _lib.CaBuffer(size=ctypes.sizeof(_lib.CaBuffer), C=1, vals=None, bg=None, g_out=ptr(g_out), g_vals=ptr(g_rows), bg_batch=0,
+                              g_stride=gs, g_channels=gc, vals_rows=P)
+        second = None if not two else _lib.CaBuffer(size=ctypes.sizeof(_lib.CaBuffer), C=C2, vals=ptr(vals2), bg=ptr(bg2), g_out=ptr(g_out2),
+                                                    g_vals=ptr(g_vals2), bg_batch=0 if bg2 is None else bg2.shape[0],
+                                                    bg_channels=0 if bg2 is None else bg2.shape[3], g_stride=gs2, g_channels=gc2,
+                                                    vals_rows=vals2.shape[0])
+        call("a3d_composite_aa_bwd", ctypes.addressof(first), None if second is None else ctypes.addressof(second), ptr(pix), P, ptr(inv), ptr(a.work),
+             ptr(a.count), a.capacity, ptr(a.clip), a.clip.shape[0], ptr(a.topo.tri), a.B, a.clip.shape[1], a.topo.tri.shape[0], a.H, a.W, ptr(g_clip),
+             ctypes.addressof(sh), stream(), tag=ctx.tag)
+        return g_gb, g_vals2, g_clip, None, None, None, None, None, None
+
+
+def _depth_source(gb, w2c, pix, state, rows, g_gb, slots=None):
+    """a3d_ca_shade carrying only the depth source: row 2 of w2c [1|B,4,4] read in place."""
+    return _lib.CaShade(size=ctypes.sizeof(_lib.CaShade), depth_gb=ptr(gb), depth_w2c_row=w2c.data_ptr() + 8 * 4,
+                        depth_w2c_stride=0 if w2c.shape[0] == 1 else 16, depth_pix=ptr(pix), depth_rows=pix.shape[0], depth_state=ptr(state),
+                        depth_out=ptr(rows), g_depth_gb=ptr(g_gb), g_depth_slots=ptr(slots))
+
+
+def depth_composite_antialias(gb, w2c, pix, inv, clip, analysis, vals2=None, background2=None, keep2=None, return_rows=False):
+    """The 'depth' render mode from the G-buffer rows ``gb`` [P,12] of the covered pixels ``pix`` / ``inv``: z = camera-space depth of the
+    interpolated position (row 2 of ``w2c`` [1|B,4,4]), normalised per image with the extremes over ALL pixels of the frame (an uncovered
+    pixel has z = w2c[b,2,3]), composited over zeros and antialiased: [B,H,W,1] (reference render.py:98-104, 311-315, 324-325).
+    With ``vals2`` a second buffer rides in the same launches as in composite_antialias: returns the pair.  Differentiable in ``gb``
+    (position columns) and ``clip`` (and ``vals2``); ``w2c`` gets no gradient.  ``return_rows``: also the [P] normalised depth rows."""
+    assert not w2c.requires_grad, "depth_composite_antialias: w2c gets no gradient here (render_mesh takes the generic path for it)"
+    assert background2 is None or not background2.requires_grad
+    if clip.dim() == 2:
+        clip = clip[None]
+    o1, o2, rows = _DepthCompositeAntialias.apply(gb, vals2, clip, w2c, pix, inv, background2, analysis, keep2)
+    res = o1 if vals2 is None else (o1, o2)
+    return (res, rows) if return_rows else res
+
+
 class _MsaaCompositeAntialias(torch.autograd.Function):
     """The compositor in supersampled mode (a3d_ca_buffer.spp > 1, csrc/antialias.hip): one or two buffers given as rows on the SHADING grid
     [B,h,w], composited with the full-resolution coverage, antialiased with the full-resolution crossing records and averaged per

@@ -581,6 +581,31 @@ typedef struct a3d_ca_shade {
     float* shaded_out;  /* (403) forward, optional [P,3]: the colour of every covered pixel as the compose launch computed it, kept (12 B per
                          * point) so that the blend launch and the whole backward read it as plain value rows (first buffer's `vals`, no
                          * `shade` struct) instead of re-deriving the shading per crossing record and channel */
+    /* The 'depth' render mode as the FIRST buffer's source (render.py:98-104 of the reference: camera-space z of the interpolated position,
+     * normalised per image to [0,1] with the extremes over ALL H W pixels, an uncovered pixel having position 0).  Appended without a version
+     * bump (a3d_version() stays 405) and size-gated: these fields are read only when `size` covers them; a caller whose `size` ends at
+     * shaded_out gets the behaviour above, bit for bit.  With depth_gb the fields above it (gb .. shaded_out) must be NULL / 0, the first
+     * buffer has vals = NULL and C = 1, and neither buffer may be supersampled (A3D_EINVAL otherwise, before anything is launched).
+     * z_p = row . [pos_p, 1] with row = depth_w2c_row + image * depth_w2c_stride; (m, M) = the extremes over the image's points, joined by
+     * row[3] (z of an uncovered pixel) exactly when the image has fewer than H W points; depth_out[p] = (z_p - m) / (M - m), which the
+     * call then composites over its background and antialiases like a `vals` buffer.  Three launches before the compositor's two.
+     * bwd (one launch after the compositor's, which wrote the first buffer's g_vals[P,1]): g_depth_gb[p,0:3] = g_z_p row[0:3], columns 3..11
+     * zero, with g_p = g_vals[p] + the four words of g_depth_slots[p] (cleared by the call) and g_z_p = g_p / (M - m) + the share of d(loss)/dm and d(loss)/dM of a point that attains the extreme: each is divided
+     * equally among ALL pixels that attain it (torch.amin / amax), the uncovered pixels' share -- a gradient of w2c -- is dropped.  The two
+     * per-image sums are carried in double and added in a fixed order; min and max are integer atomics on an order-preserving key: the
+     * result repeats bit for bit.  An image without points gets no range and no rows (its composite is the background). */
+    const float* depth_gb;      /* [P,12] G-buffer rows (columns 0..2: world position); NULL: no depth source */
+    const float* depth_w2c_row; /* row 2 of the world-to-camera matrix of image 0: w2c + 8 for [B,4,4] */
+    int64_t depth_w2c_stride;   /* floats from an image's row to the next image's: 16 for [B,4,4], 0 for a shared row */
+    const int64_t* depth_pix;   /* [P] flat pixel of every point, image-major (image of point p = depth_pix[p] / (H W), non-decreasing) */
+    int64_t depth_rows;         /* P */
+    int32_t* depth_state;       /* [B,8] words per image: min key, max key, points, points attaining m, points attaining M, 3 unused;
+                                 * written by the forward, read by the backward */
+    float* depth_out;           /* [P], written by the forward and kept: the backward reads it */
+    float* g_depth_gb;          /* backward: [P,12], fully written */
+    float* g_depth_slots;       /* backward, scratch: [P,4] (16-byte aligned) the blend adjoints of every point by its role in a crossing record
+                                 * (first / second pixel of a right / lower pair: at most one record each), stored instead of added atomically
+                                 * to g_vals and summed in a fixed order by the adjoint launch -- g_depth_gb repeats bit for bit */
 } a3d_ca_shade;
 /* One buffer of a compositor call (round 4: the two buffers of a call by name instead of ten / twelve positional arguments). */
 typedef struct a3d_ca_buffer {
