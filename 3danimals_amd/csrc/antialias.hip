@@ -1088,23 +1088,30 @@ extern "C" int a3d_aa_bwd(const float* g_out, const float* color, int C, const v
     return A3D_OK;
 }
 
-static CaJob ca_job(const float* vals, int C, const int32_t* inv, const float* bg, int bg_batch, int H, int W, float* out, const float* g_out,
-                    float* g_vals, const a3d_ca_buffer* ext = nullptr, long long P = 0) {
+// the job of one buffer (0 in an optional field = its default); the forward reads b->out, the backward b->g_out / b->g_vals
+static CaJob ca_job(const a3d_ca_buffer* b, const int32_t* inv, int H, int W, long long P) {
     CaJob j;
-    j.s.vals = vals; j.s.inv = inv; j.s.rast = nullptr; j.s.sh_gb = nullptr; j.s.sh_par = ShPar{}; j.s.sh_kd = nullptr; j.s.sh_kd_stride = 0; j.s.sh_out = nullptr;
-    j.s.sh_two_sided = 0; j.s.bg = bg; j.s.bg_shared = bg_batch == 1; j.s.C = C; j.s.hw = (unsigned)H * (unsigned)W;
-    j.s.bgC = (ext && ext->bg_channels > 0) ? ext->bg_channels : C + 1;
-    j.out = out; j.g_out = g_out; j.g_vals = g_vals; j.clear = nullptr; j.n_clear = 0; j.gHW = 0; j.g_slots = nullptr;
-    j.oC = (ext && ext->out_channels > 0) ? ext->out_channels : C + 1;
-    j.gS = (ext && ext->g_stride > 0) ? ext->g_stride : C + 1;
-    j.gC = (ext && ext->g_channels > 0) ? ext->g_channels : C + 1;
-    j.vals_rows = (ext && ext->vals_rows > P) ? ext->vals_rows : P;
+    j.s.vals = b->vals; j.s.inv = inv; j.s.rast = nullptr; j.s.sh_gb = nullptr; j.s.sh_par = ShPar{}; j.s.sh_kd = nullptr; j.s.sh_kd_stride = 0; j.s.sh_out = nullptr;
+    j.s.sh_two_sided = 0; j.s.bg = b->bg; j.s.bg_shared = b->bg_batch == 1; j.s.C = b->C; j.s.hw = (unsigned)H * (unsigned)W;
+    j.s.bgC = b->bg_channels > 0 ? b->bg_channels : b->C + 1;
+    j.out = b->out; j.g_out = b->g_out; j.g_vals = b->g_vals; j.clear = nullptr; j.n_clear = 0; j.gHW = 0; j.g_slots = nullptr;
+    j.oC = b->out_channels > 0 ? b->out_channels : b->C + 1;
+    j.gS = b->g_stride > 0 ? b->g_stride : b->C + 1;
+    j.gC = b->g_channels > 0 ? b->g_channels : b->C + 1;
+    j.vals_rows = b->vals_rows > P ? b->vals_rows : P;
     return j;
 }
 static bool ca_ext_ok(const a3d_ca_buffer* b) {
     return b->bg_channels >= 0 && b->bg_channels <= b->C + 1 && b->g_channels >= 0 && b->g_channels <= b->C + 1 && b->g_stride >= 0 &&
            (b->g_stride == 0 || b->g_stride >= (b->g_channels > 0 ? b->g_channels : b->C + 1)) && b->vals_rows >= 0 && b->out_channels >= 0 &&
            b->out_channels <= b->C + 1;
+}
+// what one buffer of an spp 1 call must bring, in either direction; `sourced`: its rows come from the call's a3d_ca_shade
+static int ca_check(const a3d_ca_buffer* b, int B, bool forward, long long P, bool sourced) {
+    A3D_CHECK_ARG(forward ? b->out != nullptr : b->g_out != nullptr);
+    A3D_CHECK_ARG(b->C > 0 && b->C + (forward ? 1 : 0) <= 4096 && (!b->bg || b->bg_batch == 1 || b->bg_batch == B) && ca_ext_ok(b));
+    A3D_CHECK_ARG(forward || P == 0 || ((b->vals || sourced) && b->g_vals));
+    return A3D_OK;
 }
 
 // the deferred shading of a compositor call's first buffer (a3d_ca_shade): the job's values come from sh_forward instead of vals
@@ -1226,25 +1233,21 @@ extern "C" int a3d_composite_aa_fwd(const a3d_ca_buffer* first, const a3d_ca_buf
     A3D_CHECK_ARG(first && ca_size_ok(first) && (!second_or_null || ca_size_ok(second_or_null)));
     if (ca_spp(first) > 1 || (second_or_null && ca_spp(second_or_null) > 1))
         return ms_fwd(first, second_or_null, inv, work, count, capacity, B, H, W, analyze_or_null != nullptr || shade_or_null != nullptr, stream);
-    const float *vals = first->vals, *bg_or_null = first->bg, *vals2_or_null = second_or_null ? second_or_null->vals : nullptr;
-    const float* bg2_or_null = second_or_null ? second_or_null->bg : nullptr;
-    const int C = first->C, bg_batch = first->bg_batch, C2 = second_or_null ? second_or_null->C : 0, bg2_batch = second_or_null ? second_or_null->bg_batch : 0;
-    float *out = first->out, *out2_or_null = second_or_null ? second_or_null->out : nullptr;
-    A3D_CHECK_ARG(!second_or_null || out2_or_null);
-    A3D_CHECK_ARG(inv && work && count && out && C > 0 && C + 1 <= 4096 && B > 0 && H > 0 && W > 0 && capacity > 0);
+    A3D_CHECK_ARG(inv && work && count && B > 0 && H > 0 && W > 0 && capacity > 0 && (long long)B * H * W < 0x7FFFFFFFll);
+    for (const a3d_ca_buffer* b : {first, second_or_null}) {
+        if (!b) continue;
+        if (int rc = ca_check(b, B, true, 0, false)) return rc;
+    }
     AaAnalyzeJob an;
     unsigned nb_an;
     if (int rc = ca_ride(analyze_or_null, nullptr, work, count, capacity, B, H, W, &an, &nb_an)) return rc;
-    A3D_CHECK_ARG((long long)B * H * W < 0x7FFFFFFFll && (!bg_or_null || bg_batch == 1 || bg_batch == B));
-    const bool two = out2_or_null != nullptr;
-    A3D_CHECK_ARG(!two || (C2 > 0 && C2 + 1 <= 4096 && (!bg2_or_null || bg2_batch == 1 || bg2_batch == B)));
+    const bool two = second_or_null != nullptr;
     hipStream_t s = (hipStream_t)stream;
-    A3D_CHECK_ARG(ca_ext_ok(first) && (!second_or_null || ca_ext_ok(second_or_null)));
-    CaJob ja = ca_job(vals, C, inv, bg_or_null, bg_batch, H, W, out, nullptr, nullptr, first);
-    if (int rc = ca_shade(shade_or_null, C, vals, &ja, true)) return rc;
+    CaJob ja = ca_job(first, inv, H, W, 0);
+    if (int rc = ca_shade(shade_or_null, first->C, first->vals, &ja, true)) return rc;
     if (ca_has_depth(shade_or_null)) {  // the first buffer's rows do not exist yet: range, values, then composited like any `vals`
         DpJob dj;
-        if (int rc = ca_depth(shade_or_null, C, vals, -1, B, H, W, true, &dj)) return rc;
+        if (int rc = ca_depth(shade_or_null, first->C, first->vals, -1, B, H, W, true, &dj)) return rc;
         hipLaunchKernelGGL(dp_init_kernel, dim3(a3d_div_up((long long)B * DP_WORDS, 256)), dim3(256), 0, s, dj.state, B);
         A3D_LAUNCH_CHECK();
         if (dj.P > 0) {
@@ -1255,7 +1258,7 @@ extern "C" int a3d_composite_aa_fwd(const a3d_ca_buffer* first, const a3d_ca_buf
         }
         ja.s.vals = dj.out;
     }
-    const CaJob jb = two ? ca_job(vals2_or_null, C2, inv, bg2_or_null, bg2_batch, H, W, out2_or_null, nullptr, nullptr, second_or_null) : ja;
+    const CaJob jb = two ? ca_job(second_or_null, inv, H, W, 0) : ja;
     const unsigned n_pix = (unsigned)B * ja.s.hw;
     const unsigned nb_compose = (unsigned)a3d_div_up(n_pix, 256), rows = two ? 2u : 1u;
     hipLaunchKernelGGL(ca_compose_kernel, dim3(nb_compose + (nb_an + rows - 1) / rows, rows), dim3(256), 0, s, ja, jb, n_pix, nb_compose, an, 1);
@@ -1276,33 +1279,26 @@ extern "C" int a3d_composite_aa_bwd(const a3d_ca_buffer* first, const a3d_ca_buf
     A3D_CHECK_ARG(first && ca_size_ok(first) && (!second_or_null || ca_size_ok(second_or_null)));
     if (ca_spp(first) > 1 || (second_or_null && ca_spp(second_or_null) > 1))
         return ms_bwd(first, second_or_null, P, inv, work, count, capacity, clip, clip_batch, tri, B, V, F, H, W, g_clip, shade_or_null != nullptr, stream);
-    const float *g_out = first->g_out, *vals = first->vals, *bg_or_null = first->bg;
-    const int C = first->C, bg_batch = first->bg_batch;
-    float* g_vals = first->g_vals;
-    const float *g_out2_or_null = second_or_null ? second_or_null->g_out : nullptr, *vals2 = second_or_null ? second_or_null->vals : nullptr;
-    const float* bg2_or_null = second_or_null ? second_or_null->bg : nullptr;
-    const int C2 = second_or_null ? second_or_null->C : 0, bg2_batch = second_or_null ? second_or_null->bg_batch : 0;
-    float* g_vals2 = second_or_null ? second_or_null->g_vals : nullptr;
-    A3D_CHECK_ARG(!second_or_null || g_out2_or_null);
-    A3D_CHECK_ARG(g_out && inv && work && count && clip && g_clip && C > 0 && C <= 4096 && B > 0 && V > 0 && H > 0 && W > 0 && P >= 0 && capacity > 0);
-    A3D_CHECK_ARG((long long)B * H * W < 0x7FFFFFFFll && (clip_batch == 1 || clip_batch == B) && (!bg_or_null || bg_batch == 1 || bg_batch == B));
-    A3D_CHECK_ARG(P == 0 || ((vals || shade_or_null) && pix && g_vals));
-    const bool two = g_out2_or_null != nullptr;
-    A3D_CHECK_ARG(!two || (C2 > 0 && C2 <= 4096 && (!bg2_or_null || bg2_batch == 1 || bg2_batch == B) && (P == 0 || (vals2 && g_vals2))));
+    A3D_CHECK_ARG(inv && work && count && clip && g_clip && B > 0 && V > 0 && H > 0 && W > 0 && P >= 0 && capacity > 0);
+    A3D_CHECK_ARG((long long)B * H * W < 0x7FFFFFFFll && (clip_batch == 1 || clip_batch == B) && (P == 0 || pix));
+    for (const a3d_ca_buffer* b : {first, second_or_null}) {
+        if (!b) continue;
+        if (int rc = ca_check(b, B, false, (long long)P, b == first && shade_or_null)) return rc;
+    }
+    const bool two = second_or_null != nullptr;
     hipStream_t s = (hipStream_t)stream;
-    A3D_CHECK_ARG(ca_ext_ok(first) && (!second_or_null || ca_ext_ok(second_or_null)));
-    CaJob ja = ca_job(vals, C, inv, bg_or_null, bg_batch, H, W, nullptr, g_out, g_vals, first, (long long)P);
-    if (int rc = ca_shade(shade_or_null, C, vals, &ja, false)) return rc;
+    CaJob ja = ca_job(first, inv, H, W, (long long)P);
+    if (int rc = ca_shade(shade_or_null, first->C, first->vals, &ja, false)) return rc;
     DpJob dj = DpJob{};
     const bool depth = ca_has_depth(shade_or_null);
     if (depth) {  // the rows the forward kept are this buffer's values; its g_vals [P,1] feed the adjoint launch at the end
-        if (int rc = ca_depth(shade_or_null, C, vals, P, B, H, W, false, &dj)) return rc;
+        if (int rc = ca_depth(shade_or_null, first->C, first->vals, P, B, H, W, false, &dj)) return rc;
         A3D_CHECK_ARG(F == 0 || tri);
         ja.s.vals = dj.out;
         ja.g_slots = shade_or_null->g_depth_slots;
         if (dj.P > 0) A3D_HIP(hipMemsetAsync(ja.g_slots, 0, sizeof(float) * 4 * (size_t)dj.P, s));
     }
-    const CaJob jb = two ? ca_job(vals2, C2, inv, bg2_or_null, bg2_batch, H, W, nullptr, g_out2_or_null, g_vals2, second_or_null, (long long)P) : ja;
+    const CaJob jb = two ? ca_job(second_or_null, inv, H, W, (long long)P) : ja;
     {
         const long long nz = 4ll * clip_batch * V;
         long long blocks = a3d_div_up(ja.vals_rows > jb.vals_rows ? ja.vals_rows : jb.vals_rows, 256);
@@ -1317,7 +1313,7 @@ extern "C" int a3d_composite_aa_bwd(const a3d_ca_buffer* first, const a3d_ca_buf
         A3D_LAUNCH_CHECK();
     }
     if (depth && dj.P > 0) {
-        hipLaunchKernelGGL(dp_bwd_kernel, dim3(B), dim3(DP_BWD_THREADS), 0, s, dj, (const float*)g_vals, (const float*)shade_or_null->g_depth_slots,
+        hipLaunchKernelGGL(dp_bwd_kernel, dim3(B), dim3(DP_BWD_THREADS), 0, s, dj, (const float*)first->g_vals, (const float*)shade_or_null->g_depth_slots,
                            shade_or_null->g_depth_gb);
         A3D_LAUNCH_CHECK();
     }
@@ -1338,7 +1334,9 @@ extern "C" int a3d_mask_aa_fwd(const float* rast, int C, const float* bg_or_null
     unsigned nb_an;
     if (int rc = ca_ride(analyze_or_null, rast, work, count, capacity, B, H, W, &an, &nb_an)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    CaJob ja = ca_job(nullptr, C, nullptr, bg_or_null, bg_batch, H, W, out, nullptr, nullptr);
+    a3d_ca_buffer m = {};
+    m.C = C; m.bg = bg_or_null; m.bg_batch = bg_batch; m.out = out;
+    CaJob ja = ca_job(&m, nullptr, H, W, 0);
     ja.s.rast = (const float4*)rast;
     const unsigned n_pix = (unsigned)B * ja.s.hw, nb_compose = (unsigned)a3d_div_up(n_pix, 256);
     hipLaunchKernelGGL(ca_compose_kernel, dim3(nb_compose + nb_an, 1), dim3(256), 0, s, ja, ja, n_pix, nb_compose, an, 1);
@@ -1357,7 +1355,9 @@ extern "C" int a3d_mask_aa_bwd(const float* g_out, const float* rast, int C, con
     A3D_HIP(hipMemsetAsync(g_clip, 0, sizeof(float) * 4 * (size_t)clip_batch * V, s));
     if (F == 0) return A3D_OK;
     A3D_CHECK_ARG(tri);
-    CaJob ja = ca_job(nullptr, C, nullptr, bg_or_null, bg_batch, H, W, nullptr, g_out, nullptr);
+    a3d_ca_buffer m = {};
+    m.C = C; m.bg = bg_or_null; m.bg_batch = bg_batch; m.g_out = g_out;
+    CaJob ja = ca_job(&m, nullptr, H, W, 0);
     ja.s.rast = (const float4*)rast;
     ja.gHW = g_channels_first ? H * W : 0;
     hipLaunchKernelGGL(ca_bwd_kernel, dim3(1024, 1), dim3(256), 0, s, ja, ja, (const AaRec*)work, count, capacity, (const float4*)clip, clip_batch,

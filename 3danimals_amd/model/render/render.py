@@ -29,6 +29,8 @@ from . import light, util
 from . import renderutils as ru
 
 ANTIALIASED_MODES = ("shaded", "flow", "dino_pred", "depth", "shading")  # reference render.py:311
+# leading channels of its [.., C+1] image that a mode hands out (reference render.py:320-331; -1: all but the alpha; not listed: all)
+MODE_CHANNELS = {"kd": 3, "ks": 3, "normal": 3, "geo_normal": 3, "tangent": 3, "shading": 1, "depth": 1, "flow": 2, "dino_pred": -1}
 FUSED_COMPOSITE = True  # sparse buffers: composite + antialias as one op (ops.composite_antialias); False = torch composite + ops.antialias
 SHADE_COVERED_ONLY = True  # evaluate the texture / DINO MLPs on rasterised pixels only (output-identical; see shade())
 POINT_BUCKET = 8192  # pad the covered-point list seen by the MLPs to a multiple of this (0 = off)
@@ -492,6 +494,65 @@ def _face_index_buffer(tri):
     return _face_idx_cache.get(tri, lambda t: torch.arange(t.shape[0], dtype=torch.int32, device=t.device)[:, None].repeat(1, 3).contiguous())
 
 
+def _slice_mode(key, out):
+    """Channel selection per render mode (reference render.py:320-331)."""
+    n = MODE_CHANNELS.get(key)
+    return out if n is None else out[..., :n]
+
+
+def _lazy_background4(background, res, dev):
+    """The reference appends a zero alpha channel to the background on every call (render.py:254-256): the fused compositor reads the
+    3-channel tensor as it is (a3d_ca_buffer.bg_channels); only who needs the 4-channel copy calls this, and it is built once."""
+    made = []
+
+    def background4():
+        if not made:
+            made.append(torch.cat((background, torch.zeros_like(background[..., 0:1])), dim=-1) if background is not None
+                        else torch.zeros(1, res[0], res[1], 4, dtype=torch.float32, device=dev))
+        return made[0]
+    return background4
+
+
+def _composite_modes(keys, rendered, background, background4, call, out, on_the_fly=False, depth_last=False):
+    """The modes ``keys`` through the fused compositor two at a time (the colour and the feature image of a training step share its
+    launches), the images into ``out``.  ``call(ka, va, bg, keep, kb, second)`` issues one: ``va`` the first mode's rows -- with
+    ``on_the_fly`` None when it has none yet (a colour that is still a recipe, 'depth'): only the FIRST buffer of a call can be computed
+    by the call -- ``second`` the vals2 / background2 / keep2 arguments.  Rows go as they are stored (``peek``: padding rows included);
+    everywhere else a colour that is still a recipe is materialised.  ``background4``: the lazily built 4-channel background, or None
+    where nobody else needs one.  ``depth_last``: 'depth' gets a call of its own behind the others -- with the buffer that would have
+    gone alone, if that one has rows, as its second one."""
+    def bg_of(k):
+        if background is None or k not in ("shaded", "geo_normal", "shading"):
+            return None
+        if k != "shading":
+            return background
+        # 'shading': the last two channels of the background with its zero alpha appended (render.py:254-256, 307-308) -- a view of the
+        # 4-channel copy where the call has one, else just those two channels
+        return background4()[..., 2:] if background4 is not None else torch.cat((background[..., 2:3], torch.zeros_like(background[..., 0:1])), dim=-1)
+
+    def keep(k, vals):  # (the op returns the channels the mode hands out, so no slice -- and no padded gradient of one -- follows it)
+        n = MODE_CHANNELS.get(k)
+        return None if n is None else (vals.shape[-1] if n == -1 else n)
+
+    has_rows = lambda k: dict.__contains__(rendered, k)
+    if depth_last:
+        keys = [k for k in keys if k != "depth"]
+    pairs = [(keys[i], keys[i + 1] if i + 1 < len(keys) else None) for i in range(0, len(keys), 2)]
+    if depth_last:
+        if pairs and pairs[-1][1] is None and has_rows(pairs[-1][0]):
+            pairs[-1] = ("depth", pairs[-1][0])
+        else:
+            pairs.append(("depth", None))
+    for ka, kb in pairs:
+        vb = None if kb is None else (rendered.peek(kb) if has_rows(kb) else rendered[kb])
+        va = rendered.peek(ka) if has_rows(ka) else (None if on_the_fly else rendered[ka])
+        res = call(ka, va, bg_of(ka), None if va is None else keep(ka, va), kb, dict(vals2=vb, background2=None if kb is None else bg_of(kb), keep2=None if kb is None else keep(kb, vb)))
+        if kb is None:
+            out[ka] = res
+        else:
+            out[ka], out[kb] = res
+
+
 def render_mesh(ctx, mesh, mtx_in, w2c, view_pos, material, lgt, resolution, spp=1, num_layers=1, msaa=False, background=None, bsdf=None,
                 feat=None, render_modes=None, prior_mesh=None, two_sided_shading=True, dino_net=None, num_frames=None, class_vector=None):
     """Rasterise, shade, composite over the background and antialias (reference render.py:228-337).
@@ -576,16 +637,7 @@ def render_mesh(ctx, mesh, mtx_in, w2c, view_pos, material, lgt, resolution, spp
 
     if background is not None and spp > 1:
         background = util.scale_img_nhwc(background, full_res, mag="nearest", min="nearest")
-    # the reference appends a zero alpha channel to the background on every call (render.py:254-256): the fused compositor reads the
-    # 3-channel tensor as it is (a3d_ca_buffer.bg_channels); only the torch branches further down build the 4-channel copy
-    bg4 = [None]
-
-    def background4():
-        if bg4[0] is None:
-            bg4[0] = (torch.cat((background, torch.zeros_like(background[..., 0:1])), dim=-1) if background is not None
-                      else torch.zeros(1, full_res[0], full_res[1], 4, dtype=torch.float32, device=dev))
-        return bg4[0]
-
+    background4 = _lazy_background4(background, full_res, dev)  # (only the torch branches further down, and 'shading', need the copy)
     analysis = None
     # composite + antialias fused (csrc/antialias.hip): one pass over the image per buffer, same values as the two steps further down;
     # the buffers go through the op two at a time (the colour and the feature image of a training step share its launches)
@@ -595,56 +647,22 @@ def render_mesh(ctx, mesh, mtx_in, w2c, view_pos, material, lgt, resolution, spp
     if fuse_keys:
         tri32 = ops.tri_int32(tri)
         analysis = ops.AAAnalysis(rast, clip_f, ops.aa_topology(tri32, clip_f.shape[1]), defer=DEFER_ANALYSIS)  # runs inside the first compositor call
-
-        def bg_of(k):
-            if k not in ("shaded", "geo_normal", "shading") or background is None:
-                return None
-            return background4()[..., 2:] if k == "shading" else background  # ('shading': the last two channels of the 4-channel background)
-
-        # channels handed out per mode (render.py:320-331): the op returns the view, so no slice (and no padded gradient of one) follows it
-        keep_of = {"flow": 2, "dino_pred": -1, "shading": 1, "depth": 1}
-
-        def keep(k, vals):
-            n = keep_of.get(k)
-            return None if n is None else (vals.shape[-1] if n == -1 else n)
-
-        recipe = getattr(rendered, "shade_recipe", None)
         # (the antialiasing differentiates w.r.t. the clip positions: it takes them as the clip transform's OTHER clip output, same storage)
         clip_of_aa = clip_f if clip_aa is None or clip_aa.dtype != clip_f.dtype else clip_aa
-        # 'depth' from the G-buffer rows: like the colour shaded on the fly it can only be the FIRST buffer of a call, so it gets a call of
-        # its own behind the others -- with the buffer that would have gone alone as its second one
-        depth_rec = getattr(rendered, "depth_recipe", None) if "depth" in fuse_keys else None
-        depth_partner = None
-        if depth_rec is not None:
-            fuse_keys.remove("depth")
-            if len(fuse_keys) % 2 == 1 and not (fuse_keys[-1] == "shaded" and recipe is not None and not dict.__contains__(rendered, "shaded")):
-                depth_partner = fuse_keys.pop()
-        for i in range(0, len(fuse_keys), 2):
-            ka, kb = fuse_keys[i], (fuse_keys[i + 1] if i + 1 < len(fuse_keys) else None)
-            vb = rendered.peek(kb) if (kb is not None and not (kb == "shaded" and recipe is not None)) else (rendered[kb] if kb is not None else None)
-            if ka == "shaded" and recipe is not None and not dict.__contains__(rendered, "shaded"):  # (only the FIRST buffer of a call can be shaded on the fly)
-                res = ops.shade_composite_antialias(recipe, rendered.pix, rendered.inv, bg_of(ka), clip_of_aa, analysis, vals2=vb,
-                                                    background2=None if kb is None else bg_of(kb), keep2=None if kb is None else keep(kb, vb))
-            else:
-                va = rendered.peek(ka) if dict.__contains__(rendered, ka) else rendered[ka]
-                res = ops.composite_antialias(va, rendered.pix, rendered.inv, bg_of(ka), clip_of_aa, analysis, vals2=vb,
-                                              background2=None if kb is None else bg_of(kb), keep=keep(ka, va), keep2=None if kb is None else keep(kb, vb))
-            if kb is None:
-                fused[ka] = res
-            else:
-                fused[ka], fused[kb] = res
-        if depth_rec is not None:
-            kb = depth_partner
-            vb = None if kb is None else rendered.peek(kb)
-            res, depth_rows = ops.depth_composite_antialias(depth_rec[0], depth_rec[1], rendered.pix, rendered.inv, clip_of_aa, analysis, vals2=vb,
-                                                            background2=None if kb is None else bg_of(kb), keep2=None if kb is None else keep(kb, vb),
-                                                            return_rows=True)
-            if kb is None:
-                fused["depth"] = res
-            else:
-                fused["depth"], fused[kb] = res
+        depth_rec = getattr(rendered, "depth_recipe", None) if "depth" in fuse_keys else None  # 'depth' from the G-buffer rows
+
+        def call(ka, va, bg, keep, kb, second):
+            if va is not None:
+                return ops.composite_antialias(va, rendered.pix, rendered.inv, bg, clip_of_aa, analysis, keep=keep, **second)
+            if ka != "depth":  # (the colour still a recipe: shaded on the fly)
+                return ops.shade_composite_antialias(rendered.shade_recipe, rendered.pix, rendered.inv, bg, clip_of_aa, analysis, **second)
+            res, depth_rows = ops.depth_composite_antialias(depth_rec[0], depth_rec[1], rendered.pix, rendered.inv, clip_of_aa, analysis, return_rows=True,
+                                                            **second)
             if LAST_POINTS[0] is not None:
                 LAST_POINTS[0]["depth"] = depth_rows
+            return res
+
+        _composite_modes(fuse_keys, rendered, background, background4, call, fused, on_the_fly=True, depth_last=depth_rec is not None)
     if LAST_POINTS[0] is not None:
         LAST_POINTS[0]["clip"] = clip_f.detach()
     assert getattr(rendered, "depth_recipe", None) is None or "depth" in fused  # (_fused_depth_tangent admits 'depth' only where the compositor runs)
@@ -683,15 +701,7 @@ def render_mesh(ctx, mesh, mtx_in, w2c, view_pos, material, lgt, resolution, spp
                 analysis = ops.AAAnalysis(rast, clip_f, ops.aa_topology(tri32, clip_f.shape[1]))
             accum = ops.antialias(accum.contiguous().float(), rast, clip_f, tri, analysis=analysis)
         out = util.avg_pool_nhwc(accum, spp) if spp > 1 else accum
-        if key in ("kd", "ks", "normal", "geo_normal", "tangent"):
-            out = out[..., :3]
-        elif key in ("shading", "depth"):
-            out = out[..., :1]
-        elif key == "flow":
-            out = out[..., :2]
-        elif key == "dino_pred":
-            out = out[..., :-1]
-        out_buffers.append(out.permute(0, 3, 1, 2))
+        out_buffers.append(_slice_mode(key, out).permute(0, 3, 1, 2))
     return out_buffers
 
 
@@ -733,50 +743,18 @@ def _render_mesh_msaa(mesh, clip_f, tri, w2c, view_pos, material, lgt, resolutio
                  class_vector=class_vector, cover=None)
     analysis = ops.AAAnalysis(rast, clip_f, ops.aa_topology(ops.tri_int32(tri), clip_f.shape[1]))
 
-    def bg_of(k):
-        if background is None or k not in ("shaded", "geo_normal", "shading"):
-            return None
-        # ('shading': the last two channels of the background with its zero alpha appended, render.py:254-256, 307-308)
-        return torch.cat((background[..., 2:3], torch.zeros_like(background[..., 0:1])), dim=-1) if k == "shading" else background
-
-    keep_of = {"kd": 3, "ks": 3, "normal": 3, "geo_normal": 3, "shading": 1, "flow": 2, "dino_pred": -1}
-    vals_of = lambda k: rendered.peek(k) if dict.__contains__(rendered, k) else rendered[k]
     null_of = lambda k: null[k][:, 0, 0, :-1].expand(B, -1)
-
-    def keep(k, vals):
-        n = keep_of.get(k)
-        return None if n is None else (vals.shape[-1] if n == -1 else n)
-
     keys = [k for k in dict.fromkeys(render_modes) if k in rendered]
     done = {}
     for aa in (True, False):
-        group = [k for k in keys if (k in ANTIALIASED_MODES) == aa]
-        for i in range(0, len(group), 2):
-            ka, kb = group[i], (group[i + 1] if i + 1 < len(group) else None)
-            va, vb = vals_of(ka), (None if kb is None else vals_of(kb))
-            res = ops.msaa_composite_antialias(va, null_of(ka), rendered.pix, rendered.inv, rast, bg_of(ka), clip_f, analysis, s, antialias=aa,
-                                               vals2=vb, null_vals2=None if kb is None else null_of(kb), background2=None if kb is None else bg_of(kb),
-                                               keep=keep(ka, va), keep2=None if kb is None else keep(kb, vb))
-            if kb is None:
-                done[ka] = res
-            else:
-                done[ka], done[kb] = res
+        def call(ka, va, bg, keep, kb, second):
+            return ops.msaa_composite_antialias(va, null_of(ka), rendered.pix, rendered.inv, rast, bg, clip_f, analysis, s,
+                                                antialias=aa, null_vals2=None if kb is None else null_of(kb), keep=keep, **second)
+
+        _composite_modes([k for k in keys if (k in ANTIALIASED_MODES) == aa], rendered, background, None, call, done)
     if LAST_POINTS[0] is not None:
         LAST_POINTS[0]["clip"] = clip_f.detach()
     return [done[k].permute(0, 3, 1, 2) if k in done else None for k in render_modes]
-
-
-def _slice_mode(key, out):
-    """Channel selection per render mode (reference render.py:320-331)."""
-    if key in ("kd", "ks", "normal", "geo_normal", "tangent"):
-        return out[..., :3]
-    if key in ("shading", "depth"):
-        return out[..., :1]
-    if key == "flow":
-        return out[..., :2]
-    if key == "dino_pred":
-        return out[..., :-1]
-    return out
 
 
 def _render_mesh_layers(mesh, clip_f, tri, w2c, view_pos, material, lgt, resolution, spp, num_layers, msaa, background, bsdf, feat, render_modes,

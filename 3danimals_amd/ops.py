@@ -1707,120 +1707,142 @@ def _image_gradient_in_place(g, H, W):
     return g, g.stride(2), g.shape[3]
 
 
-class _CompositeAntialias(torch.autograd.Function):
-    """One or two buffers (vals2 None = one) against the same pixel list and crossing records, in the same launches.
+class _CaBuf:
+    """One buffer of a compositor call, first or second alike: rows ``vals`` [>= P,C] (None: the call computes them itself, ``C`` given),
+    ``null_vals`` [B,C] (supersampled calls only), ``background`` [1|B,h,w,<= C+1] or None, on the grid (B, h, w) of the images.  The only
+    place that builds an a3d_ca_buffer.  The description holds numbers only: ``of`` hands the normalised tensors back, the node saves
+    them and passes them in again.
 
-    ``keep`` / ``keep2``: leading channels of the composited image that are materialised and handed out (None = all C + 1): render_mesh
-    returns 'dino_pred' and 'flow' without their alpha channel (render.py:320-331) -- here that channel is never written, the image comes
-    out contiguous in the channels the caller keeps, and its gradient arrives without a SliceBackward (a zero fill and a strided copy of
-    the whole image) in front of it.
-    Shading recipe (``gb`` .. ``all_tex`` given, ``vals`` None): the first buffer's colour is kd * shading computed inside the launches,
-    and the backward of this node runs the shading adjoint too (a3d_shade_bwd_rows): g_gb [P,12], the gradient of the texture field's
-    output rows [rows,T] and of w2c / view_pos / light in their own layouts.
-    ``vals`` / ``vals2`` / ``all_tex`` may have MORE rows than the list (the fields' padded point list): the extra rows are never read and
-    their gradient rows are written as zeros by the same launches."""
-
-    @staticmethod
-    def forward(ctx, vals, vals2, clip, pix, inv, bg, bg2, analysis, keep, keep2, gb, w2c, view, light, all_tex, two_sided):
-        require_device(vals, vals2, pix, inv, gb, all_tex, what="composite_antialias")
-        a = analysis
-        P = pix.shape[0]
-        assert pix.dtype == torch.int64 and inv.shape == (a.B * a.H * a.W,) and inv.dtype == torch.int32
-        shade = gb is not None
-        dev = pix.device
-
-        def prep(v, g, k):
-            if v is None:
-                return None, None, 0, None
-            v = f32c(v)
-            assert v.shape[0] >= P
-            C = v.shape[1]
-            if g is not None:
-                g = f32c(g)
-                assert g.shape[1:3] == (a.H, a.W) and g.shape[3] <= C + 1 and g.shape[0] in (1, a.B)
-            k = C + 1 if k is None else int(k)
-            assert 1 <= k <= C + 1
-            return v, g, C, torch.empty((a.B, a.H, a.W, k), dtype=torch.float32, device=dev)  # (only the channels handed out are materialised)
-
-        par_struct = sh = g_par = None
-        if shade:
-            assert vals is None and light is not None
-            ctx.view_shape = view.shape
-            gb, w2c, view, light, all_tex = f32c(gb), f32c(w2c), f32c(view.reshape(-1, 3)), f32c(light), f32c(all_tex)
-            assert gb.shape == (P, 12) and all_tex.shape[0] >= P and all_tex.shape[1] >= 3 and w2c.shape[1] == w2c.shape[2] and w2c.shape[1] in (3, 4)
-            assert all(t.shape[0] in (1, a.B) for t in (w2c, view, light)) and light.shape[1] == 5
-            bg = None if bg is None else f32c(bg)
-            assert bg is None or (bg.shape[1:3] == (a.H, a.W) and bg.shape[3] <= 4 and bg.shape[0] in (1, a.B))
-            if bg is not None and bg.shape[3] == 4 and bg.data_ptr() % 16:  # (an offset view: the compose kernel reads 4-channel texels as 16-byte loads)
-                bg = bg.clone()
-            C, out = 3, torch.empty((a.B, a.H, a.W, 4), dtype=torch.float32, device=dev)
-            # gradients of the per-image tensors: accumulated by the backward with atomics into ONE buffer (cleared by the forward's
-            # first launch), handed out as views in the tensors' own shapes
-            if any(ctx.needs_input_grad[11:14]):
-                g_par = torch.empty(w2c.numel() + view.numel() + light.numel(), dtype=torch.float32, device=dev)
-            par_struct = _shade_params(w2c, view, light)
-            # (the colours the compose launch computes are kept, 12 B per point: the blend launch and the backward read them as value rows)
-            shaded = torch.empty((P, 3), dtype=torch.float32, device=dev) if KEEP_SHADED_COLOUR else None
-            sh = _lib.CaShade(size=ctypes.sizeof(_lib.CaShade), kd_stride=all_tex.stride(0), gb=ptr(gb), par=None, kd=ptr(all_tex), clear=ptr(g_par),
-                              n_clear=0 if g_par is None else g_par.numel(), two_sided=int(two_sided), params=ctypes.addressof(par_struct),
-                              shaded_out=ptr(shaded))
-        else:
-            vals, bg, C, out = prep(vals, bg, keep)
-        vals2, bg2, C2, out2 = prep(vals2, bg2, keep2)
-        ctag = lambda c, o: f"C{c + 1}" if o.shape[3] == c + 1 else f"C{c + 1}>{o.shape[3]}"  # (C17>16: a 17-channel composite of which 16 channels are materialised)
-        tag = f"[{ctag(C, out)}]" if vals2 is None else f"[{ctag(C, out)}+{ctag(C2, out2)}]"
-        ride = a.ride_args()  # a deferred analysis runs inside the first launch of this call
-        buf = lambda v, c, g, o: _lib.CaBuffer(size=ctypes.sizeof(_lib.CaBuffer), C=c, vals=ptr(v), bg=ptr(g), out=ptr(o), bg_batch=0 if g is None else g.shape[0],
-                                               bg_channels=0 if g is None else g.shape[3], out_channels=o.shape[3])
-        first, second = buf(None if shade else vals, C, bg, out), (buf(vals2, C2, bg2, out2) if vals2 is not None else None)
-        call("a3d_composite_aa_fwd", ctypes.addressof(first), None if second is None else ctypes.addressof(second), ptr(inv), ptr(a.work), ptr(a.count),
-             a.capacity, a.B, a.H, a.W, None if ride is None else ctypes.addressof(ride), None if sh is None else ctypes.addressof(sh), stream(),
-             tag=tag + ("[+shade]" if shade else "") + ("[+analysis]" if ride is not None else ""))
-        if ride is not None:
-            a.pending = False  # (only now: the call above raises on a refused argument)
-        ctx.save_for_backward(shaded if shade else vals, vals2, pix, inv, bg, bg2, gb, w2c, view, light, all_tex)
-        ctx.analysis, ctx.tag, ctx.g_par, ctx.two_sided, ctx.shade = a, tag, g_par, int(bool(two_sided)), shade
-        ctx.set_materialize_grads(False)
-        return out, out2
+    ``keep``: leading channels of the composited image that are materialised and handed out (None = all C + 1): render_mesh returns
+    'dino_pred' and 'flow' without their alpha channel (render.py:320-331) -- here that channel is never written, the image comes out
+    contiguous in the channels the caller keeps, and its gradient arrives without a SliceBackward (a zero fill and a strided copy of the
+    whole image) in front of it.
+    ``vals`` may have MORE rows than the list (the fields' padded point list): the extra rows are never read and their gradient rows are
+    written as zeros by the same launches."""
+    __slots__ = ("C", "k", "rows", "grid", "spp")
 
     @staticmethod
-    def backward(ctx, g_out, g_out2=None):
-        vals, vals2, pix, inv, bg, bg2, gb, w2c, view, light, all_tex = ctx.saved_tensors
-        a, shade = ctx.analysis, ctx.shade
-        P = pix.shape[0]
-        dev = pix.device
-        C = 3 if shade else vals.shape[1]
-        two = vals2 is not None
-        C2 = vals2.shape[1] if two else 0
-        if g_out is None:  # (an output nobody differentiated: zero gradient)
-            g_out = torch.zeros((a.B, a.H, a.W, C + 1), dtype=torch.float32, device=dev)
-        if two and g_out2 is None:
-            g_out2 = torch.zeros((a.B, a.H, a.W, C2 + 1), dtype=torch.float32, device=dev)
-        g_out, gs, gc = _image_gradient_in_place(g_out, a.H, a.W)
-        if two:
-            g_out2, gs2, gc2 = _image_gradient_in_place(g_out2, a.H, a.W)
-        rows = P if shade else vals.shape[0]
-        g_vals = torch.empty((rows, C), dtype=torch.float32, device=dev)  # (shade: the gradient of the shaded colour, consumed below)
-        g_vals2 = torch.empty_like(vals2) if two else None
-        g_clip = torch.empty_like(a.clip)
-        par_struct = sh = None
-        if shade:
-            par_struct = _shade_params(w2c, view, light)
-            if vals is None:  # (no kept colours: the backward's kernels re-derive them from the recipe)
-                sh = _lib.CaShade(size=ctypes.sizeof(_lib.CaShade), kd_stride=all_tex.stride(0), gb=ptr(gb), par=None, kd=ptr(all_tex), clear=None, n_clear=0,
-                                  two_sided=ctx.two_sided, params=ctypes.addressof(par_struct))
-        buf = lambda v, c, g, go, gst, gch, gv, nrows: _lib.CaBuffer(size=ctypes.sizeof(_lib.CaBuffer), C=c, vals=ptr(v), bg=ptr(g), g_out=ptr(go), g_vals=ptr(gv),
-                                                                     bg_batch=0 if g is None else g.shape[0], bg_channels=0 if g is None else g.shape[3],
-                                                                     g_stride=gst, g_channels=gch, vals_rows=nrows)
-        first = buf(vals, C, bg, g_out, gs, gc, g_vals, rows)  # (shade: ``vals`` = the colours the forward kept, or None)
-        second = buf(vals2, C2, bg2, g_out2, gs2, gc2, g_vals2, vals2.shape[0]) if two else None
-        call("a3d_composite_aa_bwd", ctypes.addressof(first), None if second is None else ctypes.addressof(second), ptr(pix), P, ptr(inv), ptr(a.work),
-             ptr(a.count), a.capacity, ptr(a.clip), a.clip.shape[0], ptr(a.topo.tri), a.B, a.clip.shape[1], a.topo.tri.shape[0], a.H, a.W, ptr(g_clip),
-             None if sh is None else ctypes.addressof(sh), stream(), tag=ctx.tag)
-        if not shade:
-            return (g_vals, g_vals2, g_clip) + (None,) * 13
+    def of(vals, null_vals, background, keep, grid, P, spp, C=None):
+        """(description, (vals, null_vals, background) as float32 contiguous tensors); ``spp``: None or (s, aa)."""
+        B, h, w = grid
+        if vals is not None:
+            vals = f32c(vals)
+            assert vals.shape[0] >= P
+            C = vals.shape[1]
+        if spp is not None:
+            null_vals = f32c(null_vals)
+            assert null_vals.shape == (B, C)
+        if background is not None:
+            background = f32c(background)
+            assert background.shape[1:3] == (h, w) and background.shape[3] <= C + 1 and background.shape[0] in (1, B)
+        b = _CaBuf()
+        b.C, b.k, b.rows, b.grid, b.spp = C, (C + 1 if keep is None else int(keep)), (P if vals is None else vals.shape[0]), grid, spp
+        assert 1 <= b.k <= C + 1
+        return b, (vals, null_vals, background)
+
+    def struct(self, tensors, rast_full):
+        vals, null_vals, bg = tensors
+        st = _lib.CaBuffer(size=ctypes.sizeof(_lib.CaBuffer), C=self.C, vals=ptr(vals), bg=ptr(bg), bg_batch=0 if bg is None else bg.shape[0],
+                           bg_channels=0 if bg is None else bg.shape[3])
+        if self.spp is not None:  # (at spp 1 the supersampling fields stay zero: the library tells the modes apart by them)
+            st.spp, st.aa = self.spp
+            st.cover_rast, st.null_vals = ptr(rast_full), ptr(null_vals)
+        return st
+
+    def forward(self, tensors, rast_full, dev):
+        """(the struct of the forward call, ``out``: only the channels handed out are materialised)."""
+        out = torch.empty(self.grid + (self.k,), dtype=torch.float32, device=dev)
+        st = self.struct(tensors, rast_full)
+        st.out, st.out_channels = ptr(out), self.k
+        return st, out
+
+    def backward(self, tensors, g_out, rast_full, dev):
+        """(the struct of the backward call, g_vals, g_null or None, the gradient image the struct points to) for the saved ``tensors``
+        and the incoming gradient ``g_out``."""
+        if g_out is None:
+            # an output nobody differentiated: zeros in the shape of the image that was handed out, which is what autograd itself would
+            # materialise (k channels; the channels past g_channels have no gradient anyway)
+            g_out = torch.zeros(self.grid + (self.k,), dtype=torch.float32, device=dev)
+        g_out, gs, gc = _image_gradient_in_place(g_out, self.grid[1], self.grid[2])
+        g_vals = torch.empty((self.rows, self.C), dtype=torch.float32, device=dev)
+        st = self.struct(tensors, rast_full)
+        st.g_out, st.g_vals, st.g_stride, st.g_channels, st.vals_rows = ptr(g_out), ptr(g_vals), gs, gc, self.rows
+        g_null = None
+        if self.spp is not None:
+            g_null = torch.empty_like(tensors[1])
+            st.g_null = ptr(g_null)
+        return st, g_vals, g_null, g_out
+
+    def tag(self, cut):
+        """'C17', or 'C17>16' for a 17-channel composite of which 16 channels are materialised (``cut``: the tag says so)."""
+        return f"C{self.C + 1}>{self.k}" if cut and self.k != self.C + 1 else f"C{self.C + 1}"
+
+
+class _Source:
+    """What the first buffer of a compositor call is made of.  Stateless: what a call must remember goes on its ``ctx`` or into the saved
+    tensors.  ``forward`` -> (a3d_ca_shade of the forward call or None, the rows the call computes and keeps as the backward's value rows,
+    further non-differentiable outputs, tensors to save); ``backward`` -> (a3d_ca_shade of the backward call or None, what ``finish``
+    needs); ``finish`` -> the tail of the backward: the gradients of (gb, w2c, view, light, all_tex).  This one: plain value rows."""
+    C = None  # channels of the first buffer when the call computes its rows
+    name = None  # stands for the first buffer in the tag
+    cut_in_tag = True  # a buffer's cut channels show in the tag ('C17>16')
+    suffix = ""  # of the forward's tag
+    what = "composite_antialias"
+
+    def forward(self, ctx, tensors, pix, grid, dev):
+        return None, None, (), ()
+
+    def backward(self, ctx, kept, saved, pix, dev):
+        return None, None
+
+    def finish(self, ctx, state, g_vals, saved, pix, grid, dev):
+        return (None,) * 5
+
+
+class _Shaded(_Source):
+    """The colour is kd * shading of a ShadeRecipe's tensors, computed inside the launches; the backward runs the shading adjoint too
+    (a3d_shade_bwd_rows): g_gb [P,12], the gradient of the texture field's output rows [rows,T] and of w2c / view_pos / light in their
+    own layouts."""
+    C = 3
+    suffix = "[+shade]"
+
+    def __init__(self, two_sided):
+        self.two_sided = int(two_sided)
+
+    def forward(self, ctx, tensors, pix, grid, dev):
+        gb, w2c, view, light, all_tex = tensors
+        assert light is not None
+        B, P = grid[0], pix.shape[0]
+        ctx.view_shape = view.shape
+        gb, w2c, view, light, all_tex = f32c(gb), f32c(w2c), f32c(view.reshape(-1, 3)), f32c(light), f32c(all_tex)
+        assert gb.shape == (P, 12) and all_tex.shape[0] >= P and all_tex.shape[1] >= 3 and w2c.shape[1] == w2c.shape[2] and w2c.shape[1] in (3, 4)
+        assert all(t.shape[0] in (1, B) for t in (w2c, view, light)) and light.shape[1] == 5
+        # gradients of the per-image tensors: accumulated by the backward with atomics into ONE buffer (cleared by the forward's
+        # first launch), handed out as views in the tensors' own shapes
+        ctx.g_par = g_par = None
+        if any(ctx.needs_input_grad[8:11]):
+            ctx.g_par = g_par = torch.empty(w2c.numel() + view.numel() + light.numel(), dtype=torch.float32, device=dev)
+        par = _shade_params(w2c, view, light)
+        # (the colours the compose launch computes are kept, 12 B per point: the blend launch and the backward read them as value rows)
+        kept = torch.empty((P, 3), dtype=torch.float32, device=dev) if KEEP_SHADED_COLOUR else None
+        sh = _lib.CaShade(size=ctypes.sizeof(_lib.CaShade), kd_stride=all_tex.stride(0), gb=ptr(gb), par=None, kd=ptr(all_tex), clear=ptr(g_par),
+                          n_clear=0 if g_par is None else g_par.numel(), two_sided=self.two_sided, params=ctypes.addressof(par), shaded_out=ptr(kept))
+        sh.holds = par  # (``params`` is its address)
+        return sh, kept, (), (gb, w2c, view, light, all_tex)
+
+    def backward(self, ctx, kept, saved, pix, dev):
+        gb, w2c, view, light, all_tex = saved
+        par = _shade_params(w2c, view, light)
+        if kept is not None:
+            return None, par
+        # (no kept colours: the backward's kernels re-derive them from the recipe)
+        return _lib.CaShade(size=ctypes.sizeof(_lib.CaShade), kd_stride=all_tex.stride(0), gb=ptr(gb), par=None, kd=ptr(all_tex), clear=None, n_clear=0,
+                            two_sided=self.two_sided, params=ctypes.addressof(par)), par
+
+    def finish(self, ctx, par, g_vals, saved, pix, grid, dev):
         # the shading adjoint in the same node: g_vals -> G-buffer rows, texture rows (kd columns; the other columns and the padding rows
         # zero), camera / light tensors -- each in the layout its consumer reads
+        gb, w2c, view, light, all_tex = saved
         g_par, ctx.g_par = ctx.g_par, None  # (cleared by the forward's first launch; serves ONE backward)
         if g_par is None:
             g_par = torch.zeros(w2c.numel() + view.numel() + light.numel(), dtype=torch.float32, device=dev)
@@ -1829,9 +1851,96 @@ class _CompositeAntialias(torch.autograd.Function):
         g_struct = _shade_params(g_w2c, g_view, g_light)
         g_gb = torch.empty_like(gb)
         g_tex = torch.empty_like(all_tex)
-        call("a3d_shade_bwd_rows", ptr(g_vals), ptr(gb), ctypes.addressof(par_struct), ctypes.addressof(g_struct), ptr(pix), a.H * a.W, ptr(all_tex),
-             all_tex.stride(0), P, ctx.two_sided, ptr(g_gb), ptr(g_tex), all_tex.shape[1], all_tex.shape[0], stream())
-        return (None, g_vals2, g_clip) + (None,) * 7 + (g_gb, g_w2c, g_view.view(ctx.view_shape), g_light, g_tex, None)
+        call("a3d_shade_bwd_rows", ptr(g_vals), ptr(gb), ctypes.addressof(par), ctypes.addressof(g_struct), ptr(pix), grid[1] * grid[2], ptr(all_tex),
+             all_tex.stride(0), pix.shape[0], self.two_sided, ptr(g_gb), ptr(g_tex), all_tex.shape[1], all_tex.shape[0], stream())
+        return g_gb, g_w2c, g_view.view(ctx.view_shape), g_light, g_tex
+
+
+class _Depth(_Source):
+    """The 'depth' render mode (a3d_ca_shade.depth_*, csrc/antialias.hip): per-image range over the point list, one normalised value per
+    point, composited over zeros and antialiased by the same call; the backward runs the compositor's gather and blend adjoints and then
+    the range / normalisation adjoint -> g_gb [P,12] (position columns only).  Further output: the [P] depth rows, not differentiable.
+    (The mode is cut to 1 channel, render.py:324-325: the alpha is never written.)"""
+    C = 1
+    name = "depth"
+    cut_in_tag = False
+    what = "depth_composite_antialias"
+
+    def forward(self, ctx, tensors, pix, grid, dev):
+        B, P = grid[0], pix.shape[0]
+        gb, w2c = f32c(tensors[0]), f32c(tensors[1])
+        assert gb.shape == (P, 12) and w2c.dim() == 3 and w2c.shape[1:] == (4, 4) and w2c.shape[0] in (1, B)
+        rows = torch.empty((P,), dtype=torch.float32, device=dev)
+        state = torch.empty((B, 8), dtype=torch.int32, device=dev)
+        return _depth_source(gb, w2c, pix, state, rows, None), None, (rows,), (gb, w2c, rows, state)
+
+    def backward(self, ctx, kept, saved, pix, dev):
+        gb, w2c, rows, state = saved
+        g_gb = torch.empty_like(gb)
+        slots = torch.empty((pix.shape[0], 4), dtype=torch.float32, device=dev)  # (cleared by the call)
+        return _depth_source(gb, w2c, pix, state, rows, g_gb, slots), (g_gb, slots)
+
+    def finish(self, ctx, state, g_vals, saved, pix, grid, dev):
+        return (state[0], None, None, None, None)
+
+
+_ROWS, _DEPTH, _SHADED = _Source(), _Depth(), (_Shaded(False), _Shaded(True))
+
+
+class _Compositor(torch.autograd.Function):
+    """The fused compositor (a3d_composite_aa_fwd / _bwd): one or two buffers (vals2 None = one) against the same pixel list and crossing
+    records, in the same launches.  ``src`` (a _Source) says what the first buffer is made of.  ``opts`` = (pix, inv, background,
+    background2, analysis, keep, keep2, spp): what autograd need not see; ``spp`` = (s, aa) puts the call in supersampled mode
+    (a3d_ca_buffer.spp > 1): rows and backgrounds on the SHADING grid [B,h,w], composited with the coverage of ``rast_full``,
+    antialiased with the full-resolution crossing records and averaged per s x s block -- without any full-resolution image -- with the
+    per-image null rows as further differentiable inputs.  Returns (image, second image or None) + the source's further outputs."""
+
+    @staticmethod
+    def forward(ctx, src, opts, vals, null_vals, vals2, null_vals2, clip, gb, w2c, view, light, all_tex, rast_full):
+        pix, inv, bg, bg2, a, keep, keep2, spp = opts
+        require_device(vals, null_vals, vals2, null_vals2, pix, inv, rast_full, gb, w2c, all_tex, what=src.what if spp is None else "msaa_composite_antialias")
+        P, dev = pix.shape[0], pix.device
+        grid = (a.B, a.H, a.W)
+        assert src.C is None or (vals is None and spp is None)
+        if spp is not None:
+            a.ensure()  # (the riding analysis is an spp 1 optimisation)
+            s = int(spp[0])
+            assert 2 <= s <= 8 and a.H % s == 0 and a.W % s == 0
+            grid, rast_full, spp = (a.B, a.H // s, a.W // s), f32c(rast_full.detach()), (s, int(bool(spp[1])))
+            assert rast_full.shape == (a.B, a.H, a.W, 4)
+        assert pix.dtype == torch.int64 and inv.shape == (grid[0] * grid[1] * grid[2],) and inv.dtype == torch.int32
+        first, t1 = _CaBuf.of(vals, null_vals, bg, keep, grid, P, spp, C=src.C)
+        second, t2 = (None, (None,) * 3) if vals2 is None else _CaBuf.of(vals2, null_vals2, bg2, keep2, grid, P, spp)
+        sh, kept, outputs, src_saved = src.forward(ctx, (gb, w2c, view, light, all_tex), pix, grid, dev)
+        cut = src.cut_in_tag and spp is None
+        tag = ("" if spp is None else f"[spp{spp[0]}]") + "[" + (src.name or first.tag(cut)) + ("" if second is None else "+" + second.tag(cut)) + "]"
+        ride = a.ride_args() if spp is None else None  # a deferred analysis runs inside the first launch of this call
+        (sa, out), (sb, out2) = first.forward(t1, rast_full, dev), ((None, None) if second is None else second.forward(t2, rast_full, dev))
+        call("a3d_composite_aa_fwd", ctypes.addressof(sa), None if sb is None else ctypes.addressof(sb), ptr(inv), ptr(a.work), ptr(a.count),
+             a.capacity, a.B, a.H, a.W, None if ride is None else ctypes.addressof(ride), None if sh is None else ctypes.addressof(sh), stream(),
+             tag=tag + src.suffix + ("[+analysis]" if ride is not None else ""))
+        if ride is not None:
+            a.pending = False  # (only now: the call above raises on a refused argument)
+        # (the first buffer's rows in the backward: the caller's, or what the source kept of the ones the call computed -- or None)
+        ctx.save_for_backward(pix, inv, rast_full, t1[0] if src.C is None else kept, t1[1], t1[2], *t2, *src_saved)
+        ctx.analysis, ctx.tag, ctx.src, ctx.first, ctx.second = a, tag, src, first, second
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(*outputs)
+        return (out, out2) + outputs
+
+    @staticmethod
+    def backward(ctx, g_out, g_out2=None, *_):
+        pix, inv, rast_full, *t = ctx.saved_tensors
+        a, src, first, second, P, dev = ctx.analysis, ctx.src, ctx.first, ctx.second, pix.shape[0], pix.device
+        sa, g_vals, g_null, g_out = first.backward(t[0:3], g_out, rast_full, dev)
+        sb, g_vals2, g_null2, g_out2 = (None,) * 4 if second is None else second.backward(t[3:6], g_out2, rast_full, dev)
+        g_clip = torch.empty_like(a.clip)
+        sh, state = src.backward(ctx, t[0], t[6:], pix, dev)
+        call("a3d_composite_aa_bwd", ctypes.addressof(sa), None if sb is None else ctypes.addressof(sb), ptr(pix), P, ptr(inv), ptr(a.work),
+             ptr(a.count), a.capacity, ptr(a.clip), a.clip.shape[0], ptr(a.topo.tri), a.B, a.clip.shape[1], a.topo.tri.shape[0], a.H, a.W, ptr(g_clip),
+             None if sh is None else ctypes.addressof(sh), stream(), tag=ctx.tag)
+        g_src = src.finish(ctx, state, g_vals, t[6:], pix, first.grid, dev)
+        return (None, None, None if src.C is not None else g_vals, g_null, g_vals2, g_null2, g_clip) + g_src + (None,)
 
 
 def _shade_params(w2c, view, light):
@@ -1842,119 +1951,44 @@ def _shade_params(w2c, view, light):
                             light_image_stride=0 if light.shape[0] == 1 else 5)
 
 
-def composite_antialias(vals, pix, inv, background, clip, analysis, vals2=None, background2=None, keep=None, keep2=None):
-    """antialias(lerp(background, [vals, 1], coverage)) for a buffer given as rows ``vals`` [>= P,C] at the covered pixels ``pix`` (``inv`` =
-    the pixel -> row map of covered_pixels(return_inverse=True)): [B,H,W,C+1].  ``background`` [1|B,H,W,<= C+1] (missing trailing channels
-    = 0: the reference's 3-channel background as it is) or None (zeros); it gets no gradient (callers with a differentiable background
-    composite with torch and call antialias).  With ``vals2`` (and ``background2``) a second buffer over the same pixels is composited
-    and antialiased by the same launches: returns the pair of images.  ``keep`` / ``keep2``: see _CompositeAntialias."""
-    assert background is None or not background.requires_grad
-    assert background2 is None or not background2.requires_grad
-    if clip.dim() == 2:
-        clip = clip[None]
-    o1, o2 = _CompositeAntialias.apply(vals, vals2, clip, pix, inv, background, background2, analysis, keep, keep2, None, None, None, None, None, True)
-    return o1 if vals2 is None else (o1, o2)
-
-
-def shade_composite_antialias(recipe, pix, inv, background, clip, analysis, vals2=None, background2=None, keep2=None):
-    """composite_antialias for the shaded colour of ``recipe`` (a ShadeRecipe) as first buffer: the colour is computed inside the launches,
-    and one backward node runs compositor gather + shading adjoint (see _CompositeAntialias)."""
-    assert background is None or not background.requires_grad
-    assert background2 is None or not background2.requires_grad
-    if clip.dim() == 2:
-        clip = clip[None]
-    r = recipe
-    o1, o2 = _CompositeAntialias.apply(None, vals2, clip, pix, inv, background, background2, analysis, None, keep2, r.gb, r.w2c, r.view_pos, r.light,
-                                       r.all_tex, r.two_sided)
-    return o1 if vals2 is None else (o1, o2)
-
-
-class _DepthCompositeAntialias(torch.autograd.Function):
-    """The 'depth' render mode as the first buffer of a compositor call (a3d_ca_shade.depth_*, csrc/antialias.hip): per-image range over
-    the point list, one normalised value per point, composited over zeros and antialiased by the same call; the backward node runs the
-    compositor's gather and blend adjoints and then the range / normalisation adjoint -> g_gb [P,12] (position columns only).  A second
-    buffer rides as in _CompositeAntialias.  Returns (image [B,H,W,1], second image or None, the [P] depth rows -- not differentiable)."""
-
-    @staticmethod
-    def forward(ctx, gb, vals2, clip, w2c, pix, inv, bg2, analysis, keep2):
-        require_device(gb, vals2, w2c, pix, inv, what="depth_composite_antialias")
-        a = analysis
-        P = pix.shape[0]
-        dev = pix.device
-        assert pix.dtype == torch.int64 and inv.shape == (a.B * a.H * a.W,) and inv.dtype == torch.int32
-        gb, w2c = f32c(gb), f32c(w2c)
-        assert gb.shape == (P, 12) and w2c.dim() == 3 and w2c.shape[1:] == (4, 4) and w2c.shape[0] in (1, a.B)
-        out2 = None
-        C2 = 0
-        if vals2 is not None:
-            vals2 = f32c(vals2)
-            assert vals2.shape[0] >= P
-            C2 = vals2.shape[1]
-            if bg2 is not None:
-                bg2 = f32c(bg2)
-                assert bg2.shape[1:3] == (a.H, a.W) and bg2.shape[3] <= C2 + 1 and bg2.shape[0] in (1, a.B)
-            k2 = C2 + 1 if keep2 is None else int(keep2)
-            assert 1 <= k2 <= C2 + 1
-            out2 = torch.empty((a.B, a.H, a.W, k2), dtype=torch.float32, device=dev)
-        out = torch.empty((a.B, a.H, a.W, 1), dtype=torch.float32, device=dev)  # (the mode is cut to 1 channel, render.py:324-325: alpha never written)
-        rows = torch.empty((P,), dtype=torch.float32, device=dev)
-        state = torch.empty((a.B, 8), dtype=torch.int32, device=dev)
-        ride = a.ride_args()
-        sh = _depth_source(gb, w2c, pix, state, rows, None)
-        first = _lib.CaBuffer(size=ctypes.sizeof(_lib.CaBuffer), C=1, vals=None, bg=None, out=ptr(out), bg_batch=0, out_channels=1)
-        second = None if vals2 is None else _lib.CaBuffer(size=ctypes.sizeof(_lib.CaBuffer), C=C2, vals=ptr(vals2), bg=ptr(bg2), out=ptr(out2),
-                                                          bg_batch=0 if bg2 is None else bg2.shape[0], bg_channels=0 if bg2 is None else bg2.shape[3],
-                                                          out_channels=out2.shape[3])
-        tag = "[depth]" if vals2 is None else f"[depth+C{C2 + 1}]"
-        call("a3d_composite_aa_fwd", ctypes.addressof(first), None if second is None else ctypes.addressof(second), ptr(inv), ptr(a.work), ptr(a.count),
-             a.capacity, a.B, a.H, a.W, None if ride is None else ctypes.addressof(ride), ctypes.addressof(sh), stream(),
-             tag=tag + ("[+analysis]" if ride is not None else ""))
-        if ride is not None:
-            a.pending = False
-        ctx.save_for_backward(gb, vals2, w2c, pix, inv, bg2, rows, state)
-        ctx.analysis, ctx.tag = a, tag
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(rows)
-        return out, out2, rows
-
-    @staticmethod
-    def backward(ctx, g_out, g_out2=None, _g_rows=None):
-        gb, vals2, w2c, pix, inv, bg2, rows, state = ctx.saved_tensors
-        a = ctx.analysis
-        P = pix.shape[0]
-        dev = pix.device
-        two = vals2 is not None
-        C2 = vals2.shape[1] if two else 0
-        if g_out is None:
-            g_out = torch.zeros((a.B, a.H, a.W, 1), dtype=torch.float32, device=dev)
-        if two and g_out2 is None:
-            g_out2 = torch.zeros((a.B, a.H, a.W, C2 + 1), dtype=torch.float32, device=dev)
-        g_out, gs, gc = _image_gradient_in_place(g_out, a.H, a.W)
-        if two:
-            g_out2, gs2, gc2 = _image_gradient_in_place(g_out2, a.H, a.W)
-        g_rows = torch.empty((P, 1), dtype=torch.float32, device=dev)
-        g_vals2 = torch.empty_like(vals2) if two else None
-        g_clip = torch.empty_like(a.clip)
-        g_gb = torch.empty_like(gb)
-        slots = torch.empty((P, 4), dtype=torch.float32, device=dev)  # (cleared by the call)
-        sh = _depth_source(gb, w2c, pix, state, rows, g_gb, slots)
-        first = _lib.CaBuffer(size=ctypes.sizeof(_lib.CaBuffer), C=1, vals=None, bg=None, g_out=ptr(g_out), g_vals=ptr(g_rows), bg_batch=0,
-                              g_stride=gs, g_channels=gc, vals_rows=P)
-        second = None if not two else _lib.CaBuffer(size=ctypes.sizeof(_lib.CaBuffer), C=C2, vals=ptr(vals2), bg=ptr(bg2), g_out=ptr(g_out2),
-                                                    g_vals=ptr(g_vals2), bg_batch=0 if bg2 is None else bg2.shape[0],
-                                                    bg_channels=0 if bg2 is None else bg2.shape[3], g_stride=gs2, g_channels=gc2,
-                                                    vals_rows=vals2.shape[0])
-        call("a3d_composite_aa_bwd", ctypes.addressof(first), None if second is None else ctypes.addressof(second), ptr(pix), P, ptr(inv), ptr(a.work),
-             ptr(a.count), a.capacity, ptr(a.clip), a.clip.shape[0], ptr(a.topo.tri), a.B, a.clip.shape[1], a.topo.tri.shape[0], a.H, a.W, ptr(g_clip),
-             ctypes.addressof(sh), stream(), tag=ctx.tag)
-        return g_gb, g_vals2, g_clip, None, None, None, None, None, None
-
-
 def _depth_source(gb, w2c, pix, state, rows, g_gb, slots=None):
     """a3d_ca_shade carrying only the depth source: row 2 of w2c [1|B,4,4] read in place."""
     return _lib.CaShade(size=ctypes.sizeof(_lib.CaShade), depth_gb=ptr(gb), depth_w2c_row=w2c.data_ptr() + 8 * 4,
                         depth_w2c_stride=0 if w2c.shape[0] == 1 else 16, depth_pix=ptr(pix), depth_rows=pix.shape[0], depth_state=ptr(state),
                         depth_out=ptr(rows), g_depth_gb=ptr(g_gb), g_depth_slots=ptr(slots))
+
+
+def _composite(src, pix, inv, clip, analysis, vals=None, vals2=None, background=None, background2=None, keep=None, keep2=None, null_vals=None,
+               null_vals2=None, recipe=(None,) * 5, rast_full=None, msaa=None):
+    """What the public functions below share: the backgrounds get no gradient, one clip batch, (image[, second image]) + further outputs."""
+    assert background is None or not background.requires_grad
+    assert background2 is None or not background2.requires_grad
+    if clip.dim() == 2:
+        clip = clip[None]
+    o1, o2, *more = _Compositor.apply(src, (pix, inv, background, background2, analysis, keep, keep2, msaa), vals, null_vals, vals2, null_vals2, clip, *recipe,
+                                      rast_full)
+    return (o1 if vals2 is None else (o1, o2)), more
+
+
+def composite_antialias(vals, pix, inv, background, clip, analysis, vals2=None, background2=None, keep=None, keep2=None):
+    """antialias(lerp(background, [vals, 1], coverage)) for a buffer given as rows ``vals`` [>= P,C] at the covered pixels ``pix`` (``inv`` =
+    the pixel -> row map of covered_pixels(return_inverse=True)): [B,H,W,C+1].  ``background`` [1|B,H,W,<= C+1] (missing trailing channels
+    = 0: the reference's 3-channel background as it is) or None (zeros); it gets no gradient (callers with a differentiable background
+    composite with torch and call antialias).  With ``vals2`` (and ``background2``) a second buffer over the same pixels is composited
+    and antialiased by the same launches: returns the pair of images.  ``keep`` / ``keep2``: see _CaBuf."""
+    return _composite(_ROWS, pix, inv, clip, analysis, vals, vals2, background, background2, keep, keep2)[0]
+
+
+def shade_composite_antialias(recipe, pix, inv, background, clip, analysis, vals2=None, background2=None, keep2=None):
+    """composite_antialias for the shaded colour of ``recipe`` (a ShadeRecipe) as first buffer: the colour is computed inside the launches,
+    and one backward node runs compositor gather + shading adjoint (see _Shaded)."""
+    r = recipe
+    if background is not None:
+        background = f32c(background)
+        if background.shape[3] == 4 and background.data_ptr() % 16:  # (an offset view: the compose kernel reads 4-channel texels as 16-byte loads)
+            background = background.clone()
+    return _composite(_SHADED[bool(r.two_sided)], pix, inv, clip, analysis, None, vals2, background, background2, None, keep2,
+                      recipe=(r.gb, r.w2c, r.view_pos, r.light, r.all_tex))[0]
 
 
 def depth_composite_antialias(gb, w2c, pix, inv, clip, analysis, vals2=None, background2=None, keep2=None, return_rows=False):
@@ -1964,86 +1998,8 @@ def depth_composite_antialias(gb, w2c, pix, inv, clip, analysis, vals2=None, bac
     With ``vals2`` a second buffer rides in the same launches as in composite_antialias: returns the pair.  Differentiable in ``gb``
     (position columns) and ``clip`` (and ``vals2``); ``w2c`` gets no gradient.  ``return_rows``: also the [P] normalised depth rows."""
     assert not w2c.requires_grad, "depth_composite_antialias: w2c gets no gradient here (render_mesh takes the generic path for it)"
-    assert background2 is None or not background2.requires_grad
-    if clip.dim() == 2:
-        clip = clip[None]
-    o1, o2, rows = _DepthCompositeAntialias.apply(gb, vals2, clip, w2c, pix, inv, background2, analysis, keep2)
-    res = o1 if vals2 is None else (o1, o2)
+    res, (rows,) = _composite(_DEPTH, pix, inv, clip, analysis, None, vals2, None, background2, 1, keep2, recipe=(gb, w2c, None, None, None))
     return (res, rows) if return_rows else res
-
-
-class _MsaaCompositeAntialias(torch.autograd.Function):
-    """The compositor in supersampled mode (a3d_ca_buffer.spp > 1, csrc/antialias.hip): one or two buffers given as rows on the SHADING grid
-    [B,h,w], composited with the full-resolution coverage, antialiased with the full-resolution crossing records and averaged per
-    s x s block -- without any full-resolution image.  Gradients: the rows, the per-image null rows, the clip positions."""
-
-    @staticmethod
-    def forward(ctx, vals, null_vals, vals2, null_vals2, clip, pix, inv, rast_full, bg, bg2, analysis, spp, aa, keep, keep2):
-        require_device(vals, null_vals, vals2, null_vals2, pix, inv, rast_full, what="msaa_composite_antialias")
-        a = analysis.ensure()  # (the riding analysis is an spp 1 optimisation)
-        s = int(spp)
-        assert 2 <= s <= 8 and a.H % s == 0 and a.W % s == 0
-        h, w = a.H // s, a.W // s
-        P = pix.shape[0]
-        rast_full = f32c(rast_full.detach())
-        assert rast_full.shape == (a.B, a.H, a.W, 4) and pix.dtype == torch.int64 and inv.shape == (a.B * h * w,) and inv.dtype == torch.int32
-        dev = pix.device
-
-        def prep(v, nv, g, k):
-            if v is None:
-                return None, None, None, 0, None
-            v, nv = f32c(v), f32c(nv)
-            C = v.shape[1]
-            assert v.shape[0] >= P and nv.shape == (a.B, C)
-            if g is not None:
-                g = f32c(g)
-                assert g.shape[1:3] == (h, w) and g.shape[3] <= C + 1 and g.shape[0] in (1, a.B)
-            k = C + 1 if k is None else int(k)
-            assert 1 <= k <= C + 1
-            return v, nv, g, C, torch.empty((a.B, h, w, k), dtype=torch.float32, device=dev)
-
-        vals, null_vals, bg, C, out = prep(vals, null_vals, bg, keep)
-        vals2, null_vals2, bg2, C2, out2 = prep(vals2, null_vals2, bg2, keep2)
-        tag = f"[spp{s}][C{C + 1}]" if vals2 is None else f"[spp{s}][C{C + 1}+C{C2 + 1}]"
-        buf = lambda v, nv, c, g, o: _lib.CaBuffer(size=ctypes.sizeof(_lib.CaBuffer), C=c, vals=ptr(v), bg=ptr(g), out=ptr(o), bg_batch=0 if g is None else g.shape[0],
-                                                   bg_channels=0 if g is None else g.shape[3], out_channels=o.shape[3], spp=s, aa=int(bool(aa)),
-                                                   cover_rast=ptr(rast_full), null_vals=ptr(nv))
-        first, second = buf(vals, null_vals, C, bg, out), (buf(vals2, null_vals2, C2, bg2, out2) if vals2 is not None else None)
-        call("a3d_composite_aa_fwd", ctypes.addressof(first), None if second is None else ctypes.addressof(second), ptr(inv), ptr(a.work), ptr(a.count),
-             a.capacity, a.B, a.H, a.W, None, None, stream(), tag=tag)
-        ctx.save_for_backward(vals, null_vals, vals2, null_vals2, pix, inv, rast_full, bg, bg2)
-        ctx.analysis, ctx.tag, ctx.spp, ctx.aa = a, tag, s, int(bool(aa))
-        ctx.set_materialize_grads(False)
-        return out, out2
-
-    @staticmethod
-    def backward(ctx, g_out, g_out2=None):
-        vals, null_vals, vals2, null_vals2, pix, inv, rast_full, bg, bg2 = ctx.saved_tensors
-        a, s = ctx.analysis, ctx.spp
-        h, w = a.H // s, a.W // s
-        P, dev = pix.shape[0], pix.device
-        two = vals2 is not None
-        C, C2 = vals.shape[1], (vals2.shape[1] if two else 0)
-        if g_out is None:
-            g_out = torch.zeros((a.B, h, w, C + 1), dtype=torch.float32, device=dev)
-        if two and g_out2 is None:
-            g_out2 = torch.zeros((a.B, h, w, C2 + 1), dtype=torch.float32, device=dev)
-        g_out, gs, gc = _image_gradient_in_place(g_out, h, w)
-        if two:
-            g_out2, gs2, gc2 = _image_gradient_in_place(g_out2, h, w)
-        g_vals, g_null = torch.empty_like(vals), torch.empty_like(null_vals)
-        g_vals2, g_null2 = (torch.empty_like(vals2), torch.empty_like(null_vals2)) if two else (None, None)
-        g_clip = torch.empty_like(a.clip)
-        buf = lambda v, nv, c, g, go, gst, gch, gv, gn: _lib.CaBuffer(size=ctypes.sizeof(_lib.CaBuffer), C=c, vals=ptr(v), bg=ptr(g), g_out=ptr(go), g_vals=ptr(gv),
-                                                                      bg_batch=0 if g is None else g.shape[0], bg_channels=0 if g is None else g.shape[3],
-                                                                      g_stride=gst, g_channels=gch, vals_rows=v.shape[0], spp=s, aa=ctx.aa,
-                                                                      cover_rast=ptr(rast_full), null_vals=ptr(nv), g_null=ptr(gn))
-        first = buf(vals, null_vals, C, bg, g_out, gs, gc, g_vals, g_null)
-        second = buf(vals2, null_vals2, C2, bg2, g_out2, gs2, gc2, g_vals2, g_null2) if two else None
-        call("a3d_composite_aa_bwd", ctypes.addressof(first), None if second is None else ctypes.addressof(second), ptr(pix), P, ptr(inv), ptr(a.work),
-             ptr(a.count), a.capacity, ptr(a.clip), a.clip.shape[0], ptr(a.topo.tri), a.B, a.clip.shape[1], a.topo.tri.shape[0], a.H, a.W, ptr(g_clip),
-             None, stream(), tag=ctx.tag)
-        return (g_vals, g_null, g_vals2, g_null2, g_clip) + (None,) * 10
 
 
 def msaa_composite_antialias(vals, null_vals, pix, inv, rast_full, background, clip, analysis, spp, antialias=True, vals2=None, null_vals2=None,
@@ -2054,13 +2010,8 @@ def msaa_composite_antialias(vals, null_vals, pix, inv, rast_full, background, c
     coverage of ``rast_full``))) as [B,h,w,C+1].  ``analysis``: the AAAnalysis of (rast_full, clip), full resolution.  ``background``
     [1|B,h,w,<= C+1] on the shading grid (its nearest up-scale is what the reference composites over) or None; no gradient.
     ``antialias`` False: composite and average only.  A second buffer and ``keep`` / ``keep2`` as in composite_antialias."""
-    assert background is None or not background.requires_grad
-    assert background2 is None or not background2.requires_grad
-    if clip.dim() == 2:
-        clip = clip[None]
-    o1, o2 = _MsaaCompositeAntialias.apply(vals, null_vals, vals2, null_vals2, clip, pix, inv, rast_full, background, background2, analysis, spp,
-                                           antialias, keep, keep2)
-    return o1 if vals2 is None else (o1, o2)
+    return _composite(_ROWS, pix, inv, clip, analysis, vals, vals2, background, background2, keep, keep2, null_vals,
+                      null_vals2, rast_full=rast_full, msaa=(spp, antialias))[0]
 
 
 def antialias(color, rast, clip, tri, analysis=None):
