@@ -115,6 +115,18 @@ FIELD_HEAD_ACT_NONE, FIELD_HEAD_ACT_SIGMOID = 0, 1
 NVV_THREADS = 256
 NVV_MAX_TRIPS = 32
 NVV_KEYPOINT_TILE = 16
+EB_ONE_GROUP_MAX_N = 32  # a3d_estimate_bones: one work-group up to here ...
+EB_ONE_GROUP_MAX_POINTS = 1 << 22
+EB_WIDE_MAX_POINTS = 1 << 24  # ... work-groups of (instance, slab) up to here (torch.quantile's own limit)
+EB_WIDE_SLAB = 1024
+EB_WIDE_FIXED_WORDS = 16640
+EB_WIDE_WORDS_PER_INSTANCE = 15
+EB_WIDE_WORDS_PER_SLAB = 6
+
+
+def eb_wide_workspace_words(N, V):
+    """A3D_EB_WIDE_WORKSPACE_WORDS(N, V) of include/a3d.h: the 4-byte words of workspace a wide a3d_estimate_bones call needs."""
+    return EB_WIDE_FIXED_WORDS + N * (EB_WIDE_WORDS_PER_INSTANCE + EB_WIDE_WORDS_PER_SLAB * ((V + EB_WIDE_SLAB - 1) // EB_WIDE_SLAB))
 
 
 class Surface(NamedTuple):
@@ -226,7 +238,10 @@ SURFACES = (
         "a3d_cubemap_specular_bwd": (_c_int, [_p, _p]),
     }, {"a3d_dmtet_order": DmtetOrder, "a3d_dmtet_emit_opts": DmtetEmitOpts, "a3d_estimate_bones_args": EstimateBonesArgs,
         "a3d_shade_params": ShadeParams, "a3d_rast_opts": RastOpts, "a3d_gb_aux": GbAux, "a3d_aa_ride": AaRide, "a3d_ca_shade": CaShade,
-        "a3d_ca_buffer": CaBuffer, "a3d_tex_desc": TexDesc, "a3d_env_desc": EnvDesc}, {}),
+        "a3d_ca_buffer": CaBuffer, "a3d_tex_desc": TexDesc, "a3d_env_desc": EnvDesc},
+       {"A3D_EB_ONE_GROUP_MAX_N": EB_ONE_GROUP_MAX_N, "A3D_EB_ONE_GROUP_MAX_POINTS": EB_ONE_GROUP_MAX_POINTS,
+        "A3D_EB_WIDE_MAX_POINTS": EB_WIDE_MAX_POINTS, "A3D_EB_WIDE_SLAB": EB_WIDE_SLAB, "A3D_EB_WIDE_FIXED_WORDS": EB_WIDE_FIXED_WORDS,
+        "A3D_EB_WIDE_WORDS_PER_INSTANCE": EB_WIDE_WORDS_PER_INSTANCE, "A3D_EB_WIDE_WORDS_PER_SLAB": EB_WIDE_WORDS_PER_SLAB}),
     Surface("a3d_bsdf.h", {
         "a3d_bsdf_rows": (ctypes.c_int64, [_p]),
         "a3d_bsdf_fwd": (_c_int, [_p, _p]),

@@ -10,6 +10,7 @@
 // factors onto the three angles (summed per link in a fixed order: bit-reproducible).  Bones carry no gradient.
 // A few hundred threads in total; the point is 2 launches instead of ~80 tiny ones on a host-bound stretch of the step.
 #include "bones_common.h"
+#include "eb_common.h"
 
 // ---- one work-group per instance: the K link matrices are built ONCE (one thread each) into LDS, then every bone walks its
 // chain over LDS copies (<= 8 products of 3x4 affines).  The first version rebuilt every link of every chain per thread
@@ -86,16 +87,9 @@ extern "C" int a3d_bone_transforms_bwd(const float* g_M, const float* bones, int
 // reference itself hold to 1e-6 (tests/test_gpu_parity.py::test_estimate_bones_on_device_against_reference_golden).
 #define EB_THREADS 1024
 #define EB_MAXN 32
-#define EB_MAXSEL 12
-#define EB_MAXGROUP 6
+static_assert(EB_MAXN == A3D_EB_ONE_GROUP_MAX_N, "include/a3d.h states which calls the one work-group takes");
 #define EB_COPIES 16
-
-__device__ __forceinline__ unsigned eb_key(float f) {  // monotone float -> uint
-    const unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float eb_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
-__device__ __forceinline__ float eb_lerp(float a, float b, float w) { return w < 0.5f ? a + w * (b - a) : b - (b - a) * (1.f - w); }  // torch.lerp
+// (the keys, the rank arithmetic, the bin search and the closed forms of phase D: eb_common.h, shared with bones_wide.hip)
 
 struct EbArg { float v; int i; };
 
@@ -172,23 +166,12 @@ __device__ __forceinline__ void eb_multiselect(F f, int total, int mg, int* s_ra
         // a planar scratch array, no compaction of the low vertices -- 41.5 -> 38.0 us in the kernel for 128 VGPRs and a 24-byte spill, and the
         // spill's scratch set-up made the Fauna tests run ten times longer end to end: not kept.)
         {
-            const int w = threadIdx.x >> 6, ln = threadIdx.x & 63;
+            const int w = threadIdx.x >> 6;
             for (int t = w; t < m; t += EB_THREADS / 64) {
-                const int4 c = reinterpret_cast<const int4*>(s_hist[s_rep[t]])[ln];
-                const int s4 = c.x + c.y + c.z + c.w;
-                const int incl = a3d_wave_incl_scan(s4), excl = incl - s4;
-                const int r = s_rank[t];
                 const unsigned pre = s_prefix[t];
-                if (r >= excl && r < incl) {  // exactly one lane per target
-                    int b = 4 * ln, base = excl;
-                    if (r >= base + c.x) {
-                        base += c.x; ++b;
-                        if (r >= base + c.y) {
-                            base += c.y; ++b;
-                            if (r >= base + c.z) { base += c.z; ++b; }
-                        }
-                    }
-                    s_rank[t] = r - base;
+                int b, rest;
+                if (eb_find_bin(s_hist[s_rep[t]], s_rank[t], &b, &rest)) {  // exactly one lane per target
+                    s_rank[t] = rest;
                     s_prefix[t] = pass == 0 ? (unsigned)b : ((pre << 8) | (unsigned)b);
                 }
             }
@@ -296,9 +279,9 @@ __global__ __launch_bounds__(EB_THREADS) void eb_kernel(const EbParams a) {
     if (a.n_leg > 0) {
         // ---- phase B: quantiles over ALL values of the call
         auto ranks_of = [&](float q, int n, int slot, float* w_out) {  // pos = q (n - 1), float32 as torch.quantile computes it
-            const float ps = q * (float)(n - 1), lo = floorf(ps), hi = ceilf(ps);
-            s_rank[slot] = max((int)lo, 0); s_rank[slot + 1] = max((int)hi, 0);
-            *w_out = ps - lo;
+            const EbRanks r = eb_ranks_of(q, n);
+            s_rank[slot] = r.lo; s_rank[slot + 1] = r.hi;
+            *w_out = r.w;
         };
         if (!a.fauna) {
             float w95 = 0.f, w05 = 0.f;
@@ -394,35 +377,17 @@ __global__ __launch_bounds__(EB_THREADS) void eb_kernel(const EbParams a) {
     A3D_STAMP(0, 4);
     // ---- phase D: joints and bones, one thread per bone end; every joint is a closed form of the spine ends and the centroid
     __shared__ int s_attach[4];
-    const int nj = a.n_body + 1, half = a.n_body / 2, nb2 = (nj + 1) / 2, K = a.n_body + 4 * a.n_leg;
-    auto joint = [&](int n, int j, float* o) {  // joints_a[:-1] ++ joints_b   (skinning.py:118-126)
-        const float* p = pos + (long long)n * V * 3;
-        const bool head = j < nb2 - 1;
-        const int i = head ? j : j - (nb2 - 1), vi = s_ab[n][head ? 0 : 1];
-        const float e[3] = {0.f, p[3 * vi + 1], p[3 * vi + 2]}, mid[3] = {0.f, s_cent[n][1] + (a.n_leg > 0 ? 0.5f : 0.f), s_cent[n][2]};
-        const float bl = s_blend[i];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) o[c] = head ? e[c] * (1.f - bl) + mid[c] * bl : e[c] * bl + mid[c] * (1.f - bl);
-    };
-    // body bones: (i + 1, i) for the first half, then (i, i + 1) for i = n_body - 1 .. half   (skinning.py:128-141)
-    auto body_end = [&](int n, int bone, int e, float* o) {
-        const int i = bone < half ? bone : a.n_body - 1 - (bone - half);
-        joint(n, bone < half ? (e == 0 ? i + 1 : i) : (e == 0 ? i : i + 1), o);
+    const int K = a.n_body + 4 * a.n_leg;
+    auto spine_of = [&](int n) {  // (the closed forms themselves: eb_common.h)
+        EbSpine s;
+        s.p = pos + (long long)n * V * 3; s.va = s_ab[n][0]; s.vb = s_ab[n][1]; s.cy = s_cent[n][1]; s.cz = s_cent[n][2];
+        s.n_body = a.n_body; s.n_leg = a.n_leg; s.blend = s_blend;
+        return s;
     };
     if (a.n_leg > 0) {
         if (tid < 2) {  // attachment joints (instance 0): nearest body bone end in z to the foot, first index on ties
             int att = a.attach[tid];
-            if (att < 0) {
-                const float fz = pos[3 * s_foot[0][tid] + 2];
-                float bd = INFINITY;
-                att = 0;
-                for (int k = 0; k < a.n_body; ++k) {
-                    float o[3];
-                    body_end(0, k, 1, o);
-                    const float d = fabsf(o[2] - fz);
-                    if (d < bd) { bd = d; att = k; }
-                }
-            }
+            if (att < 0) att = eb_nearest_body_bone(spine_of(0), pos[3 * s_foot[0][tid] + 2]);
             s_attach[tid] = att;
         }
         __syncthreads();
@@ -437,16 +402,12 @@ __global__ __launch_bounds__(EB_THREADS) void eb_kernel(const EbParams a) {
     for (int idx = tid; idx < N * K * 2; idx += EB_THREADS) {
         const int n = idx / (2 * K), r = idx - n * 2 * K, bone = r >> 1, e = r & 1;
         float o[3];
+        const EbSpine s = spine_of(n);
         if (bone < a.n_body) {
-            body_end(n, bone, e, o);
+            eb_body_end(s, bone, e, o);
         } else {  // leg bone i = (joint i + 1, joint i) of the ramp foot -> attachment   (skinning.py:196-215)
             const int l = (bone - a.n_body) / a.n_leg, i = (bone - a.n_body) - l * a.n_leg;
-            const float* foot = pos + (long long)n * V * 3 + 3 * s_foot[n][l];
-            float anchor[3];
-            body_end(n, s_attach[l], 1, anchor);  // bones_pred[:, :, body_bone_idx, 1]
-            const float rm = s_ramp[e == 0 ? i + 1 : i];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) o[c] = foot[c] * (1.f - rm) + anchor[c] * rm;
+            eb_leg_end(s, s.p + 3 * s_foot[n][l], s_attach[l], s_ramp, i, e, o);
         }
         float* out = a.bones + ((long long)n * K + bone) * 6 + 3 * e;
         out[0] = o[0]; out[1] = o[1]; out[2] = o[2];
@@ -456,15 +417,19 @@ __global__ __launch_bounds__(EB_THREADS) void eb_kernel(const EbParams a) {
 
 extern "C" int a3d_estimate_bones(const a3d_estimate_bones_args* args, a3d_stream_t stream) {
     A3D_CHECK_ARG(args && args->size >= sizeof(a3d_estimate_bones_args));
-    A3D_CHECK_ARG(args->pos && args->bones && args->nearest && args->ok && args->workspace && args->N > 0 && args->N <= EB_MAXN && args->V > 0);
-    A3D_CHECK_ARG((long long)args->N * args->V <= (1 << 22) && args->n_body >= 2 && args->n_body % 2 == 0 && args->n_body <= 32 && args->n_leg >= 0 && args->n_leg <= 8);
+    // one work-group (eb_kernel) for the calls it has always taken, the multi-work-group path (bones_wide.hip) for the others: N and V decide
+    const bool wide = args->N > A3D_EB_ONE_GROUP_MAX_N || (long long)args->N * args->V > A3D_EB_ONE_GROUP_MAX_POINTS;
+    A3D_CHECK_ARG(args->pos && args->bones && args->nearest && args->ok && args->workspace && args->N > 0 && args->V > 0);
+    A3D_CHECK_ARG((long long)args->N * args->V <= A3D_EB_WIDE_MAX_POINTS && args->n_body >= 2 && args->n_body % 2 == 0 && args->n_body <= 32 && args->n_leg >= 0 && args->n_leg <= 8);
+    A3D_CHECK_ARG(!wide || ((uintptr_t)args->workspace & 15) == 0);  // (histogram rows are read 16 bytes at a time, keys and sums are 8-byte words)
+    A3D_CHECK_ARG(args->n_leg == 0 || (args->attach[0] < args->n_body && args->attach[1] < args->n_body && args->attach[2] < args->n_body && args->attach[3] < args->n_body));
+    if (wide) return a3d_eb_wide_launch(args, (hipStream_t)stream);
     EbParams p;
     p.pos = args->pos; p.N = args->N; p.V = args->V; p.n_body = args->n_body; p.n_leg = args->n_leg; p.yplus = args->body_mode_y_plus;
     p.fauna = args->use_y_threshold; p.y_q = args->y_threshold;
     for (int i = 0; i < 17; ++i) p.blend[i] = args->blend[i];
     for (int i = 0; i < 9; ++i) p.ramp[i] = args->ramp[i];
     for (int i = 0; i < 4; ++i) p.attach[i] = args->attach[i];
-    A3D_CHECK_ARG(args->n_leg == 0 || ((p.attach[0] < args->n_body && p.attach[1] < args->n_body && p.attach[2] < args->n_body && p.attach[3] < args->n_body)));
     p.bones = args->bones; p.nearest = args->nearest; p.ok = args->ok; p.work = args->workspace;
     hipLaunchKernelGGL(eb_kernel, dim3(1), dim3(EB_THREADS), 0, (hipStream_t)stream, p);
     A3D_LAUNCH_CHECK();

@@ -25,6 +25,7 @@ SOURCES = {
     "dmtet.hip": ["-ffp-contract=off"],
     "skin.hip": [],
     "bones.hip": [],
+    "bones_wide.hip": ["-ffp-contract=off"],
     "normals.hip": ["-ffp-contract=off"],
     "raster.hip": ["-ffp-contract=off"],
     "cover.hip": [],

@@ -78,6 +78,9 @@ def _masked_quantiles(x, mask, qs):
 
 DEVICE_ESTIMATE_BONES = os.environ.get("A3D_DEVICE_ESTIMATE_BONES", "1") != "0"  # estimate_bones as one HIP launch (a3d_estimate_bones); off: the torch restatement below
 
+# ... also for the calls one work-group does not take (more than 32 instances or 2^22 points: csrc/bones_wide.hip); off: those go to the torch restatement
+DEVICE_ESTIMATE_BONES_WIDE = os.environ.get("A3D_ESTIMATE_BONES_WIDE", "1") != "0"
+
 
 def _body_chain(n_body_bones):
     """(bones_to_joints, kinematic_chain) of the spine (reference :128-141)."""
@@ -100,7 +103,7 @@ def _body_chain(n_body_bones):
 
 def _estimate_bones_device(seq_shape, n_body_bones, n_leg_bones, body_bones_mode, compute_kinematic_chain, aux, attach_legs_to_body,
                            legs_to_body_joint_indices, bone_y_threshold):
-    """estimate_bones through a3d_estimate_bones (csrc/bones.hip): ONE launch for the ~245 torch launches of the restatement below; the
+    """estimate_bones through a3d_estimate_bones (csrc/bones.hip, bones_wide.hip): ONE launch (a dozen beyond 32 instances) for the ~245 torch launches of the restatement below; the
     kinematic chain -- a Python structure -- is built here from the two attachment joints the launch hands back (the one read-back of a
     chain rebuild, as before; none with a cached chain).  None: a cached ``aux`` this form does not cover (the caller takes the torch path)."""
     from ..._lib import defer_check, read_back
@@ -159,7 +162,7 @@ def estimate_bones(seq_shape, n_body_bones, resample=False, n_legs=4, n_leg_bone
         seq_shape = pts.transpose(1, 2).reshape(b, -1, n // 4, 3)
 
     if (DEVICE_ESTIMATE_BONES and QUADRANT_POPULATION is None and body_bones_mode in ("z_minmax", "z_minmax_y+")
-            and ops.estimate_bones_device_ok(seq_shape, n_body_bones, n_leg_bones, n_legs)):
+            and ops.estimate_bones_device_ok(seq_shape, n_body_bones, n_leg_bones, n_legs, wide=DEVICE_ESTIMATE_BONES_WIDE)):
         out = _estimate_bones_device(seq_shape, n_body_bones, n_leg_bones, body_bones_mode, compute_kinematic_chain, aux, attach_legs_to_body,
                                      legs_to_body_joint_indices, bone_y_threshold)
         if out is not None:

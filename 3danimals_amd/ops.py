@@ -441,8 +441,8 @@ def _linspace01(n):
 
 
 def estimate_bones_device(seq_shape, n_body_bones, n_leg_bones, body_mode_y_plus, y_threshold, attach):
-    """a3d_estimate_bones: seq_shape [B,F,V,3] (float32, on the GPU) -> (bones [B,F,K,2,3], nearest int32 [2], ok int32 [1]) -- one launch,
-    no host synchronisation.  ``attach``: the four legs' body joints (negative = found on the device, see include/a3d.h); ``y_threshold``
+    """a3d_estimate_bones: seq_shape [B,F,V,3] (float32, on the GPU) -> (bones [B,F,K,2,3], nearest int32 [2], ok int32 [1]) -- one launch
+    of one work-group, or (estimate_bones_is_wide) a dozen launches of many; no host synchronisation either way.  ``attach``: the four legs' body joints (negative = found on the device, see include/a3d.h); ``y_threshold``
     None or Fauna's bone_y_threshold."""
     require_device(seq_shape, what="estimate_bones")
     pos = f32c(seq_shape)
@@ -452,7 +452,9 @@ def estimate_bones_device(seq_shape, n_body_bones, n_leg_bones, body_mode_y_plus
     bones = torch.empty((B, Fr, K, 2, 3), dtype=torch.float32, device=dev)
     nearest = torch.empty(2, dtype=torch.int32, device=dev)
     ok = torch.empty(1, dtype=torch.int32, device=dev)
-    work = torch.empty(3 * B * Fr * V, dtype=torch.float32, device=dev)
+    # the workspace by the header's rule: 3 N V floats for the one work-group, A3D_EB_WIDE_WORKSPACE_WORDS(N, V) words for the wide path
+    work = torch.empty(_lib.eb_wide_workspace_words(B * Fr, V) if estimate_bones_is_wide(B * Fr, V) else 3 * B * Fr * V, dtype=torch.float32,
+                       device=dev)
     a = _lib.EstimateBonesArgs(size=ctypes.sizeof(_lib.EstimateBonesArgs), N=B * Fr, pos=ptr(pos), bones=ptr(bones), nearest=ptr(nearest), ok=ptr(ok), V=V,
                                workspace=ptr(work),
                                n_body=n_body_bones, n_leg=n_leg_bones, body_mode_y_plus=int(bool(body_mode_y_plus)),
@@ -467,10 +469,16 @@ def estimate_bones_device(seq_shape, n_body_bones, n_leg_bones, body_mode_y_plus
     return bones, nearest, ok
 
 
-def estimate_bones_device_ok(seq_shape, n_body_bones, n_leg_bones, n_legs):
-    """Whether a3d_estimate_bones takes this call (else: the torch restatement)."""
+def estimate_bones_is_wide(N, V):
+    """Whether a3d_estimate_bones runs N instances of V vertices on its multi-work-group path (include/a3d.h: N and V alone decide)."""
+    return N > _lib.EB_ONE_GROUP_MAX_N or N * V > _lib.EB_ONE_GROUP_MAX_POINTS
+
+
+def estimate_bones_device_ok(seq_shape, n_body_bones, n_leg_bones, n_legs, wide=True):
+    """Whether a3d_estimate_bones takes this call (else: the torch restatement).  ``wide`` False: only the calls of the one work-group."""
     return (seq_shape.is_cuda and seq_shape.dtype == torch.float32 and seq_shape.dim() == 4 and seq_shape.shape[3] == 3
-            and seq_shape.shape[0] * seq_shape.shape[1] <= 32 and seq_shape.shape[0] * seq_shape.shape[1] * seq_shape.shape[2] <= (1 << 22)
+            and seq_shape.shape[0] * seq_shape.shape[1] * seq_shape.shape[2] <= _lib.EB_WIDE_MAX_POINTS
+            and (wide or not estimate_bones_is_wide(seq_shape.shape[0] * seq_shape.shape[1], seq_shape.shape[2]))
             and seq_shape.shape[2] > 0 and n_body_bones % 2 == 0 and 2 <= n_body_bones <= 32 and 0 <= n_leg_bones <= 8 and (n_leg_bones == 0 or n_legs == 4))
 
 

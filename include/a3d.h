@@ -180,15 +180,33 @@ int a3d_skin_bwd(const float* g_out, const float* v, int v_batch, const float* b
  * The same pair exists for a3d_shade_fwd / _bwd (g_par) and a3d_gbuffer_fwd / _bwd (g_rows).) */
 
 /* ------------------------------------------------------------------------------------------------
- * (403) estimate_bones on the device -- the heuristic skeleton of /root/reference/model/geometry/skinning.py:50-248 as ONE
- * launch: pos[N,V,3] (N = B x F instances, <= 32) -> bones[N, n_body + 4 n_leg, 2, 3].  Spine: the extreme-z vertices (body_mode_y_plus:
+ * (403) estimate_bones on the device -- the heuristic skeleton of /root/reference/model/geometry/skinning.py:50-248:
+ * pos[N,V,3] (N = B x F instances) -> bones[N, n_body + 4 n_leg, 2, 3].  Spine: the extreme-z vertices (body_mode_y_plus:
  * among those not far below the centroid, 'z_minmax_y+'), snapped to x = 0, joined through the lifted centroid; blend[ceil((n_body+1)/2)] =
  * linspace(0, 1, .) of the caller.  Legs (n_leg > 0): the lowest vertex of each top-view quadrant -- margins from the 5 % / 95 % quantiles of
  * x over ALL values of the call, or (use_y_threshold: Fauna) quadrants centred on the medians of x and z among the vertices below the
  * y_threshold quantile of y -- joined to body joint attach[l] by n_leg bones, ramp[n_leg + 1] = linspace(0, 1, .).  attach[0], attach[1] < 0:
  * found here (nearest body bone end in z, instance 0) and attach[2], attach[3] < 0: copies of attach[1], attach[0] (skinning.py:187-216).
  * nearest[2] = the attachment joints of legs 0 / 1 as used (what the caller's kinematic chain needs: its ONE read-back), ok[1] = 0 when a
- * quadrant held no vertex (the reference drops into pdb there, :183; the foot is then vertex 0). */
+ * quadrant held no vertex (the reference drops into pdb there, :183; the foot is then vertex 0).
+ * Which path a call takes depends on N and V alone:
+ *   N <= A3D_EB_ONE_GROUP_MAX_N and N V <= A3D_EB_ONE_GROUP_MAX_POINTS: ONE launch of one work-group; workspace = 3 N V floats.
+ *   otherwise, up to N V <= A3D_EB_WIDE_MAX_POINTS (beyond it the reference's tensor.quantile() itself refuses its input): work-groups
+ *   of (instance, slab of A3D_EB_WIDE_SLAB vertices), 3 launches without legs, 8 with, 12 with use_y_threshold, every dependency between
+ *   work-groups a launch boundary; integer atomics and fixed-order sums only, so the bits repeat from call to call.  No planar copies;
+ *   workspace = A3D_EB_WIDE_WORKSPACE_WORDS(N, V) 4-byte words, 16-byte aligned: A3D_EB_WIDE_FIXED_WORDS of histograms and select
+ *   state, A3D_EB_WIDE_WORDS_PER_INSTANCE per instance (six 64-bit arg-extremum keys, the centroid) and A3D_EB_WIDE_WORDS_PER_SLAB per
+ *   (instance, slab) (three partial sums in double) -- for small V more than the 3 N V floats of the one-group path.  The call clears
+ *   what it needs of it.
+ * Either way the call validates before it launches, synchronises nothing and allocates nothing; a null workspace is refused. */
+#define A3D_EB_ONE_GROUP_MAX_N 32
+#define A3D_EB_ONE_GROUP_MAX_POINTS 4194304
+#define A3D_EB_WIDE_MAX_POINTS 16777216
+#define A3D_EB_WIDE_SLAB 1024
+#define A3D_EB_WIDE_FIXED_WORDS 16640
+#define A3D_EB_WIDE_WORDS_PER_INSTANCE 15
+#define A3D_EB_WIDE_WORDS_PER_SLAB 6
+#define A3D_EB_WIDE_WORKSPACE_WORDS(N, V) ((size_t)A3D_EB_WIDE_FIXED_WORDS + (size_t)(N) * (A3D_EB_WIDE_WORDS_PER_INSTANCE + (size_t)A3D_EB_WIDE_WORDS_PER_SLAB * (((size_t)(V) + A3D_EB_WIDE_SLAB - 1) / A3D_EB_WIDE_SLAB)))
 typedef struct a3d_estimate_bones_args {
     uint32_t size;
     int32_t N;
@@ -205,8 +223,9 @@ typedef struct a3d_estimate_bones_args {
     int32_t attach[4];
     float blend[17];
     float ramp[9];
-    float* workspace; /* [3 N V] floats of scratch: the select passes read a planar copy of the coordinate they rank (and, Fauna, the
-                         compacted x / z of the low vertices) instead of striding through pos again */
+    float* workspace; /* one work-group: [3 N V] floats of scratch -- the select passes read a planar copy of the coordinate they rank (and,
+                         Fauna, the compacted x / z of the low vertices) instead of striding through pos again; the wide path:
+                         A3D_EB_WIDE_WORKSPACE_WORDS(N, V) words, see above */
 } a3d_estimate_bones_args;
 int a3d_estimate_bones(const a3d_estimate_bones_args* args, a3d_stream_t stream);
 
