@@ -34,6 +34,10 @@
 #define RS_EMPTY 0xFFFFFFFFFFFFFFFFull
 #define RS_BIG 512          // boxes above this many pixels go through the tile stage
 #define RS_TILE_CHUNK 512   // tiles tested per round of the work-group (survivors <= this: the LDS list cannot overflow)
+// absolute part of the tile test's and the row span's ``tol``: below 2^-126 a float carries an absolute error of up to 2^-150 per
+// operation, not a relative one, and a tolerance that is a fraction of the products' size vanishes with them -- next to a vertex
+// whose w is denormal the edge functions live there (~13 roundings each in the culls' polynomial and in rs_frag: ~28 denormal steps)
+#define RS_TOL_ABS 4e-44f
 
 // the vertex-normals job that may ride in the triangle launch (a3d_rast_fwd: normals_*)
 struct RsNormalsJob {
@@ -93,8 +97,11 @@ __device__ __forceinline__ RsFrag rs_frag(const float4 p0, const float4 p1, cons
     return r;
 }
 
-__device__ __forceinline__ unsigned rs_order(float f) {  // monotone float -> uint
-    unsigned u = __float_as_uint(f);
+// monotone float -> uint.  -0 is taken as +0 first: as bit patterns -0 ranks strictly in front of +0, while the oracle's f.zw < best_z
+// holds them equal and gives the pixel to the lower id -- clip-space z = -0 yields z/w = -0 for either winding, and two coplanar
+// triangles at +0 and -0 came out by depth instead of by id (tests/raster_cases.py: signed_zero_pair; also in the peel's ``prev`` key)
+__device__ __forceinline__ unsigned rs_order(float f) {
+    unsigned u = __float_as_uint(f == 0.f ? 0.f : f);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
@@ -115,13 +122,17 @@ __device__ __forceinline__ void rs_row_span(const float4 p0, const float4 p1, co
         const float4 u = pp[(k + 1) % 3], v = pp[(k + 2) % 3];
         const float C = u.x * v.y - u.y * v.x, A = -(u.w * v.y - u.y * v.w), Bc = -(u.x * v.w - u.w * v.x);
         const float tol = 5e-6f * ((fabsf(u.x * v.y) + fabsf(u.y * v.x)) + 2.f * (fabsf(u.w * v.y) + fabsf(u.y * v.w)) + 2.f * (fabsf(u.x * v.w) + fabsf(u.w * v.x))
-                                   + 2.f * fabsf(u.w * v.w) * fx_abs_max * fabsf(fy));
+                                   + 2.f * fabsf(u.w * v.w) * fx_abs_max * fabsf(fy)) + RS_TOL_ABS;
         const float D = C + Bc * fy;
         if (A != 0.f) {
             const float rA = 1.f / A;
             const float tp = (-tol - D) * rA, tn = (tol - D) * rA;  // a_k >= -tol  <=>  A fx >= -tol - D ;  a_k <= tol  <=>  A fx <= tol - D
-            if (A > 0.f) { lo_p = fmaxf(lo_p, tp); hi_n = fminf(hi_n, tn); }
-            else { hi_p = fminf(hi_p, tp); lo_n = fmaxf(lo_n, tn); }
+            // (|A| so small that its reciprocal overflows -- an edge at a vertex with a denormal w --: tp, tn are +-inf whatever the true
+            // quotients, and an inf on the wrong side emptied the span; such an edge bounds nothing here)
+            if (fabsf(rA) < INFINITY) {
+                if (A > 0.f) { lo_p = fmaxf(lo_p, tp); hi_n = fminf(hi_n, tn); }
+                else { hi_p = fminf(hi_p, tp); lo_n = fmaxf(lo_n, tn); }
+            }
         } else {
             none_p = none_p || (D < -tol);
             none_n = none_n || (D > tol);
@@ -354,7 +365,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
                     // (+ the q1x q2y products' own w w f f terms, which cancel in exact arithmetic but not in their rounding: they
                     // dominate when two vertices project next to the NDC origin and the tile lies far from it)
                     const float tol = 5e-6f * ((fabsf(u.x * v.y) + fabsf(u.y * v.x)) + 2.f * (fabsf(u.w * v.y) + fabsf(u.y * v.w)) + 2.f * (fabsf(u.x * v.w) + fabsf(u.w * v.x))
-                                               + 2.f * fabsf(u.w * v.w) * (fabsf(fx) + hx) * (fabsf(fy) + hy));
+                                               + 2.f * fabsf(u.w * v.w) * (fabsf(fx) + hx) * (fabsf(fy) + hy)) + RS_TOL_ABS;
                     const float vk = C + A * fx + Bc * fy, ext = fabsf(A) * hx + fabsf(Bc) * hy + tol;
                     pos = pos && (vk + ext >= 0.f);
                     neg = neg && (vk - ext <= 0.f);

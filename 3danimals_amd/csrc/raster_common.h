@@ -13,8 +13,16 @@ __device__ __forceinline__ int rs_box(const float4 p0, const float4 p1, const fl
         const float r0 = __builtin_amdgcn_rcpf(p0.w), r1 = __builtin_amdgcn_rcpf(p1.w), r2 = __builtin_amdgcn_rcpf(p2.w);
         const float sx0 = p0.x * r0, sx1 = p1.x * r1, sx2 = p2.x * r2;
         const float sy0 = p0.y * r0, sy1 = p1.y * r1, sy2 = p2.y * r2;
-        const float mnx = fminf(sx0, fminf(sx1, sx2)), mxx = fmaxf(sx0, fmaxf(sx1, sx2));
-        const float mny = fminf(sy0, fminf(sy1, sy2)), mxy = fmaxf(sy0, fmaxf(sy1, sy2));
+        float mnx = fminf(sx0, fminf(sx1, sx2)), mxx = fmaxf(sx0, fmaxf(sx1, sx2));
+        float mny = fminf(sy0, fminf(sy1, sy2)), mxy = fmaxf(sy0, fmaxf(sy1, sy2));
+        // a projected coordinate that is not finite says nothing about where the vertex lies: the reciprocal of a denormal w is +inf,
+        // x = 0 then gives 0 * inf = NaN, which fminf / fmaxf DROP -- the box shrank to the hull of the other two vertices and the
+        // triangle lost its pixels (the oracle's 0 / w is 0) --, and a denormal x gives +-inf where x / w is on screen.  Every pixel
+        // is a candidate then, as for a triangle that straddles the eye plane.  (The sum of the magnitudes is inf or NaN exactly when
+        // one of them is, or -- above ~5e37 -- when it overflows: the full frame is conservative there too.)
+        if (!(((fabsf(sx0) + fabsf(sx1)) + fabsf(sx2)) + ((fabsf(sy0) + fabsf(sy1)) + fabsf(sy2)) < INFINITY)) {
+            mnx = -INFINITY; mny = -INFINITY; mxx = INFINITY; mxy = INFINITY;
+        }
         // pixel centres px+0.5 inside [min,max], widened by 1/32 px (coverage itself is decided by rs_frag)
         const float fx0 = ceilf((mnx + 1.f) * 0.5f * W - 0.53125f), fx1 = floorf((mxx + 1.f) * 0.5f * W - 0.46875f);
         const float fy0 = ceilf((mny + 1.f) * 0.5f * H - 0.53125f), fy1 = floorf((mxy + 1.f) * 0.5f * H - 0.46875f);

@@ -67,8 +67,8 @@ static frag_t frag(const float* p0, const float* p1, const float* p2, float fx, 
 /* pos [B,V,4] (or [1,V,4] with pos_batch==1), tri [F,3], out rast [B,H,W,4].
  * prev (NULL or [B,H,W,4]) = the previous depth layer (DepthPeeler.rasterize_next_layer, layer n > 0): a fragment is eligible only
  * where the previous layer is non-empty and only if it lies strictly behind it in (z/w, triangle id) order. */
-int a3d_ref_rasterize_peel(const float* pos, int pos_batch, const int32_t* tri, int B, int V, int F, int H, int W,
-                           const float* prev, float* rast) {
+static int rasterize_impl(const float* pos, int pos_batch, const int32_t* tri, int B, int V, int F, int H, int W,
+                          const float* prev, int whole_frame, float* rast) {
     const float xs = 2.f / (float)W, xo = 1.f / (float)W - 1.f;
     const float ys = 2.f / (float)H, yo = 1.f / (float)H - 1.f;
     size_t npix = (size_t)H * W;
@@ -83,7 +83,9 @@ int a3d_ref_rasterize_peel(const float* pos, int pos_batch, const int32_t* tri, 
             if (i0 < 0 || i0 >= V || i1 < 0 || i1 >= V || i2 < 0 || i2 >= V) continue;
             const float *p0 = pb + 4 * (size_t)i0, *p1 = pb + 4 * (size_t)i1, *p2 = pb + 4 * (size_t)i2;
             int x0 = 0, x1 = W - 1, y0 = 0, y1 = H - 1;
-            if (p0[3] > 0.f && p1[3] > 0.f && p2[3] > 0.f) {
+            if (whole_frame) {
+                /* box-free: frag() decides every pixel of the frame, nothing is culled beforehand */
+            } else if (p0[3] > 0.f && p1[3] > 0.f && p2[3] > 0.f) {
                 /* conservative pixel bounding box: pixel centres px+0.5 inside [min,max] widened by 1/32 px */
                 float sx[3] = {p0[0] / p0[3], p1[0] / p1[3], p2[0] / p2[3]};
                 float sy[3] = {p0[1] / p0[3], p1[1] / p1[3], p2[1] / p2[3]};
@@ -135,6 +137,54 @@ int a3d_ref_rasterize_peel(const float* pos, int pos_batch, const int32_t* tri, 
     return 0;
 }
 
+int a3d_ref_rasterize_peel(const float* pos, int pos_batch, const int32_t* tri, int B, int V, int F, int H, int W,
+                           const float* prev, float* rast) {
+    return rasterize_impl(pos, pos_batch, tri, B, V, F, H, W, prev, 0, rast);
+}
+
 int a3d_ref_rasterize(const float* pos, int pos_batch, const int32_t* tri, int B, int V, int F, int H, int W, float* rast) {
-    return a3d_ref_rasterize_peel(pos, pos_batch, tri, B, V, F, H, W, 0, rast);
+    return rasterize_impl(pos, pos_batch, tri, B, V, F, H, W, 0, 0, rast);
+}
+
+/* The DEFINITION the pixel box, the tile test and the row spans of the HIP kernel are conservative culls of: the unchanged frag() at
+ * every pixel of the frame for every valid triangle, the same winner rule; prev as above (NULL: layer 0).  O(F H W) per image. */
+int a3d_ref_rasterize_whole(const float* pos, int pos_batch, const int32_t* tri, int B, int V, int F, int H, int W,
+                            const float* prev, float* rast) {
+    return rasterize_impl(pos, pos_batch, tri, B, V, F, H, W, prev, 1, rast);
+}
+
+/* Every fragment of every pixel, box-free: count[B,H,W] = how many triangles frag() accepts there, and the first L of them in
+ * (z/w, id) order -- zw[B,H,W,L], id[B,H,W,L] (unused slots: 0, -1).  Layer n of depth peeling is entry n of this list. */
+int a3d_ref_fragments(const float* pos, int pos_batch, const int32_t* tri, int B, int V, int F, int H, int W, int L,
+                      float* zw, int32_t* id, int32_t* count) {
+    const float xs = 2.f / (float)W, xo = 1.f / (float)W - 1.f;
+    const float ys = 2.f / (float)H, yo = 1.f / (float)H - 1.f;
+    size_t npix = (size_t)H * W;
+    for (size_t i = 0; i < (size_t)B * npix; ++i) count[i] = 0;
+    for (size_t i = 0; i < (size_t)B * npix * L; ++i) { zw[i] = 0.f; id[i] = -1; }
+    for (int b = 0; b < B; ++b) {
+        const float* pb = pos + (size_t)(pos_batch == 1 ? 0 : b) * V * 4;
+        for (int t = 0; t < F; ++t) {
+            int i0 = tri[3 * t], i1 = tri[3 * t + 1], i2 = tri[3 * t + 2];
+            if (i0 < 0 || i0 >= V || i1 < 0 || i1 >= V || i2 < 0 || i2 >= V) continue;
+            const float *p0 = pb + 4 * (size_t)i0, *p1 = pb + 4 * (size_t)i1, *p2 = pb + 4 * (size_t)i2;
+            for (int py = 0; py < H; ++py) {
+                float fy = fmaf(ys, (float)py, yo);
+                for (int px = 0; px < W; ++px) {
+                    frag_t f = frag(p0, p1, p2, fmaf(xs, (float)px, xo), fy);
+                    if (!f.hit) continue;
+                    size_t pi = (size_t)b * npix + (size_t)py * W + px;
+                    int n = count[pi]++;
+                    float* z = zw + pi * L;
+                    int32_t* d = id + pi * L;
+                    int k = n < L ? n : L; /* insertion point, from the back: triangles arrive in id order, so a tie stays behind */
+                    while (k > 0 && f.zw < z[k - 1]) --k;
+                    if (k >= L) continue;
+                    for (int m = (n < L ? n : L - 1); m > k; --m) { z[m] = z[m - 1]; d[m] = d[m - 1]; }
+                    z[k] = f.zw; d[k] = t;
+                }
+            }
+        }
+    }
+    return 0;
 }

@@ -37,18 +37,30 @@ def _lib():
         _LIB.a3d_ref_rasterize.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p]
         _LIB.a3d_ref_rasterize_peel.restype = ctypes.c_int
         _LIB.a3d_ref_rasterize_peel.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_void_p]
+        _LIB.a3d_ref_rasterize_whole.restype = ctypes.c_int
+        _LIB.a3d_ref_rasterize_whole.argtypes = _LIB.a3d_ref_rasterize_peel.argtypes
+        _LIB.a3d_ref_fragments.restype = ctypes.c_int
+        _LIB.a3d_ref_fragments.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p] + [ctypes.c_int] * 6 + [ctypes.c_void_p] * 3
     return _LIB
 
 
-def rasterize(pos: torch.Tensor, tri: torch.Tensor, resolution, prev: torch.Tensor = None) -> torch.Tensor:
+def rasterize(pos: torch.Tensor, tri: torch.Tensor, resolution, prev: torch.Tensor = None, whole_frame: bool = False) -> torch.Tensor:
     """dr.rasterize / DepthPeeler layer 0 -> rast [B,H,W,4] = (u, v, z/w, tri_id+1); with ``prev`` (the previous layer) the next
-    depth layer: per pixel the nearest fragment strictly behind the previous one in (z/w, id) order."""
+    depth layer: per pixel the nearest fragment strictly behind the previous one in (z/w, id) order.
+    ``whole_frame``: box-free -- frag() at every pixel of the frame for every valid triangle, O(F H W): the definition every
+    conservative cull (the oracle's own pixel box included) is tested against."""
     H, W = int(resolution[0]), int(resolution[1])
     p = pos.detach().to(torch.float32).contiguous()
     t = tri.to(torch.int32).contiguous()
     B, V = p.shape[0], p.shape[1]
     out = torch.empty(B, H, W, 4, dtype=torch.float32)
-    if prev is None:
+    if whole_frame:
+        pv = None
+        if prev is not None:
+            pv = prev.detach().to(torch.float32).contiguous()
+            assert tuple(pv.shape) == (B, H, W, 4)
+        rc = _lib().a3d_ref_rasterize_whole(p.data_ptr(), B, t.data_ptr(), B, V, t.shape[0], H, W, None if pv is None else pv.data_ptr(), out.data_ptr())
+    elif prev is None:
         rc = _lib().a3d_ref_rasterize(p.data_ptr(), B, t.data_ptr(), B, V, t.shape[0], H, W, out.data_ptr())
     else:
         pv = prev.detach().to(torch.float32).contiguous()
@@ -56,6 +68,21 @@ def rasterize(pos: torch.Tensor, tri: torch.Tensor, resolution, prev: torch.Tens
         rc = _lib().a3d_ref_rasterize_peel(p.data_ptr(), B, t.data_ptr(), B, V, t.shape[0], H, W, pv.data_ptr(), out.data_ptr())
     assert rc == 0
     return out
+
+
+def fragments(pos: torch.Tensor, tri: torch.Tensor, resolution, layers: int):
+    """Box-free list of every pixel's fragments: (count [B,H,W] int32 -- all of them --, zw [B,H,W,layers], id [B,H,W,layers] -- the
+    first ``layers`` in (z/w, id) order, unused slots 0 / -1).  Depth-peeling layer n is entry n."""
+    H, W = int(resolution[0]), int(resolution[1])
+    p = pos.detach().to(torch.float32).contiguous()
+    t = tri.to(torch.int32).contiguous()
+    B, V = p.shape[0], p.shape[1]
+    count = torch.empty(B, H, W, dtype=torch.int32)
+    zw = torch.empty(B, H, W, layers, dtype=torch.float32)
+    ids = torch.empty(B, H, W, layers, dtype=torch.int32)
+    rc = _lib().a3d_ref_fragments(p.data_ptr(), B, t.data_ptr(), B, V, t.shape[0], H, W, int(layers), zw.data_ptr(), ids.data_ptr(), count.data_ptr())
+    assert rc == 0
+    return count, zw, ids
 
 
 def barycentrics(pos: torch.Tensor, tri: torch.Tensor, rast: torch.Tensor) -> torch.Tensor:

@@ -3415,7 +3415,9 @@ def test_rasterize_hard_frames_bit_exact_and_rearmed(case, dev, ops):
     straddlers (boxes of many tiles: the tile stage) and the trained-like mesh of a full step.  Two calls in a row -- the first pays the
     key clear, the second finds the keys re-armed by the first one's resolve (scratch_is_clean) -- leave the same texels, covered-pixel
     block counts and group sums bit for bit; the counts the resolve leaves are those of a stand-alone a3d_cover_count over the same
-    texels; words 1 and 2 of the group-sum area stay zero.  Texels against oracle/raster_ref.c where it finishes in seconds."""
+    texels; words 1 and 2 of the group-sum area stay zero.  Texels against oracle/raster_ref.c where it finishes in seconds: not on
+    'spiky-step' -- the reference that case lacks is held by its small stand-in, 'spiky_small' of tests/raster_cases.py (the same
+    synthetic_spikes on a 720-triangle sphere, 96 x 96, against the box-free oracle: tests/test_raster_adversarial_gpu.py)."""
     from oracle import raster_ref
 
     L = importlib.import_module("3danimals_amd._lib")
