@@ -255,20 +255,6 @@ __device__ __forceinline__ long long aa_record_slot(int r, const int* s_off, int
     return (long long)lo * (capacity / AA_SHARDS) + (r - s_off[lo]);
 }
 
-__global__ __launch_bounds__(256) void aa_fwd_kernel(const float* __restrict__ color, int C, const AaRec* __restrict__ work,
-                                                     const int* __restrict__ count, int capacity, int W, float* __restrict__ out) {
-    __shared__ int s_off[AA_SHARDS + 1];
-    const int n = aa_segment_offsets(count, capacity, s_off);
-    const long long total = (long long)n * C;
-    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
-        const int r = (int)(idx / C), c = (int)(idx - (long long)r * C);
-        const AaRec rec = work[aa_record_slot(r, s_off, capacity)];
-        const long long p0 = rec.pix0, p1 = p0 + ((rec.flags & 1) ? W : 1);
-        const long long dst = rec.alpha > 0.f ? p0 : p1;
-        atomicAdd(out + dst * C + c, rec.alpha * (color[p1 * C + c] - color[p0 * C + c]));
-    }
-}
-
 // d(loss)/d(alpha) of one crossing record pushed onto the two vertices of the crossing edge (clip x, y, w)
 __device__ __forceinline__ void aa_edge_adjoint(const AaRec& rec, unsigned p0, int d, int di, bool use1, float dd, const float4* __restrict__ clip,
                                                 int clip_batch, const int* __restrict__ tri, int V, int H, int W, float xh, float yh,
@@ -303,36 +289,89 @@ __device__ __forceinline__ void aa_edge_adjoint(const AaRec& rec, unsigned p0, i
     atomicAdd(ob + 3, -(gsxb * pbv.x * xh + gsyb * pbv.y * yh) * iwb * iwb);
 }
 
-// 32 lanes per crossing record: lane l takes channels l, l + 32, ... (colour gradients of both pixels, two atomics per channel) and
-// the lanes' partial d(loss)/d(alpha) meet in lane 0, which pushes it onto the two vertices of the crossing edge.  (One thread per
-// record walked the channels serially: 21 us for the 17-channel buffer.)
-__global__ __launch_bounds__(256) void aa_bwd_kernel(const float* __restrict__ g_out, const float* __restrict__ color, int C,
-                                                     const AaRec* __restrict__ work, const int* __restrict__ count, int capacity,
-                                                     const float4* __restrict__ clip, int clip_batch, const int* __restrict__ tri, int V,
-                                                     int H, int W, float* __restrict__ g_color, float* __restrict__ g_clip) {
-    __shared__ int s_off[AA_SHARDS + 1];
-    const int n = aa_segment_offsets(count, capacity, s_off);
+// ---- the back end: ONE walk over the crossing records in each direction.  A source says what differs between the
+// dense image (AaDenseSrc), the composited one (AaCaSrc) and the supersampled one (AaMsSrc): Idx, the index type of a full-resolution pixel
+// (64 bits where no entry point bounds the image); W, its row stride; nc, the channels walked (of out's rows in the blend, those with a
+// gradient in the adjoint); pixel(p), what is looked up once per pixel of a record, and out_index(x), the element of out / g_out it maps
+// to; pre(x, c), the pre-blend value; scale(v), applied to a blend term and to an incoming gradient; kBlendZeros, whether a zero difference
+// is added too; grad(dst, c), the incoming gradient, and sink(x, c, v, role), where the colour adjoint of pixel x goes (role = 2 second + d).
+template <class Src>
+__device__ __forceinline__ void aa_blend_records(const Src& s, float* out, int n, const int* s_off, const AaRec* __restrict__ work, int capacity) {
+    typedef typename Src::Idx Idx;
+    const Idx nc = (Idx)s.nc, total = (Idx)n * nc;  // (Idx unsigned: n <= capacity records, nc <= 4096)
+    for (Idx idx = (Idx)blockIdx.x * AA_SHARDS + threadIdx.x; idx < total; idx += (Idx)gridDim.x * AA_SHARDS) {  // (blockDim.x == AA_SHARDS)
+        const Idx r = idx / nc;
+        const int c = (int)(idx - r * nc);
+        const AaRec rec = work[aa_record_slot((int)r, s_off, capacity)];
+        const Idx p0 = (Idx)rec.pix0, p1 = p0 + ((rec.flags & 1) ? (Idx)s.W : (Idx)1);
+        const typename Src::Px x0 = s.pixel(p0), x1 = s.pixel(p1);
+        const float d = s.pre(x1, c) - s.pre(x0, c);
+        const Idx dst = rec.alpha > 0.f ? s.out_index(x0) : s.out_index(x1);
+        if (Src::kBlendZeros || d != 0.f) atomicAdd(out + (long long)dst * s.nc + c, s.scale(rec.alpha * d));
+    }
+}
+
+// 32 lanes per crossing record: lane l takes channels l, l + 32, ... (colour adjoints of both pixels) and the lanes' partial
+// d(loss)/d(alpha) meet in lane 0, which pushes it onto the two vertices of the crossing edge.  (One thread per record walked the
+// channels serially: 21 us for the 17-channel buffer.)
+template <class Src>
+__device__ __forceinline__ void aa_adjoint_records(const Src& s, int n, const int* s_off, const AaRec* __restrict__ work, int capacity,
+                                                   const float4* __restrict__ clip, int clip_batch, const int* __restrict__ tri, int V, int H,
+                                                   float* __restrict__ g_clip) {
+    typedef typename Src::Idx Idx;
+    const int W = s.W;
     const float xh = 0.5f * W, yh = 0.5f * H;
-    const int sub = threadIdx.x & 31, groups = (gridDim.x * blockDim.x) >> 5;
-    for (int r = (blockIdx.x * blockDim.x + threadIdx.x) >> 5; r < n; r += groups) {
+    const int sub = threadIdx.x & 31, groups = (gridDim.x * AA_SHARDS) >> 5;  // (blockDim.x == AA_SHARDS)
+    for (int r = (blockIdx.x * AA_SHARDS + threadIdx.x) >> 5; r < n; r += groups) {
         const AaRec rec = work[aa_record_slot(r, s_off, capacity)];
         const int d = rec.flags & 1, di = (rec.flags >> 1) & 3;
         const bool use1 = rec.flags & 8, clamped = rec.flags & 16;
-        const long long p0 = rec.pix0, p1 = p0 + (d ? W : 1);
-        const long long dst = rec.alpha > 0.f ? p0 : p1;
+        const Idx p0 = (Idx)rec.pix0, p1 = p0 + (d ? (Idx)W : (Idx)1);
+        const typename Src::Px x0 = s.pixel(p0), x1 = s.pixel(p1);
+        const Idx dst = rec.alpha > 0.f ? s.out_index(x0) : s.out_index(x1);
         float dd = 0.f;
-        for (int c = sub; c < C; c += 32) {
-            const float gd = g_out[dst * C + c];
+        for (int c = sub; c < s.nc; c += 32) {
+            const float gd = s.scale(s.grad(dst, c));
             if (gd != 0.f) {
-                atomicAdd(g_color + p1 * C + c, rec.alpha * gd);
-                atomicAdd(g_color + p0 * C + c, -rec.alpha * gd);
-                dd += gd * (color[p1 * C + c] - color[p0 * C + c]);
+                s.sink(x1, c, rec.alpha * gd, 2 + d);
+                s.sink(x0, c, -rec.alpha * gd, d);
+                dd += gd * (s.pre(x1, c) - s.pre(x0, c));
             }
         }
         dd = a3d_group_sum<32>(dd);  // (a record's 32 lanes are in the same trip)
         if (sub != 0 || clamped || dd == 0.f) continue;
         aa_edge_adjoint(rec, (unsigned)p0, d, di, use1, dd, clip, clip_batch, tri, V, H, W, xh, yh, g_clip);
     }
+}
+
+struct AaDenseSrc {  // a dense [B,H,W,C] image: every channel, every difference, 64-bit indices
+    typedef long long Idx, Px;
+    static constexpr bool kBlendZeros = true;
+    const float *color, *g_out;
+    float* g_color;
+    int W, nc;
+    __device__ Px pixel(Idx p) const { return p; }
+    __device__ Idx out_index(Px x) const { return x; }
+    __device__ float pre(Px x, int c) const { return color[x * nc + c]; }
+    __device__ float scale(float v) const { return v; }
+    __device__ float grad(Idx dst, int c) const { return g_out[dst * nc + c]; }
+    __device__ void sink(Px x, int c, float v, int) const { atomicAdd(g_color + x * nc + c, v); }
+};
+
+__global__ __launch_bounds__(256) void aa_fwd_kernel(const float* __restrict__ color, int C, const AaRec* __restrict__ work,
+                                                     const int* __restrict__ count, int capacity, int W, float* __restrict__ out) {
+    __shared__ int s_off[AA_SHARDS + 1];
+    const int n = aa_segment_offsets(count, capacity, s_off);
+    aa_blend_records(AaDenseSrc{color, nullptr, nullptr, W, C}, out, n, s_off, work, capacity);
+}
+
+__global__ __launch_bounds__(256) void aa_bwd_kernel(const float* __restrict__ g_out, const float* __restrict__ color, int C,
+                                                     const AaRec* __restrict__ work, const int* __restrict__ count, int capacity,
+                                                     const float4* __restrict__ clip, int clip_batch, const int* __restrict__ tri, int V,
+                                                     int H, int W, float* __restrict__ g_color, float* __restrict__ g_clip) {
+    __shared__ int s_off[AA_SHARDS + 1];
+    const int n = aa_segment_offsets(count, capacity, s_off);
+    aa_adjoint_records(AaDenseSrc{color, g_out, g_color, W, C}, n, s_off, work, capacity, clip, clip_batch, tri, V, H, g_clip);
 }
 
 // g_color = g_out (streamed, 16 bytes per lane) and g_clip = 0 in ONE launch (was a device-to-device memcpy + a memset)
@@ -555,26 +594,37 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     else A3D_STAMP(0, 5);
 }
 
+// the composited image as a source of the record walks: values from the job's CaSrc, colour adjoints to the point rows -- or, for the
+// depth source, to the g_slots of each point by its role, as plain stores.  (A constant colour has no adjoint.)
+struct AaCaSrc {
+    typedef unsigned Idx;
+    struct Px { unsigned p; int q; };
+    static constexpr bool kBlendZeros = false;
+    const CaJob& j;
+    int W, nc;
+    __device__ Px pixel(unsigned p) const { return Px{p, ca_point(j.s, p)}; }
+    __device__ unsigned out_index(const Px& x) const { return x.p; }
+    __device__ float pre(const Px& x, int c) const { return ca_pre(j.s, x.p, c); }
+    __device__ float scale(float v) const { return v; }
+    __device__ float grad(unsigned dst, int c) const {
+        // (channels-first: pixel dst = image b, pixel q  ->  (b gS + c) gHW + q = dst + b (gS - 1) gHW + c gHW)
+        return j.gHW ? j.g_out[(long long)dst + ((long long)(dst / (unsigned)j.gHW) * (j.gS - 1) + c) * j.gHW] : j.g_out[(long long)dst * j.gS + c];
+    }
+    __device__ void sink(const Px& x, int c, float v, int role) const {
+        if (c >= j.s.C || x.q < 0) return;
+        if (j.g_slots) j.g_slots[4ll * x.q + role] = v;
+        else if (j.g_vals) atomicAdd(j.g_vals + (long long)x.q * j.s.C + c, v);
+    }
+};
+
 __global__ __launch_bounds__(256) void ca_blend_kernel(CaJob ja, CaJob jb, const AaRec* __restrict__ work, const int* __restrict__ count,
                                                        int capacity, int W) {
     __shared__ int s_off[AA_SHARDS + 1];
     A3D_STAMP(1, 0);
     const CaJob& job = blockIdx.y ? jb : ja;
-    const CaSrc& s = job.s;
-    float* __restrict__ out = job.out;
     const int n = aa_segment_offsets(count, capacity, s_off);
     A3D_STAMP(1, 1);
-    const unsigned C1 = (unsigned)job.oC;
-    const unsigned total = (unsigned)n * C1;  // (n <= capacity records, C1 <= 4096)
-    for (unsigned idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
-        const unsigned ru = idx / C1;
-        const int r = (int)ru, c = (int)(idx - ru * C1);
-        const AaRec rec = work[aa_record_slot(r, s_off, capacity)];
-        const unsigned p0 = (unsigned)rec.pix0, p1 = p0 + ((rec.flags & 1) ? (unsigned)W : 1u);
-        const unsigned dst = rec.alpha > 0.f ? p0 : p1;
-        const float d = ca_pre(s, p1, c) - ca_pre(s, p0, c);
-        if (d != 0.f) atomicAdd(out + (long long)dst * C1 + c, rec.alpha * d);
-    }
+    aa_blend_records(AaCaSrc{job, W, job.oC}, job.out, n, s_off, work, capacity);
     A3D_STAMP(1, 5);
 }
 
@@ -620,47 +670,15 @@ __global__ __launch_bounds__(256) void ca_gather_kernel(CaJob ja, CaJob jb, cons
     A3D_STAMP(2, 5);
 }
 
-// aa_bwd_kernel on the composited image: colours come from the sources, colour adjoints go to the point rows
 __global__ __launch_bounds__(256) void ca_bwd_kernel(CaJob ja, CaJob jb, const AaRec* __restrict__ work, const int* __restrict__ count,
                                                      int capacity, const float4* __restrict__ clip, int clip_batch, const int* __restrict__ tri,
                                                      int V, int H, int W, float* __restrict__ g_clip) {
     __shared__ int s_off[AA_SHARDS + 1];
     A3D_STAMP(3, 0);
     const CaJob& job = blockIdx.y ? jb : ja;
-    const CaSrc& s = job.s;
-    const float* __restrict__ g_out = job.g_out;
-    float* __restrict__ g_vals = job.g_vals;
     const int n = aa_segment_offsets(count, capacity, s_off);
     A3D_STAMP(3, 1);
-    const float xh = 0.5f * W, yh = 0.5f * H;
-    const int C = s.C, C1 = min(s.C + 1, job.gC), gS = job.gS;  // (channels without a gradient contribute nothing)
-    const int sub = threadIdx.x & 31, groups = (gridDim.x * blockDim.x) >> 5;
-    for (int r = (blockIdx.x * blockDim.x + threadIdx.x) >> 5; r < n; r += groups) {
-        const AaRec rec = work[aa_record_slot(r, s_off, capacity)];
-        const int d = rec.flags & 1, di = (rec.flags >> 1) & 3;
-        const bool use1 = rec.flags & 8, clamped = rec.flags & 16;
-        const unsigned p0 = (unsigned)rec.pix0, p1 = p0 + (d ? (unsigned)W : 1u);
-        const unsigned dst = rec.alpha > 0.f ? p0 : p1;
-        const int q0 = ca_point(s, p0), q1 = ca_point(s, p1);
-        float dd = 0.f;
-        for (int c = sub; c < C1; c += 32) {
-            // (channels-first: pixel dst = image b, pixel q  ->  (b gS + c) gHW + q = dst + b (gS - 1) gHW + c gHW)
-            const float gd = job.gHW ? g_out[(long long)dst + ((long long)(dst / (unsigned)job.gHW) * (gS - 1) + c) * job.gHW] : g_out[(long long)dst * gS + c];
-            if (gd != 0.f) {
-                if (c < C && job.g_slots) {
-                    if (q1 >= 0) job.g_slots[4ll * q1 + 2 + d] = rec.alpha * gd;
-                    if (q0 >= 0) job.g_slots[4ll * q0 + d] = -rec.alpha * gd;
-                } else if (c < C && g_vals) {  // (a constant colour has no adjoint)
-                    if (q1 >= 0) atomicAdd(g_vals + (long long)q1 * C + c, rec.alpha * gd);
-                    if (q0 >= 0) atomicAdd(g_vals + (long long)q0 * C + c, -rec.alpha * gd);
-                }
-                dd += gd * (ca_pre(s, p1, c) - ca_pre(s, p0, c));
-            }
-        }
-        dd = a3d_group_sum<32>(dd);  // (a record's 32 lanes are in the same trip)
-        if (sub != 0 || clamped || dd == 0.f) continue;
-        aa_edge_adjoint(rec, p0, d, di, use1, dd, clip, clip_batch, tri, V, H, W, xh, yh, g_clip);
-    }
+    aa_adjoint_records(AaCaSrc{job, W, min(job.s.C + 1, job.gC)}, n, s_off, work, capacity, clip, clip_batch, tri, V, H, g_clip);
     A3D_STAMP(3, 5);
 }
 
@@ -720,11 +738,12 @@ __device__ __forceinline__ MsSample ms_sample(const MsGrid& g, unsigned p) {  //
     return m;
 }
 
-// channel c of pre(sample): [v, 1] covered, [bg, 0] not (row = inv of the sample's block)
-__device__ __forceinline__ float ms_pre(const MsJob& j, const MsSample& m, int row, int c, unsigned hw) {
-    if (m.covered) return c < j.C ? (row >= 0 ? j.vals[(long long)row * j.C + c] : j.null_vals[(long long)m.b * j.C + c]) : 1.f;
-    if (!j.bg || c >= j.bgC) return 0.f;
-    return j.bg[(long long)(j.bg_shared ? m.q % hw : m.q) * j.bgC + c];
+// channel c of pre(sample): [v, 1] covered (v: the row of the sample's block, or image b's null row), [bg, 0] not (block q)
+__device__ __forceinline__ float ms_value(const MsJob& j, int row, unsigned b, int c) {
+    return c < j.C ? (row >= 0 ? j.vals[(long long)row * j.C + c] : j.null_vals[(long long)b * j.C + c]) : 1.f;
+}
+__device__ __forceinline__ float ms_bg(const MsJob& j, unsigned q, int c, unsigned hw) {
+    return (j.bg && c < j.bgC) ? j.bg[(long long)(j.bg_shared ? q % hw : q) * j.bgC + c] : 0.f;
 }
 
 // 256 blocks per work-group: count and point row of every block through LDS, then the blocks' oC floats as one contiguous run
@@ -742,14 +761,31 @@ __global__ __launch_bounds__(256) void ms_compose_kernel(MsJob ja, MsJob jb, MsG
     float* o = job.out + (long long)base * C1;
     for (unsigned j = threadIdx.x; j < nloc; j += 256u) {
         const unsigned pl = j / C1;
-        const int c = (int)(j - pl * C1), k = s_k[pl], row = s_row[pl];
+        const int c = (int)(j - pl * C1), k = s_k[pl];
         const unsigned qq = base + pl;
-        float v = 0.f, bgv = 0.f;
-        if (k > 0) v = c < job.C ? (row >= 0 ? job.vals[(long long)row * job.C + c] : job.null_vals[(long long)(qq / hw) * job.C + c]) : 1.f;
-        if (k < n && job.bg && c < job.bgC) bgv = job.bg[(long long)(job.bg_shared ? qq % hw : qq) * job.bgC + c];
+        const float v = k > 0 ? ms_value(job, s_row[pl], qq / hw, c) : 0.f, bgv = k < n ? ms_bg(job, qq, c, hw) : 0.f;
         o[j] = k == n ? v : (k == 0 ? bgv : ((float)k * v + (float)(n - k) * bgv) / (float)n);
     }
 }
+
+// the supersampled image as a source of the record walks: a full-resolution sample maps to its s x s block, blends and gradients are
+// divided by s^2, colour adjoints go to the point row of the sample's block or to its image's null row
+struct AaMsSrc {
+    typedef unsigned Idx;
+    struct Px { MsSample m; int row; };
+    static constexpr bool kBlendZeros = false;
+    const MsJob& j;
+    const MsGrid& g;
+    int W, nc;
+    __device__ Px pixel(unsigned p) const { const MsSample m = ms_sample(g, p); return Px{m, g.inv[m.q]}; }
+    __device__ unsigned out_index(const Px& x) const { return x.m.q; }
+    __device__ float pre(const Px& x, int c) const { return x.m.covered ? ms_value(j, x.row, (unsigned)x.m.b, c) : ms_bg(j, x.m.q, c, (unsigned)g.h * (unsigned)g.w); }
+    __device__ float scale(float v) const { return v / (float)(g.s * g.s); }
+    __device__ float grad(unsigned dst, int c) const { return j.g_out[(long long)dst * j.gS + c]; }
+    __device__ void sink(const Px& x, int c, float v, int) const {
+        if (c < j.C && x.m.covered) atomicAdd((x.row >= 0 ? j.g_vals + (long long)x.row * j.C : j.g_null + (long long)x.m.b * j.C) + c, v);
+    }
+};
 
 __global__ __launch_bounds__(256) void ms_blend_kernel(MsJob ja, MsJob jb, MsGrid g, const AaRec* __restrict__ work, const int* __restrict__ count,
                                                        int capacity) {
@@ -757,19 +793,7 @@ __global__ __launch_bounds__(256) void ms_blend_kernel(MsJob ja, MsJob jb, MsGri
     const MsJob& job = blockIdx.y ? jb : ja;
     const int n = aa_segment_offsets(count, capacity, s_off);
     if (!job.aa) return;
-    const unsigned C1 = (unsigned)job.oC, total = (unsigned)n * C1, hw = (unsigned)g.h * (unsigned)g.w;
-    const unsigned W = (unsigned)g.w * (unsigned)g.s;
-    const float nn = (float)(g.s * g.s);
-    for (unsigned idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
-        const unsigned ru = idx / C1;
-        const int c = (int)(idx - ru * C1);
-        const AaRec rec = work[aa_record_slot((int)ru, s_off, capacity)];
-        const unsigned p0 = (unsigned)rec.pix0, p1 = p0 + ((rec.flags & 1) ? W : 1u);
-        const MsSample m0 = ms_sample(g, p0), m1 = ms_sample(g, p1);
-        const float d = ms_pre(job, m1, g.inv[m1.q], c, hw) - ms_pre(job, m0, g.inv[m0.q], c, hw);
-        const unsigned dst = rec.alpha > 0.f ? m0.q : m1.q;
-        if (d != 0.f) atomicAdd(job.out + (long long)dst * C1 + c, rec.alpha * d / nn);
-    }
+    aa_blend_records(AaMsSrc{job, g, g.w * g.s, job.oC}, job.out, n, s_off, work, capacity);
 }
 
 // backward, one pass over the shading grid: g_vals[row] = (k / s^2) g_out[block] WRITTEN (a row belongs to exactly one block), the same
@@ -802,8 +826,6 @@ __global__ __launch_bounds__(256) void ms_gather_kernel(MsJob ja, MsJob jb, MsGr
     }
 }
 
-// ca_bwd_kernel on the full-resolution records: colour adjoints to the point row (or the null row) of each sample's block, the edge
-// adjoint scaled by 1 / s^2
 __global__ __launch_bounds__(256) void ms_bwd_kernel(MsJob ja, MsJob jb, MsGrid g, const AaRec* __restrict__ work, const int* __restrict__ count,
                                                      int capacity, const float4* __restrict__ clip, int clip_batch, const int* __restrict__ tri,
                                                      int V, float* __restrict__ g_clip) {
@@ -811,36 +833,7 @@ __global__ __launch_bounds__(256) void ms_bwd_kernel(MsJob ja, MsJob jb, MsGrid 
     const MsJob& job = blockIdx.y ? jb : ja;
     const int n = aa_segment_offsets(count, capacity, s_off);
     if (!job.aa) return;
-    const int H = g.h * g.s, W = g.w * g.s;
-    const float xh = 0.5f * W, yh = 0.5f * H, nn = (float)(g.s * g.s);
-    const unsigned hw = (unsigned)g.h * (unsigned)g.w;
-    const int C = job.C, C1 = min(C + 1, job.gC), gS = job.gS;
-    const int sub = threadIdx.x & 31, groups = (gridDim.x * blockDim.x) >> 5;
-    for (int r = (blockIdx.x * blockDim.x + threadIdx.x) >> 5; r < n; r += groups) {
-        const AaRec rec = work[aa_record_slot(r, s_off, capacity)];
-        const int d = rec.flags & 1, di = (rec.flags >> 1) & 3;
-        const bool use1 = rec.flags & 8, clamped = rec.flags & 16;
-        const unsigned p0 = (unsigned)rec.pix0, p1 = p0 + (d ? (unsigned)W : 1u);
-        const MsSample m0 = ms_sample(g, p0), m1 = ms_sample(g, p1);
-        const int row0 = g.inv[m0.q], row1 = g.inv[m1.q];
-        const unsigned dst = rec.alpha > 0.f ? m0.q : m1.q;
-        float* t0 = row0 >= 0 ? job.g_vals + (long long)row0 * C : job.g_null + (long long)m0.b * C;
-        float* t1 = row1 >= 0 ? job.g_vals + (long long)row1 * C : job.g_null + (long long)m1.b * C;
-        float dd = 0.f;
-        for (int c = sub; c < C1; c += 32) {
-            const float gd = job.g_out[(long long)dst * gS + c] / nn;
-            if (gd != 0.f) {
-                if (c < C) {
-                    if (m1.covered) atomicAdd(t1 + c, rec.alpha * gd);
-                    if (m0.covered) atomicAdd(t0 + c, -rec.alpha * gd);
-                }
-                dd += gd * (ms_pre(job, m1, row1, c, hw) - ms_pre(job, m0, row0, c, hw));
-            }
-        }
-        dd = a3d_group_sum<32>(dd);  // (a record's 32 lanes are in the same trip)
-        if (sub != 0 || clamped || dd == 0.f) continue;
-        aa_edge_adjoint(rec, p0, d, di, use1, dd, clip, clip_batch, tri, V, H, W, xh, yh, g_clip);
-    }
+    aa_adjoint_records(AaMsSrc{job, g, g.w * g.s, min(job.C + 1, job.gC)}, n, s_off, work, capacity, clip, clip_batch, tri, V, g.h * g.s, g_clip);
 }
 
 // ---- the 'depth' render mode on the point list (a3d_ca_shade.depth_*) --------------------------------------------------------------------

@@ -34,3 +34,8 @@ for C, attr in ((3, shape.v_pos.detach().contiguous()), (3, prior.v_pos.detach()
     g_attr = torch.empty_like(attr)
     g_r = torch.empty_like(rast)
     print(f"interp_bwd C{C} attr_batch {ab} us/call", round(t(lambda: _lib.call("a3d_interp_bwd", p(g_out), p(attr), ab, C, p(rast), p(tri32), B, V, F, H, W, p(g_attr), p(g_r), st())), 2))
+# the dense antialiasing pair (a3d_aa_fwd + a3d_aa_bwd through ops.antialias) on the same raster, the analysis shared
+analysis = ops.AAAnalysis(rast, clip, ops.AATopology(tri32, V))
+for C in (4, 17):
+    color, cg, g_out = torch.rand(B, H, W, C, device=dev, requires_grad=True), clip.clone().requires_grad_(True), torch.rand(B, H, W, C, device=dev)
+    print(f"antialias C{C} fwd+bwd us/call", round(t(lambda: torch.autograd.grad(ops.antialias(color, rast, cg, tri32, analysis=analysis), [color, cg], g_out)), 2))
