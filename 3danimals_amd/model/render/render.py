@@ -5,7 +5,7 @@ inside shade like the reference, render.py:127-128), same arithmetic; underneath
 
 * one triangle-parallel rasterisation pass (csrc/raster.hip: 64-bit atomicMin on depth|id, then a resolve) instead of the OpenGL
   depth peeler (layers > 0 peel behind the previous layer's (depth, id): render_mesh(num_layers > 1) takes the general dense path);
-* on the training path (spp 1; 'tangent' / 'depth' where _fused_depth_tangent allows) ONE fused kernel builds the G-buffer of the covered pixels only
+* on the training path (spp 1; 'tangent' / 'depth' where _plan_route serves them) ONE fused kernel builds the G-buffer of the covered pixels only
   (csrc/cover.hip + csrc/gbuffer.hip: world position, face normal, smooth normal, canonical position; its backward also carries
   the rasteriser's gradient), ONE kernel does the shading arithmetic (csrc/shade.hip), and the texture / DINO fields see the
   covered pixels only -- output-identical, because uncovered pixels are composited with alpha 0 (render.py:261-262);
@@ -16,10 +16,22 @@ inside shade like the reference, render.py:127-128), same arithmetic; underneath
   separately (render.py:311-315).
 
 The texture / DINO / light MLPs (``material.sample``, ``dino_net.sample``, ``lgt.shade``) stay PyTorch modules.
+
+The route of a call (_Route, filled once by _plan_route; first match; DESIGN.md section 26 names the switches behind each row):
+
+  path      conditions                                                                          entry points
+  layers    num_layers != 1                                                                     _render_mesh_layers: ops.rasterize(prev=), dense render_layer
+  msaa      FUSED_MSAA, msaa, spp 2..8, 'covered' on the shading grid with the one-launch       _render_mesh_msaa: ops.covered_gbuffer,
+            list, the fused compositor, device float32 operands, no autocast                    ops.msaa_composite_antialias
+  mask      no material / light / DINO net, modes ['shaded'], spp 1, the fused compositor       ops.mask_antialias
+  covered   a clip set per image, spp 1, normals indexed like positions, every 'depth' /        ops.covered_gbuffer | ops.covered_pixels + ops.gbuffer,
+            'tangent' asked for served                                                          _shade_points, _composite_modes | _composite_torch
+  dense     otherwise                                                                           ops.interpolate, shade, _composite_torch
 """
 from __future__ import annotations
 
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -50,7 +62,7 @@ FUSED_SHADING = True
 FUSED_MSAA = os.environ.get("A3D_FUSED_MSAA", "0") not in ("0", "")
 # 'depth' and 'tangent' on the fused path (spp 1, one layer): the tangent rides through the G-buffer launch as its extra attribute, the
 # depth is computed by the compositor from the G-buffer rows (ops.depth_composite_antialias); off = both modes switch the whole call to
-# the generic path, as they always do where _fused_depth_tangent's conditions fail (tools/bench_render_modes.py)
+# the generic path, as they always do where _plan_route's conditions for them fail (tools/bench_render_modes.py)
 FUSED_DEPTH_TANGENT = os.environ.get("A3D_FUSED_DEPTH_TANGENT", "1") not in ("0", "")
 ALIAS_POSITIONS = os.environ.get("A3D_ALIAS_POSITIONS", "1") != "0"  # the clip transform's node feeds the G-buffer's position attribute too (one accumulation launch less)
 FIELD_INPUTS_FROM_GBUFFER = os.environ.get("A3D_FIELD_INPUTS", "1") != "0"  # the fields' padded input rows + image index written by the G-buffer launch (round 6)
@@ -383,47 +395,93 @@ def _covered_pixels(rast):
 
 
 FUSED_GBUFFER_MODES = frozenset(("shaded", "kd", "ks", "normal", "geo_normal", "shading", "dino_pred", "flow", "depth", "tangent"))
-_GENERIC_ONLY = frozenset(("tangent", "depth"))  # ... the last two only where _fused_depth_tangent allows them
 
 
-def _fused_depth_tangent(render_modes, mesh, w2c, spp, num_layers, background):
-    """Which of 'depth' / 'tangent' the fused path serves in this call: all that are asked for, or none (one of them on the generic path
-    takes the whole call there).  Both: FUSED_DEPTH_TANGENT, spp 1, one layer, no autocast.  'depth': w2c a [B,4,4] float32 device tensor
-    that does not require grad (the compositor gives it none), and the fused compositor available (no differentiable background).
-    'tangent': per-vertex tangents [B,V,3] float32 on the device whose index buffer is the position one -- and no 'flow' in the same
-    call: the G-buffer launch carries ONE extra attribute of at most 3 columns, and a call that wants both keeps the generic path."""
-    asked = _GENERIC_ONLY & set(render_modes)
-    if not asked or not FUSED_DEPTH_TANGENT or spp != 1 or num_layers != 1 or torch.is_autocast_enabled() or not mesh.v_pos.is_cuda:
-        return frozenset()
-    if "depth" in asked:
-        if not (torch.is_tensor(w2c) and w2c.is_cuda and w2c.dtype == torch.float32 and w2c.dim() == 3 and w2c.shape[1:] == (4, 4)
-                and w2c.shape[0] == mesh.v_pos.shape[0] and not w2c.requires_grad and FUSED_COMPOSITE
-                and (background is None or not background.requires_grad)):
-            return frozenset()
-    if "tangent" in asked:
-        if "flow" in render_modes:
-            return frozenset()
-        # (tangents still pending come out in the positions' shape and dtype; asking for them here would run the vertex normals before the
-        # rasteriser's launch could carry them)
-        pending = getattr(mesh, "_v_tng", 0) is None and getattr(mesh, "_lazy_tng", False) and mesh.v_tex is not None
-        tng = mesh.v_pos if pending else mesh.v_tng
-        if not (tng is not None and tng.is_cuda and tng.dtype == torch.float32 and tng.dim() == 3 and tng.shape[-1] == 3
-                and tng.shape[:2] == mesh.v_pos.shape[:2] and mesh.t_tng_idx is not None
-                and mesh.t_tng_idx.data_ptr() == mesh.t_pos_idx.data_ptr()):
-            return frozenset()
-    return frozenset(asked)
+class _Route(NamedTuple):
+    """What one render_mesh / render_layer call does: decided once, by _plan_route, before the first launch (the table in the module
+    docstring); every stage reads its own field and none of them looks at a switch or an argument again."""
+    path: str  # 'layers' | 'msaa' | 'mask' | 'covered' | 'dense'
+    one_launch: bool = False  # covered points: list and rows from ONE launch (ops.covered_gbuffer); else ops.covered_pixels + ops.gbuffer
+    defer: bool = False  # ... and the rasteriser's resolve in that launch too: ops.rasterize(defer_resolve=True), the promise that it comes next
+    extra: str = None  # the one attribute of at most 3 columns that rides in the G-buffer launch: None | 'flow' | 'tangent'
+    served: frozenset = frozenset()  # which of 'depth' / 'tangent' the covered-point path serves ('depth' leaves it as a recipe for the compositor)
+    composite: bool = False  # the fused compositor takes the antialiased modes; else the torch compositor + ops.antialias
+    alias: bool = False  # the clip transform hands its operands and its result out once more (ops.xfm_points(alias=3))
+    flow_delta: bool = False  # 'flow': the per-vertex motion to the next frame from ops.flow_delta
+
+    @property
+    def covered_points(self):
+        """render_layer shades a list of covered points (on the 'msaa' path: the covered shading samples)."""
+        return self.path in ("covered", "msaa")
+
+
+_DEPTH_TANGENT = frozenset(("depth", "tangent"))
+
+
+def _on_gpu_f32(t):
+    """``t`` is a float32 tensor on the GPU: the one question the planner asks about where an operand lives."""
+    return isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32
+
+
+def _plan_route(render_modes, mesh, w2c, resolution, spp=1, num_layers=1, msaa=False, background=None, material=None, lgt=None, dino_net=None,
+                mtx=None, num_frames=None, clip=None, flow_cols=2):
+    """-> the _Route of a call, from its arguments and the module switches alone.  ``mtx``: render_mesh's call, made before the clip
+    transform -- the clip positions' batch and placement follow from its operands (device float32 clip positions are taken to need device
+    float32 positions AND matrix: the transform's matmul does not promote, it refuses operands of two dtypes).  Without it render_layer plans for itself: ``clip`` is
+    what it was handed, there is no stage around it, and ``resolution`` is its raster's.  ``flow_cols``: the columns of the 'flow' attribute a lone render_layer call was
+    handed; render_mesh builds its own from the clip positions' x and y, two columns, and leaves the default.
+
+    'depth' / 'tangent' are served by the covered-point path all that are asked for, or none (one of them on the dense path takes the whole
+    call there).  Both: spp 1, one layer, no autocast.  'depth': w2c a [B,4,4] float32 device tensor that does not require grad (the
+    compositor gives it none), and the fused compositor.  'tangent': per-vertex tangents [B,V,3] float32 on the device whose index buffer is
+    the position one -- and no 'flow' in the same call: a call that wants both extras keeps the dense path."""
+    modes, b, top = render_modes, mesh.v_pos.shape[0], mtx is not None  # (a handful of names: membership in the list as it is)
+    autocast = torch.is_autocast_enabled()
+    if top:
+        have_clip, clip_b = FUSED_GBUFFER, max(b, mtx.shape[0] if mtx.dim() == 3 else 1)
+        clip_gpu = _on_gpu_f32(mesh.v_pos) and _on_gpu_f32(mtx)
+    else:
+        have_clip, clip_b, clip_gpu = clip is not None, 0 if clip is None else clip.shape[0], _on_gpu_f32(clip)
+    alias = (top and ALIAS_POSITIONS and spp == 1 and num_layers == 1 and not autocast and ru.ops._hip_xfm_ok(mesh.v_pos, mtx, _on_gpu_f32)
+             and mtx.shape[0] == b)  # (the clip transform's kernel, and a matrix per image)
+    flow_delta = top and "flow" in modes and FUSED_FLOW_DELTA and clip_gpu and num_frames > 1 and clip_b % num_frames == 0 and not autocast
+    if num_layers != 1:  # depth peeling: never used by a config (AnimalModel.py:247); every layer on the dense path
+        return _Route("layers", flow_delta=flow_delta)
+    can_composite = top and FUSED_COMPOSITE and (background is None or not background.requires_grad)  # (the compositor gives the background no gradient)
+
+    asked, served = _DEPTH_TANGENT.intersection(modes), frozenset()
+    if asked and top and clip_b == b and FUSED_DEPTH_TANGENT and spp == 1 and not autocast and _on_gpu_f32(mesh.v_pos):
+        ok = "depth" not in asked or (_on_gpu_f32(w2c) and tuple(w2c.shape) == (b, 4, 4) and not w2c.requires_grad and can_composite)
+        if ok and "tangent" in asked:
+            # (tangents still pending come out in the positions' shape and dtype; asking for them here would run the vertex normals before the
+            # rasteriser's launch could carry them)
+            pending = getattr(mesh, "_v_tng", 0) is None and getattr(mesh, "_lazy_tng", False) and mesh.v_tex is not None
+            tng = mesh.v_pos if pending else mesh.v_tng
+            ok = ("flow" not in modes and _on_gpu_f32(tng) and tng.dim() == 3 and tng.shape[-1] == 3 and tng.shape[:2] == mesh.v_pos.shape[:2]
+                  and mesh.t_tng_idx is not None and mesh.t_tng_idx.data_ptr() == mesh.t_pos_idx.data_ptr())
+        served = asked if ok else served
+    extra = "flow" if "flow" in modes and flow_cols <= 3 else ("tangent" if "tangent" in served else None)
+    # the G-buffer kernels take the clip positions, one set per image, and read the smooth normals through the position index buffer
+    rows = have_clip and SHADE_COVERED_ONLY and clip_b == b and served == asked and mesh.t_nrm_idx.data_ptr() == mesh.t_pos_idx.data_ptr()
+    one_launch = rows and FUSED_COVER_GBUFFER and PIXEL_TILE == 8 and resolution[0] % 8 == 0 and resolution[1] % 8 == 0
+
+    if top and FUSED_MSAA and msaa and 2 <= spp <= 8 and one_launch and can_composite and clip_gpu and not autocast and flow_cols <= 3:
+        return _Route("msaa", one_launch=True, extra=extra, composite=True, flow_delta=flow_delta)  # (the point list lives on the shading grid: spp 1 there)
+    if can_composite and FUSED_MASK_RENDER and material is None and lgt is None and dino_net is None and list(render_modes) == ["shaded"] and spp == 1:
+        return _Route("mask", alias=alias)
+    if rows and spp == 1:
+        return _Route("covered", one_launch, DEFER_RESOLVE and top and one_launch, extra, served, can_composite, alias, flow_delta)
+    return _Route("dense", alias=alias, flow_delta=flow_delta)
 
 
 def render_layer(rast, rast_deriv, mesh, w2c, view_pos, material, lgt, resolution, spp, msaa, bsdf, feat, render_modes=None, prior_mesh=None,
-                 two_sided_shading=True, delta_xy=None, dino_net=None, class_vector=None, clip=None, sparse=False, v_pos_attr=None,
-                 fused_depth_tangent=frozenset()):
+                 two_sided_shading=True, delta_xy=None, dino_net=None, class_vector=None, clip=None, sparse=False, v_pos_attr=None, route=None):
     """G-buffer interpolation + shading of one depth layer (reference render.py:139-221).
 
-    ``clip`` (the [B,V,4] clip-space vertices, not in the reference signature) enables the fused path: one HIP kernel builds
+    ``clip`` (the [B,V,4] clip-space vertices, not in the reference signature) enables the covered-point path: one HIP kernel builds
     the G-buffer of the covered pixels and its backward also carries the rasteriser's gradient (csrc/gbuffer.hip).  Without
-    it, or for modes that need other attributes or spp > 1, the generic interpolate path runs.  ``fused_depth_tangent``: which of
-    'depth' / 'tangent' the caller has cleared for the fused path (_fused_depth_tangent; render_mesh only -- 'depth' leaves as a recipe for
-    the compositor, which needs ``sparse``).
+    it, or for modes that need other attributes or spp > 1, the dense interpolate path runs.  ``route``: the caller's _Route, which this
+    call is one stage of (render_mesh and its helpers); a call without one plans for itself (_plan_route).
     """
     full_res = [resolution[0] * spp, resolution[1] * spp]
     if prior_mesh is None:
@@ -431,18 +489,14 @@ def render_layer(rast, rast_deriv, mesh, w2c, view_pos, material, lgt, resolutio
     render_modes = render_modes if render_modes is not None else ["shaded"]
     tri = mesh.t_pos_idx[0]
     assert mesh.v_nrm is not None
+    if route is None:
+        route = _plan_route(render_modes, mesh, w2c, rast.shape[1:3], spp, clip=clip, flow_cols=delta_xy.shape[-1] if "flow" in render_modes else 0)
 
-    fused = (clip is not None and SHADE_COVERED_ONLY and spp == 1 and not ((_GENERIC_ONLY - fused_depth_tangent) & set(render_modes))
-             and clip.shape[0] == mesh.v_pos.shape[0] and mesh.t_nrm_idx.data_ptr() == mesh.t_pos_idx.data_ptr())
-    if fused:
+    if route.covered_points:
         b, h, w = rast.shape[:3]
-        flow = None
-        flow_fused = "flow" in render_modes and delta_xy.shape[-1] <= 3  # the one extra attribute of the sequence models rides in the same kernels
-        # ... or the per-vertex tangents, for the 'tangent' mode (never both: _fused_depth_tangent)
-        tng_fused = "tangent" in render_modes and "tangent" in fused_depth_tangent and not flow_fused
-        extra = delta_xy if flow_fused else (mesh.v_tng if tng_fused else None)
-        assert not ("tangent" in render_modes and not tng_fused)
-        if FUSED_COVER_GBUFFER and PIXEL_TILE == 8 and h % 8 == 0 and w % 8 == 0:
+        # the one extra attribute of the sequence models rides in the same kernels -- or the per-vertex tangents, for the 'tangent' mode
+        extra = delta_xy if route.extra == "flow" else (mesh.v_tng if route.extra == "tangent" else None)
+        if route.one_launch:
             # the covered-pixel list and its G-buffer rows from ONE launch (one host sync before it: the number of covered pixels)
             # (... and what the fields take from it -- canonical positions as dense rows, point -> image index, padded -- from the same launch)
             res = ops.covered_gbuffer(clip, mesh.v_pos if v_pos_attr is None else v_pos_attr, mesh.v_nrm, prior_mesh.v_pos, rast, tri,
@@ -451,16 +505,16 @@ def render_layer(rast, rast_deriv, mesh, w2c, view_pos, material, lgt, resolutio
             (gb, flow, pix, inv), rest = (res[:4], res[4:]) if extra is not None else ((res[0], None, res[1], res[2]), res[3:])
             tex_in, img_p = rest if rest else (None, None)
         else:
-            tex_in = img_p = None
+            tex_in = img_p = flow = None
             pix, inv = ops.covered_pixels(rast, tile=PIXEL_TILE, return_inverse=True)  # one host sync for the number of covered pixels
             if extra is not None:
                 gb, flow = ops.gbuffer(clip, mesh.v_pos, mesh.v_nrm, prior_mesh.v_pos, rast, tri, pix, extra=extra)  # [P,12], [P,2] (tangent: [P,3])
             else:
                 gb = ops.gbuffer(clip, mesh.v_pos, mesh.v_nrm, prior_mesh.v_pos, rast, tri, pix)  # [P,12]
-        if "flow" in render_modes and not flow_fused:
+        if "flow" in render_modes and route.extra != "flow":
             flow = interpolate(delta_xy, rast, tri)[0].reshape(b * h * w, -1).index_select(0, pix)
         tng = None
-        if tng_fused:
+        if route.extra == "tangent":
             tng, flow = flow, None
         return _shade_points(gb[:, 0:3], gb[:, 3:6], gb[:, 6:9], tng, gb[:, 9:12], flow, pix, (b, h, w), w2c, view_pos, lgt, material, bsdf, feat,
                              render_modes, two_sided_shading, dino_net, class_vector, sparse=sparse, gb=gb, inv=inv, tex_in=tex_in, img_p=img_p)
@@ -513,6 +567,66 @@ def _lazy_background4(background, res, dev):
     return background4
 
 
+def _mode_background(mode, background, background4=None):
+    """What ``mode`` is composited over (reference render.py:301-308), None for nothing.  ``background``: the call's, with 3 channels as the
+    fused compositor reads it or with the zero alpha appended (the torch compositor).  'shading' takes the last two channels of the
+    4-channel copy: of ``background`` itself where it is that copy, else a view of ``background4()`` where the call has one, else just
+    those two channels."""
+    if background is None or mode not in ("shaded", "geo_normal", "shading"):
+        return None
+    if mode != "shading":
+        return background
+    if background.shape[-1] == 4:
+        return background[..., 2:]
+    return background4()[..., 2:] if background4 is not None else torch.cat((background[..., 2:3], torch.zeros_like(background[..., 0:1])), dim=-1)
+
+
+def _frame_analysis(rast, clip_f, tri, defer=False):
+    """The silhouette analysis of one rasterised frame: one per frame, shared by every buffer that is antialiased with its geometry.
+    ``defer``: it runs inside the first fused compositor call (ops.AAAnalysis)."""
+    return ops.AAAnalysis(rast, clip_f, ops.aa_topology(ops.tri_int32(tri), clip_f.shape[1]), defer=defer)
+
+
+def _rasterize_frame(mesh, clip_f, tri, full_res, defer=False, graph_pos=None):
+    """The frame's one triangle launch: pending vertex normals ride in it as extra work-groups and are handed back to the mesh
+    (``graph_pos``: Mesh.take_normals), and the introspection hooks are reset."""
+    job = mesh.normals_job() if hasattr(mesh, "normals_job") else None
+    rast = ops.rasterize(clip_f, tri, full_res, normals_job=job, defer_resolve=defer)
+    if job is not None:
+        mesh.take_normals(job, graph_pos=graph_pos)
+    LAST_RAST[0] = rast.detach()  # introspection hook for benchmarks / debugging (coverage, ids)
+    LAST_POINTS[0] = None
+    return rast
+
+
+def _composite_torch(key, layers, background4, clip_f, tri, spp):
+    """Mode ``key`` through the torch compositor (reference render.py:258-268, 301-331) -> NCHW.  ``layers``: ``[buffers, rast, analysis]``
+    front to back (analysis None: made here at its first use and left in the list); each is laid over what lies behind it -- the background
+    first -- and antialiased with its own geometry; then the block average and the channels the mode hands out."""
+    accum = _mode_background(key, background4())
+    for layer in reversed(layers):
+        buffers, rast = layer[:2]
+        coverage = (rast[..., -1:] > 0).float()
+        if isinstance(buffers, SparseBuffers):
+            # coverage is 0 or 1, for which lerp(bg, [rgb,1], alpha) (render.py:261-262) returns exactly bg or exactly [rgb,1]:
+            # start from the background and overwrite the covered pixels -- same bits, a third of the passes over the image
+            vals = buffers[key]
+            c1 = vals.shape[-1] + 1
+            accum = (torch.zeros(*rast.shape[:3], c1, dtype=torch.float32, device=rast.device) if accum is None
+                     else accum.expand(rast.shape[0], -1, -1, -1).clone())
+            accum.view(-1, c1).index_copy_(0, buffers.pix, torch.cat((vals, torch.ones_like(vals[:, :1])), dim=-1))
+        else:
+            buf = buffers[key]
+            accum = torch.lerp(torch.zeros_like(buf) if accum is None else accum, torch.cat((buf[..., :-1], torch.ones_like(buf[..., -1:])), dim=-1),
+                               coverage * buf[..., -1:])  # render.py:261-262
+        if key in ANTIALIASED_MODES:
+            if layer[2] is None:  # (the frame's analysis is made where its first consumer stands, and kept for the next mode)
+                layer[2] = _frame_analysis(rast, clip_f, tri)
+            accum = ops.antialias(accum.contiguous().float(), rast, clip_f, tri, analysis=layer[2])
+    out = util.avg_pool_nhwc(accum, spp) if spp > 1 else accum
+    return _slice_mode(key, out).permute(0, 3, 1, 2)
+
+
 def _composite_modes(keys, rendered, background, background4, call, out, on_the_fly=False, depth_last=False):
     """The modes ``keys`` through the fused compositor two at a time (the colour and the feature image of a training step share its
     launches), the images into ``out``.  ``call(ka, va, bg, keep, kb, second)`` issues one: ``va`` the first mode's rows -- with
@@ -521,14 +635,7 @@ def _composite_modes(keys, rendered, background, background4, call, out, on_the_
     everywhere else a colour that is still a recipe is materialised.  ``background4``: the lazily built 4-channel background, or None
     where nobody else needs one.  ``depth_last``: 'depth' gets a call of its own behind the others -- with the buffer that would have
     gone alone, if that one has rows, as its second one."""
-    def bg_of(k):
-        if background is None or k not in ("shaded", "geo_normal", "shading"):
-            return None
-        if k != "shading":
-            return background
-        # 'shading': the last two channels of the background with its zero alpha appended (render.py:254-256, 307-308) -- a view of the
-        # 4-channel copy where the call has one, else just those two channels
-        return background4()[..., 2:] if background4 is not None else torch.cat((background[..., 2:3], torch.zeros_like(background[..., 0:1])), dim=-1)
+    bg_of = lambda k: _mode_background(k, background, background4)
 
     def keep(k, vals):  # (the op returns the channels the mode hands out, so no slice -- and no padded gradient of one -- follows it)
         n = MODE_CHANNELS.get(k)
@@ -569,9 +676,9 @@ def render_mesh(ctx, mesh, mtx_in, w2c, view_pos, material, lgt, resolution, spp
     view_pos = torch.tensor(view_pos, dtype=torch.float32, device=dev) if not torch.is_tensor(view_pos) else view_pos
     view_pos = view_pos[:, None, None, :] if view_pos.dim() == 2 else view_pos
 
+    route = _plan_route(render_modes, mesh, w2c, resolution, spp, num_layers, msaa, background, material, lgt, dino_net, mtx=mtx_in, num_frames=num_frames)
     v_pos_attr = v_pos_nrm = clip_aa = None
-    if ALIAS_POSITIONS and spp == 1 and num_layers == 1 and mesh.v_pos.is_cuda and ru.ops._hip_xfm_ok(mesh.v_pos, mtx_in) and mesh.v_pos.shape[0] == mtx_in.shape[0] \
-            and not torch.is_autocast_enabled():
+    if route.alias:
         # the clip transform's node hands the positions out once more for the G-buffer's position attribute: their two gradients (through
         # clip space, through the interpolated position) meet inside that node's ONE backward launch, not in an accumulation kernel
         # (... and a third time for the pending vertex normals, whose backward is the positions' third gradient)
@@ -581,8 +688,7 @@ def render_mesh(ctx, mesh, mtx_in, w2c, view_pos, material, lgt, resolution, spp
         v_pos_clip = ru.xfm_points(mesh.v_pos, mtx_in, use_python=True)  # [B,V,4]
 
     delta_xy = None
-    if "flow" in render_modes and FUSED_FLOW_DELTA and v_pos_clip.is_cuda and v_pos_clip.dtype == torch.float32 and num_frames > 1 and v_pos_clip.shape[0] % num_frames == 0 \
-            and not torch.is_autocast_enabled():
+    if route.flow_delta:
         delta_xy = ops.flow_delta(v_pos_clip, num_frames)  # the expression below as ONE launch each way (a3d_flow_delta_*)
     elif "flow" in render_modes:  # 2-D motion of each vertex to the next frame (render.py:281-288)
         ndc = v_pos_clip[..., :2] / v_pos_clip[..., -1:]
@@ -592,64 +698,44 @@ def render_mesh(ctx, mesh, mtx_in, w2c, view_pos, material, lgt, resolution, spp
 
     tri = mesh.t_pos_idx[0]
     clip_f = v_pos_clip.float()
-    fused_dt = _fused_depth_tangent(render_modes, mesh, w2c, spp, num_layers, background) if clip_f.shape[0] == mesh.v_pos.shape[0] else frozenset()
-    if num_layers != 1:  # depth peeling: never used by a config (AnimalModel.py:247); the general, dense path
-        return _render_mesh_layers(mesh, clip_f, tri, w2c, view_pos, material, lgt, resolution, spp, num_layers, msaa, background, bsdf, feat,
-                                   render_modes, prior_mesh, two_sided_shading, dino_net, class_vector, delta_xy)
-    if (FUSED_MSAA and msaa and 2 <= spp <= 8 and FUSED_GBUFFER and FUSED_COVER_GBUFFER and FUSED_COMPOSITE and SHADE_COVERED_ONLY and PIXEL_TILE == 8
-            and clip_f.is_cuda and mesh.v_pos.dtype == torch.float32 and v_pos_clip.dtype == torch.float32 and not torch.is_autocast_enabled()
-            and not ({"tangent", "depth"} & set(render_modes)) and clip_f.shape[0] == mesh.v_pos.shape[0]
-            and mesh.t_nrm_idx.data_ptr() == mesh.t_pos_idx.data_ptr() and resolution[0] % 8 == 0 and resolution[1] % 8 == 0
-            and (delta_xy is None or delta_xy.shape[-1] <= 3) and (background is None or not background.requires_grad)):
-        return _render_mesh_msaa(mesh, clip_f, tri, w2c, view_pos, material, lgt, resolution, spp, background, bsdf, feat, render_modes, prior_mesh,
-                                 two_sided_shading, dino_net, class_vector, delta_xy)
-    job = mesh.normals_job() if hasattr(mesh, "normals_job") else None  # pending auto_normals: extra work-groups of the triangle launch
-    mask_only = (FUSED_MASK_RENDER and FUSED_COMPOSITE and material is None and lgt is None and dino_net is None and list(render_modes) == ["shaded"]
-                 and spp == 1 and (background is None or not background.requires_grad))
-    # when render_layer's fused path is certain to come next, the rasteriser's resolve waits for it: ONE launch then writes the texels,
-    # the covered-pixel list and the G-buffer rows (ops.DEFER_RESOLVE; the conditions are render_layer's own)
-    defer = (DEFER_RESOLVE and not mask_only and FUSED_GBUFFER and FUSED_COVER_GBUFFER and SHADE_COVERED_ONLY and PIXEL_TILE == 8 and spp == 1
-             and not ((_GENERIC_ONLY - fused_dt) & set(render_modes)) and clip_f.shape[0] == mesh.v_pos.shape[0]
-             and mesh.t_nrm_idx.data_ptr() == mesh.t_pos_idx.data_ptr() and full_res[0] % 8 == 0 and full_res[1] % 8 == 0)
-    rast = ops.rasterize(clip_f, tri, full_res, normals_job=job, defer_resolve=defer)
-    if job is not None:
-        mesh.take_normals(job, graph_pos=v_pos_nrm)
-    LAST_RAST[0] = rast.detach()  # introspection hook for benchmarks / debugging (coverage, ids)
-    LAST_POINTS[0] = None
-    if mask_only:
+    layer_args = (mesh, w2c, view_pos, material, lgt, resolution)
+    layer_kwargs = dict(feat=feat, render_modes=render_modes, prior_mesh=prior_mesh, two_sided_shading=two_sided_shading, delta_xy=delta_xy,
+                        dino_net=dino_net, class_vector=class_vector, route=route)
+    if route.path == "layers":
+        return _render_mesh_layers(clip_f, tri, layer_args, spp, num_layers, msaa, background, bsdf, layer_kwargs)
+    if route.path == "msaa":
+        return _render_mesh_msaa(clip_f, tri, layer_args, spp, background, bsdf, layer_kwargs)
+    # when render_layer's covered_gbuffer is to come next, the rasteriser's resolve waits for it: ONE launch then writes the texels, the
+    # covered-pixel list and the G-buffer rows (ops.DEFER_RESOLVE)
+    rast = _rasterize_frame(mesh, clip_f, tri, full_res, route.defer, v_pos_nrm)
+    if route.path == "mask":
         _resolve_bsdf(bsdf, material)  # the reference's asserts come first (render.py:79,85): bsdf None without a material, 'pbr' without a light
         # shade() gives every covered pixel kd = (1,1,1) here (render.py:57-60, :84-85 with lgt None): the image is the coverage, and the only
         # gradient is the silhouette's.  Fauna's random-view mask (Fauna.py:111-173).  No covered-pixel list, no G-buffer, no read-back.
         bg = None if background is None else torch.cat((background, torch.zeros_like(background[..., 0:1])), dim=-1)
-        tri32 = ops.tri_int32(tri)
-        analysis = ops.AAAnalysis(rast, clip_f, ops.aa_topology(tri32, clip_f.shape[1]), defer=DEFER_ANALYSIS)
+        analysis = _frame_analysis(rast, clip_f, tri, defer=DEFER_ANALYSIS)
         LAST_POINTS[0] = dict(clip=clip_f.detach())
         return [ops.mask_antialias(rast, clip_f, bg, analysis, 3).permute(0, 3, 1, 2)]
     try:
-        rendered = render_layer(rast, None, mesh, w2c, view_pos, material, lgt, resolution, spp, msaa, bsdf, feat=feat, render_modes=render_modes,
-                                prior_mesh=prior_mesh, two_sided_shading=two_sided_shading, delta_xy=delta_xy, dino_net=dino_net,
-                                class_vector=class_vector, clip=clip_f if FUSED_GBUFFER else None, sparse=True, v_pos_attr=v_pos_attr,
-                                fused_depth_tangent=fused_dt)
+        rendered = render_layer(rast, None, *layer_args, spp, msaa, bsdf, clip=clip_f, sparse=True, v_pos_attr=v_pos_attr, **layer_kwargs)
     except BaseException:
-        if defer:  # the consumer the deferred resolve was promised failed: nothing may be left pending (keys pinned, texels unwritten)
+        if route.defer:  # the consumer the deferred resolve was promised failed: nothing may be left pending (keys pinned, texels unwritten)
             ops.drop_pending_resolve(rast)
         raise
 
     if background is not None and spp > 1:
         background = util.scale_img_nhwc(background, full_res, mag="nearest", min="nearest")
-    background4 = _lazy_background4(background, full_res, dev)  # (only the torch branches further down, and 'shading', need the copy)
+    background4 = _lazy_background4(background, full_res, dev)  # (only the torch compositor, and 'shading', need the copy)
     analysis = None
-    # composite + antialias fused (csrc/antialias.hip): one pass over the image per buffer, same values as the two steps further down;
+    # composite + antialias fused (csrc/antialias.hip): one pass over the image per buffer, same values as the torch compositor's two steps;
     # the buffers go through the op two at a time (the colour and the feature image of a training step share its launches)
     fused = {}
-    can_fuse = isinstance(rendered, SparseBuffers) and rendered.inv is not None and FUSED_COMPOSITE and (background is None or not background.requires_grad)
-    fuse_keys = [k for k in dict.fromkeys(render_modes) if can_fuse and k in rendered and k in ANTIALIASED_MODES]
+    fuse_keys = [k for k in dict.fromkeys(render_modes) if route.composite and k in rendered and k in ANTIALIASED_MODES]
     if fuse_keys:
-        tri32 = ops.tri_int32(tri)
-        analysis = ops.AAAnalysis(rast, clip_f, ops.aa_topology(tri32, clip_f.shape[1]), defer=DEFER_ANALYSIS)  # runs inside the first compositor call
+        analysis = _frame_analysis(rast, clip_f, tri, defer=DEFER_ANALYSIS)  # runs inside the first compositor call
         # (the antialiasing differentiates w.r.t. the clip positions: it takes them as the clip transform's OTHER clip output, same storage)
-        clip_of_aa = clip_f if clip_aa is None or clip_aa.dtype != clip_f.dtype else clip_aa
-        depth_rec = getattr(rendered, "depth_recipe", None) if "depth" in fuse_keys else None  # 'depth' from the G-buffer rows
+        clip_of_aa = clip_f if clip_aa is None else clip_aa  # (no dtype test: route.alias implies float32 operands, so clip_aa is float32 like clip_f)
+        depth_rec = rendered.depth_recipe if "depth" in fuse_keys else None  # 'depth' from the G-buffer rows
 
         def call(ka, va, bg, keep, kb, second):
             if va is not None:
@@ -665,65 +751,34 @@ def render_mesh(ctx, mesh, mtx_in, w2c, view_pos, material, lgt, resolution, spp
         _composite_modes(fuse_keys, rendered, background, background4, call, fused, on_the_fly=True, depth_last=depth_rec is not None)
     if LAST_POINTS[0] is not None:
         LAST_POINTS[0]["clip"] = clip_f.detach()
-    assert getattr(rendered, "depth_recipe", None) is None or "depth" in fused  # (_fused_depth_tangent admits 'depth' only where the compositor runs)
+    layer = [rendered, rast, analysis]
     out_buffers = []
     for key in render_modes:
-        if key not in rendered:
-            out_buffers.append(None)
-            continue
-        fused_aa = key in fused
-        if fused_aa:  # (already antialiased, and already cut to the channels the mode returns)
+        if key in fused:  # (already antialiased, and already cut to the channels the mode returns)
             out_buffers.append(fused[key].permute(0, 3, 1, 2))
-            continue
-        background = background4()
-        coverage = (rast[..., -1:] > 0).float()
-        if isinstance(rendered, SparseBuffers):
-            # coverage is 0 or 1, for which lerp(bg, [rgb,1], alpha) (render.py:261-262) returns exactly bg or exactly [rgb,1]:
-            # start from the background and overwrite the covered pixels -- same bits, a third of the passes over the image
-            vals = rendered[key]
-            c1 = vals.shape[-1] + 1
-            if key in ("shaded", "geo_normal", "shading"):
-                bgk = background[..., 2:] if (key == "shading" and background.shape[-1] == 4) else background
-                accum = bgk.expand(rast.shape[0], -1, -1, -1).clone()
-            else:
-                accum = torch.zeros(*rast.shape[:3], c1, dtype=torch.float32, device=dev)
-            accum.view(-1, c1).index_copy_(0, rendered.pix, torch.cat((vals, torch.ones_like(vals[:, :1])), dim=-1))
+        elif key in rendered:
+            out_buffers.append(_composite_torch(key, [layer], background4, clip_f, tri, spp))
         else:
-            buf = rendered[key]
-            bg = background if key in ("shaded", "geo_normal", "shading") else torch.zeros_like(buf)
-            if key == "shading" and bg.shape[-1] == 4:
-                bg = bg[..., 2:]
-            alpha = coverage * buf[..., -1:]
-            accum = torch.lerp(bg, torch.cat((buf[..., :-1], torch.ones_like(buf[..., -1:])), dim=-1), alpha)  # render.py:261-262
-        if key in ANTIALIASED_MODES:
-            if analysis is None:
-                tri32 = ops.tri_int32(tri)
-                analysis = ops.AAAnalysis(rast, clip_f, ops.aa_topology(tri32, clip_f.shape[1]))
-            accum = ops.antialias(accum.contiguous().float(), rast, clip_f, tri, analysis=analysis)
-        out = util.avg_pool_nhwc(accum, spp) if spp > 1 else accum
-        out_buffers.append(_slice_mode(key, out).permute(0, 3, 1, 2))
+            out_buffers.append(None)
     return out_buffers
 
 
 _msaa_shift = {}
 
 
-def _render_mesh_msaa(mesh, clip_f, tri, w2c, view_pos, material, lgt, resolution, spp, background, bsdf, feat, render_modes, prior_mesh,
-                      two_sided_shading, dino_net, class_vector, delta_xy):
+def _render_mesh_msaa(clip_f, tri, layer_args, spp, background, bsdf, layer_kwargs):
     """render_mesh(spp = s > 1, msaa = True, num_layers = 1) with the reference's semantics (render.py:170-171, 217-219, 258-268, 318) and
     none of its full-resolution images.  The reference shades at the nearest-minified raster -- texel (y s, x s) of every s x s block -- ALL
     low-resolution pixels with alpha 1, replicates the result over the block, composites with the full-resolution coverage, antialiases
     at full resolution and averages the blocks.  Here the covered shading samples are shaded as a point list (the spp 1 kernels on
     rast[:, ::s, ::s]), a block whose shading sample is uncovered takes the image's `null` row -- shade() on all-zero attributes, which is
-    what the reference evaluates there -- and ops.msaa_composite_antialias does the rest on the shading grid."""
+    what the reference evaluates there -- and ops.msaa_composite_antialias does the rest on the shading grid.
+    ``layer_args`` / ``layer_kwargs``: render_layer's, as render_mesh made them (the route among them)."""
+    mesh, w2c, view_pos, material, lgt, resolution = layer_args
+    render_modes, feat, dino_net = layer_kwargs["render_modes"], layer_kwargs["feat"], layer_kwargs["dino_net"]
     s, (h, w) = int(spp), resolution
     dev = clip_f.device
-    job = mesh.normals_job() if hasattr(mesh, "normals_job") else None
-    rast = ops.rasterize(clip_f, tri, [h * s, w * s], normals_job=job)
-    if job is not None:
-        mesh.take_normals(job, graph_pos=None)
-    LAST_RAST[0] = rast.detach()
-    LAST_POINTS[0] = None
+    rast = _rasterize_frame(mesh, clip_f, tri, [h * s, w * s])
     rast_s = rast.detach()[:, ::s, ::s].contiguous()
     # the G-buffer's backward re-derives the centre of shading pixel x as (x + 0.5) 2 / w - 1; the sample it was taken at, full-resolution
     # texel x s, lies (1 - 1/s) / w to the left of that: the geometry is handed over shifted by as much (autograd carries it back to clip)
@@ -731,17 +786,14 @@ def _render_mesh_msaa(mesh, clip_f, tri, w2c, view_pos, material, lgt, resolutio
     if key not in _msaa_shift:  # (kept per shape: building it is a host-to-device copy, which blocks)
         _msaa_shift[key] = torch.tensor([(1.0 - 1.0 / s) / w, (1.0 - 1.0 / s) / h, 0.0, 0.0], dtype=torch.float32, device=dev)
     clip_s = torch.addcmul(clip_f, clip_f[..., 3:4], _msaa_shift[key])
-    rendered = render_layer(rast_s, None, mesh, w2c, view_pos, material, lgt, resolution, 1, True, bsdf, feat=feat, render_modes=render_modes,
-                            prior_mesh=prior_mesh, two_sided_shading=two_sided_shading, delta_xy=delta_xy, dino_net=dino_net,
-                            class_vector=class_vector, clip=clip_s, sparse=True)
-    assert isinstance(rendered, SparseBuffers) and rendered.inv is not None
+    rendered = render_layer(rast_s, None, *layer_args, 1, True, bsdf, clip=clip_s, sparse=True, **layer_kwargs)
     B = rast.shape[0]
     zero = torch.zeros(B, 1, 1, 3, dtype=torch.float32, device=dev)
     flow0 = torch.zeros(B, 1, 1, rendered.peek("flow").shape[-1], dtype=torch.float32, device=dev) if "flow" in render_modes else None
     null = shade(zero, zero, zero, None, zero, w2c, view_pos, lgt, material, bsdf, feat=feat, render_modes=render_modes,
-                 two_sided_shading=two_sided_shading, delta_xy_interp=flow0, dino_net=dino_net if "dino_pred" in render_modes else None,
-                 class_vector=class_vector, cover=None)
-    analysis = ops.AAAnalysis(rast, clip_f, ops.aa_topology(ops.tri_int32(tri), clip_f.shape[1]))
+                 two_sided_shading=layer_kwargs["two_sided_shading"], delta_xy_interp=flow0, dino_net=dino_net if "dino_pred" in render_modes else None,
+                 class_vector=layer_kwargs["class_vector"], cover=None)
+    analysis = _frame_analysis(rast, clip_f, tri)
 
     null_of = lambda k: null[k][:, 0, 0, :-1].expand(B, -1)
     keys = [k for k in dict.fromkeys(render_modes) if k in rendered]
@@ -757,44 +809,23 @@ def _render_mesh_msaa(mesh, clip_f, tri, w2c, view_pos, material, lgt, resolutio
     return [done[k].permute(0, 3, 1, 2) if k in done else None for k in render_modes]
 
 
-def _render_mesh_layers(mesh, clip_f, tri, w2c, view_pos, material, lgt, resolution, spp, num_layers, msaa, background, bsdf, feat, render_modes,
-                        prior_mesh, two_sided_shading, dino_net, class_vector, delta_xy):
+def _render_mesh_layers(clip_f, tri, layer_args, spp, num_layers, msaa, background, bsdf, layer_kwargs):
     """render_mesh with ``num_layers`` depth layers (reference render.py:258-268, 290-337): every layer is rasterised behind the previous
-    one (DepthPeeler), shaded, and the layers are composited back to front, antialiasing after each layer with that layer's geometry."""
-    dev = clip_f.device
+    one (DepthPeeler), shaded, and the layers are composited back to front, antialiasing after each layer with that layer's geometry.
+    ``layer_args`` / ``layer_kwargs``: render_layer's, as render_mesh made them (the route among them)."""
+    resolution, render_modes = layer_args[-1], layer_kwargs["render_modes"]
     full_res = [resolution[0] * spp, resolution[1] * spp]
     layers, prev = [], None
     for _ in range(num_layers):
         rast = ops.rasterize(clip_f, tri, full_res, prev=prev)
         prev = rast.detach()
-        rendered = render_layer(rast, None, mesh, w2c, view_pos, material, lgt, resolution, spp, msaa, bsdf, feat=feat, render_modes=render_modes,
-                                prior_mesh=prior_mesh, two_sided_shading=two_sided_shading, delta_xy=delta_xy, dino_net=dino_net,
-                                class_vector=class_vector, clip=None, sparse=False)
-        layers.append((rendered, rast, ops.AAAnalysis(rast, clip_f, ops.aa_topology(ops.tri_int32(tri), clip_f.shape[1]))))
+        rendered = render_layer(rast, None, *layer_args, spp, msaa, bsdf, **layer_kwargs)
+        layers.append([rendered, rast, _frame_analysis(rast, clip_f, tri)])
     LAST_RAST[0] = layers[0][1].detach()
-    if background is not None:
-        if spp > 1:
-            background = util.scale_img_nhwc(background, full_res, mag="nearest", min="nearest")
-        background = torch.cat((background, torch.zeros_like(background[..., 0:1])), dim=-1)
-    else:
-        background = torch.zeros(1, full_res[0], full_res[1], 4, dtype=torch.float32, device=dev)
-    out_buffers = []
-    for key in render_modes:
-        if key not in layers[0][0]:
-            out_buffers.append(None)
-            continue
-        accum = background if key in ("shaded", "geo_normal", "shading") else torch.zeros_like(layers[0][0][key])
-        if key == "shading" and accum.shape[-1] == 4:
-            accum = accum[..., 2:]
-        for buffers, rast, analysis in reversed(layers):
-            buf = buffers[key]
-            alpha = (rast[..., -1:] > 0).float() * buf[..., -1:]
-            accum = torch.lerp(accum, torch.cat((buf[..., :-1], torch.ones_like(buf[..., -1:])), dim=-1), alpha)
-            if key in ANTIALIASED_MODES:
-                accum = ops.antialias(accum.contiguous().float(), rast, clip_f, tri, analysis=analysis)
-        out = util.avg_pool_nhwc(accum, spp) if spp > 1 else accum
-        out_buffers.append(_slice_mode(key, out).permute(0, 3, 1, 2))
-    return out_buffers
+    if background is not None and spp > 1:
+        background = util.scale_img_nhwc(background, full_res, mag="nearest", min="nearest")
+    background4 = _lazy_background4(background, full_res, clip_f.device)
+    return [_composite_torch(key, layers, background4, clip_f, tri, spp) if key in layers[0][0] else None for key in render_modes]
 
 
 def render_uv(ctx, mesh, resolution, mlp_texture, feat=None):

@@ -22,8 +22,13 @@ def _dot(x, y):
     return torch.sum(x * y, -1, keepdim=True)
 
 
-def _hip_xfm_ok(points, matrix):
-    if not (HIP_XFM_POINTS and points.is_cuda and matrix.is_cuda and points.dtype == torch.float32 and matrix.dtype == torch.float32):
+def _on_gpu_f32(t):
+    return t.is_cuda and t.dtype == torch.float32
+
+
+def _hip_xfm_ok(points, matrix, on_gpu_f32=_on_gpu_f32):
+    """The clip transform's kernel takes these operands.  ``on_gpu_f32``: the caller's form of the device question (render._plan_route's)."""
+    if not (HIP_XFM_POINTS and on_gpu_f32(points) and on_gpu_f32(matrix)):
         return False
     if points.dim() != 3 or matrix.dim() != 3 or points.shape[2] != 3 or tuple(matrix.shape[1:]) != (4, 4):
         return False

@@ -51,6 +51,7 @@ PATH_FUNCTIONS = [  # (module under 3danimals_amd, attribute path)
     ("model.render.mesh", "Mesh.normals_job"), ("model.render.mesh", "Mesh.take_normals"),
     ("model.render.render", "render_mesh"), ("model.render.render", "render_layer"), ("model.render.render", "shade"),
     ("model.render.render", "_shade_points"), ("model.render.render", "interpolate"), ("model.render.render", "_render_mesh_layers"),
+    ("model.render.render", "_composite_torch"), ("model.render.render", "_rasterize_frame"),
     ("model.render.renderutils.ops", "xfm_points"), ("model.render.renderutils", "xfm_points"),
 ]
 F3_FUNCTIONS = [("ops", "reconstruction_losses"), ("ops", "flow_loss")]
