@@ -294,7 +294,9 @@ __device__ __forceinline__ void aa_edge_adjoint(const AaRec& rec, unsigned p0, i
 // (64 bits where no entry point bounds the image); W, its row stride; nc, the channels walked (of out's rows in the blend, those with a
 // gradient in the adjoint); pixel(p), what is looked up once per pixel of a record, and out_index(x), the element of out / g_out it maps
 // to; pre(x, c), the pre-blend value; scale(v), applied to a blend term and to an incoming gradient; kBlendZeros, whether a zero difference
-// is added too; grad(dst, c), the incoming gradient, and sink(x, c, v, role), where the colour adjoint of pixel x goes (role = 2 second + d).
+// is added too; grad(dst, c), the incoming gradient, and sink(x, c, v, role), where the colour adjoint of pixel x goes (role = 2 second + d);
+// kEdgeAdjoint, whether the walk also pushes d(loss)/d(alpha) onto the crossing edge's vertices (false: colour adjoints only, clip / tri /
+// g_clip are never touched).
 template <class Src>
 __device__ __forceinline__ void aa_blend_records(const Src& s, float* out, int n, const int* s_off, const AaRec* __restrict__ work, int capacity) {
     typedef typename Src::Idx Idx;
@@ -338,6 +340,7 @@ __device__ __forceinline__ void aa_adjoint_records(const Src& s, int n, const in
                 dd += gd * (s.pre(x1, c) - s.pre(x0, c));
             }
         }
+        if (!Src::kEdgeAdjoint) continue;
         dd = a3d_group_sum<32>(dd);  // (a record's 32 lanes are in the same trip)
         if (sub != 0 || clamped || dd == 0.f) continue;
         aa_edge_adjoint(rec, (unsigned)p0, d, di, use1, dd, clip, clip_batch, tri, V, H, W, xh, yh, g_clip);
@@ -346,7 +349,7 @@ __device__ __forceinline__ void aa_adjoint_records(const Src& s, int n, const in
 
 struct AaDenseSrc {  // a dense [B,H,W,C] image: every channel, every difference, 64-bit indices
     typedef long long Idx, Px;
-    static constexpr bool kBlendZeros = true;
+    static constexpr bool kBlendZeros = true, kEdgeAdjoint = true;
     const float *color, *g_out;
     float* g_color;
     int W, nc;
@@ -599,7 +602,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 struct AaCaSrc {
     typedef unsigned Idx;
     struct Px { unsigned p; int q; };
-    static constexpr bool kBlendZeros = false;
+    static constexpr bool kBlendZeros = false, kEdgeAdjoint = true;
     const CaJob& j;
     int W, nc;
     __device__ Px pixel(unsigned p) const { return Px{p, ca_point(j.s, p)}; }
@@ -680,6 +683,74 @@ __global__ __launch_bounds__(256) void ca_bwd_kernel(CaJob ja, CaJob jb, const A
     A3D_STAMP(3, 1);
     aa_adjoint_records(AaCaSrc{job, W, min(job.s.C + 1, job.gC)}, n, s_off, work, capacity, clip, clip_batch, tri, V, H, g_clip);
     A3D_STAMP(3, 5);
+}
+
+// ---- the background's gradient (a3d_ca_buffer.g_null at spp 1) ------------------------------------------------------------------------------
+// lerp(bg, [v, 1], coverage) hands an UNCOVERED pixel's pre-antialias adjoint to the background and a covered pixel's to the point row
+// (coverage is 0 or 1).  The covered side is ca_gather_kernel + ca_bwd_kernel, which run as they always do; a buffer that asks for its
+// background's gradient gets two launches more, and a call in which none asks gets none:
+//   dense   : g_bg[r, c] = the sum over the images b that read background pixel r (all B when the background is shared, else the one) of
+//             g_out[b, p, c] where pixel p of image b is uncovered -- one thread per element, the images in ascending order: plain stores,
+//             the same bits every run, zeros included (g_bg is fully written here);
+//   records : the walk of ca_bwd_kernel once more with a source that sinks the colour adjoints of the UNCOVERED pixels of a record into
+//             g_bg (float atomics, like the covered side's into g_vals) and has no edge adjoint: g_clip is ca_bwd_kernel's alone.
+struct CaBgJob {
+    const int* inv;      // [B*H*W]
+    const float* g_out;  // [B,H,W,gS], gC leading channels have a gradient
+    float* g_bg;         // [n_pix, bgC]
+    int gS, gC, bgC;
+    int images;          // images summed into one background pixel: B for a shared background, else 1
+    unsigned hw, n_pix;  // pixels of an image, of the background (bg_batch H W)
+};
+
+// 256 background pixels per work-group, their bgC floats as one contiguous run (ca_gather_kernel's index arithmetic)
+__global__ __launch_bounds__(256) void ca_bg_dense_kernel(CaBgJob ja, CaBgJob jb) {
+    const CaBgJob& j = blockIdx.y ? jb : ja;
+    const unsigned base = blockIdx.x * 256u;
+    if (base >= j.n_pix) return;
+    const int* __restrict__ inv = j.inv;
+    const float* __restrict__ g_out = j.g_out;
+    const int cb = j.bgC, nloc = (int)min(256u, j.n_pix - base) * cb;
+    const float rc = 1.f / (float)cb;
+    float* o = j.g_bg + (long long)base * cb;
+    for (int e = threadIdx.x; e < nloc; e += 256) {
+        const int pl = (int)(((float)e + 0.5f) * rc), c = e - pl * cb;
+        float acc = 0.f;
+        if (c < j.gC)
+            for (int b = 0; b < j.images; ++b) {
+                const long long p = (long long)b * j.hw + base + pl;
+                if (inv[p] < 0) acc += g_out[p * j.gS + c];
+            }
+        o[e] = acc;
+    }
+}
+
+struct AaCaBgSrc {  // the composited image as AaCaSrc sees it, the adjoints of its uncovered pixels to the background's gradient
+    typedef unsigned Idx;
+    typedef AaCaSrc::Px Px;
+    static constexpr bool kBlendZeros = false, kEdgeAdjoint = false;
+    AaCaSrc a;
+    float* g_bg;
+    int W, nc;
+    __device__ Px pixel(unsigned p) const { return a.pixel(p); }
+    __device__ unsigned out_index(const Px& x) const { return x.p; }
+    __device__ float pre(const Px&, int) const { return 0.f; }  // (only d(loss)/d(alpha) reads it, which this walk does not form)
+    __device__ float scale(float v) const { return v; }
+    __device__ float grad(unsigned dst, int c) const { return a.grad(dst, c); }
+    __device__ void sink(const Px& x, int c, float v, int) const {
+        const CaSrc& s = a.j.s;
+        if (x.q >= 0 || c >= s.bgC) return;
+        atomicAdd(g_bg + (long long)(s.bg_shared ? x.p % s.hw : x.p) * s.bgC + c, v);
+    }
+};
+
+__global__ __launch_bounds__(256) void ca_bg_records_kernel(CaJob ja, CaJob jb, float* g_bg_a, float* g_bg_b, const AaRec* __restrict__ work,
+                                                            const int* __restrict__ count, int capacity, int H, int W) {
+    __shared__ int s_off[AA_SHARDS + 1];
+    const CaJob& job = blockIdx.y ? jb : ja;
+    const int n = aa_segment_offsets(count, capacity, s_off);
+    const int nc = min(job.s.bgC, job.gC);
+    aa_adjoint_records(AaCaBgSrc{AaCaSrc{job, W, nc}, blockIdx.y ? g_bg_b : g_bg_a, W, nc}, n, s_off, work, capacity, nullptr, 0, nullptr, 0, H, nullptr);
 }
 
 // ---- the compositor in supersampled mode (a3d_ca_buffer.spp = s > 1) -----------------------------------------------------------------------
@@ -773,7 +844,7 @@ __global__ __launch_bounds__(256) void ms_compose_kernel(MsJob ja, MsJob jb, MsG
 struct AaMsSrc {
     typedef unsigned Idx;
     struct Px { MsSample m; int row; };
-    static constexpr bool kBlendZeros = false;
+    static constexpr bool kBlendZeros = false, kEdgeAdjoint = true;
     const MsJob& j;
     const MsGrid& g;
     int W, nc;
@@ -1151,6 +1222,8 @@ static int ca_ride(const a3d_aa_ride* r, const float* rast_override, void* work,
 // the header without them (size = the offset of `spp`) gets the spp 1 compositor.  No header ever ended between the two sizes.
 static bool ca_size_ok(const a3d_ca_buffer* b) { return b->size == offsetof(a3d_ca_buffer, spp) || b->size >= sizeof(a3d_ca_buffer); }
 static int ca_spp(const a3d_ca_buffer* b) { return b->size >= sizeof(a3d_ca_buffer) ? b->spp : 0; }
+// the background's gradient of an spp 1 buffer: g_null, which has no null rows to serve there (a3d.h)
+static float* ca_g_bg(const a3d_ca_buffer* b) { return (b->size >= sizeof(a3d_ca_buffer) && b->spp <= 1) ? b->g_null : nullptr; }
 
 static MsJob ms_job(const a3d_ca_buffer* b, long long P) {
     MsJob j;
@@ -1270,7 +1343,10 @@ extern "C" int a3d_composite_aa_bwd(const a3d_ca_buffer* first, const a3d_ca_buf
                                     const int32_t* tri, int B, int V, int F, int H, int W, float* g_clip, const a3d_ca_shade* shade_or_null,
                                     a3d_stream_t stream) {
     A3D_CHECK_ARG(first && ca_size_ok(first) && (!second_or_null || ca_size_ok(second_or_null)));
-    if (ca_spp(first) > 1 || (second_or_null && ca_spp(second_or_null) > 1))
+    const bool supersampled = ca_spp(first) > 1 || (second_or_null && ca_spp(second_or_null) > 1);
+    for (const a3d_ca_buffer* b : {first, second_or_null})  // a background's gradient: of a background (spp 1: ca_g_bg)
+        if (b && !supersampled && ca_g_bg(b)) A3D_CHECK_ARG(b->bg);
+    if (supersampled)
         return ms_bwd(first, second_or_null, P, inv, work, count, capacity, clip, clip_batch, tri, B, V, F, H, W, g_clip, shade_or_null != nullptr, stream);
     A3D_CHECK_ARG(inv && work && count && clip && g_clip && B > 0 && V > 0 && H > 0 && W > 0 && P >= 0 && capacity > 0);
     A3D_CHECK_ARG((long long)B * H * W < 0x7FFFFFFFll && (clip_batch == 1 || clip_batch == B) && (P == 0 || pix));
@@ -1304,6 +1380,30 @@ extern "C" int a3d_composite_aa_bwd(const a3d_ca_buffer* first, const a3d_ca_buf
         hipLaunchKernelGGL(ca_bwd_kernel, dim3(1024, two ? 2 : 1), dim3(256), 0, s, ja, jb, (const AaRec*)work, count, capacity, (const float4*)clip,
                            clip_batch, tri, V, H, W, g_clip);
         A3D_LAUNCH_CHECK();
+    }
+    {   // the buffers that ask for their background's gradient (none: nothing more is launched)
+        CaJob aj[2] = {ja, ja};
+        CaBgJob bj[2] = {};
+        unsigned asking = 0, widest = 0;
+        for (const a3d_ca_buffer* b : {first, second_or_null}) {
+            if (!b || !ca_g_bg(b)) continue;
+            const CaJob& j = b == first ? ja : jb;
+            CaBgJob& d = bj[asking];
+            d.inv = inv; d.g_out = j.g_out; d.g_bg = ca_g_bg(b); d.gS = j.gS; d.gC = j.gC; d.bgC = j.s.bgC;
+            d.images = j.s.bg_shared ? B : 1; d.hw = j.s.hw; d.n_pix = (j.s.bg_shared ? 1u : (unsigned)B) * j.s.hw;
+            widest = d.n_pix > widest ? d.n_pix : widest;
+            aj[asking++] = j;
+        }
+        if (asking) {
+            if (asking == 1) { aj[1] = aj[0]; bj[1] = bj[0]; }
+            hipLaunchKernelGGL(ca_bg_dense_kernel, dim3((unsigned)a3d_div_up(widest, 256), asking), dim3(256), 0, s, bj[0], bj[1]);
+            A3D_LAUNCH_CHECK();
+            if (F != 0) {
+                hipLaunchKernelGGL(ca_bg_records_kernel, dim3(1024, asking), dim3(256), 0, s, aj[0], aj[1], bj[0].g_bg, bj[1].g_bg, (const AaRec*)work,
+                                   count, capacity, H, W);
+                A3D_LAUNCH_CHECK();
+            }
+        }
     }
     if (depth && dj.P > 0) {
         hipLaunchKernelGGL(dp_bwd_kernel, dim3(B), dim3(DP_BWD_THREADS), 0, s, dj, (const float*)first->g_vals, (const float*)shade_or_null->g_depth_slots,

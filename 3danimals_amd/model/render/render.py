@@ -23,7 +23,8 @@ The route of a call (_Route, filled once by _plan_route; first match; DESIGN.md 
   layers    num_layers != 1                                                                     _render_mesh_layers: ops.rasterize(prev=), dense render_layer
   msaa      FUSED_MSAA, msaa, spp 2..8, 'covered' on the shading grid with the one-launch       _render_mesh_msaa: ops.covered_gbuffer,
             list, the fused compositor, device float32 operands, no autocast                    ops.msaa_composite_antialias
-  mask      no material / light / DINO net, modes ['shaded'], spp 1, the fused compositor       ops.mask_antialias
+  mask      no material / light / DINO net, modes ['shaded'], spp 1, the fused compositor,      ops.mask_antialias
+            no background that requires grad
   covered   a clip set per image, spp 1, normals indexed like positions, every 'depth' /        ops.covered_gbuffer | ops.covered_pixels + ops.gbuffer,
             'tangent' asked for served                                                          _shade_points, _composite_modes | _composite_torch
   dense     otherwise                                                                           ops.interpolate, shade, _composite_torch
@@ -64,6 +65,10 @@ FUSED_MSAA = os.environ.get("A3D_FUSED_MSAA", "0") not in ("0", "")
 # depth is computed by the compositor from the G-buffer rows (ops.depth_composite_antialias); off = both modes switch the whole call to
 # the generic path, as they always do where _plan_route's conditions for them fail (tools/bench_render_modes.py)
 FUSED_DEPTH_TANGENT = os.environ.get("A3D_FUSED_DEPTH_TANGENT", "1") not in ("0", "")
+# a background that requires grad through the fused compositor, which then returns its gradient (a3d_ca_buffer.g_null at spp 1; spp 1, one layer, not
+# the mask render).  OFF unless A3D_FUSED_BACKGROUND_GRAD=1: such a call takes the torch compositor + ops.antialias as it always did
+# ("Background gradient"; tools/bench_background_grad.py)
+FUSED_BACKGROUND_GRAD = os.environ.get("A3D_FUSED_BACKGROUND_GRAD", "0") not in ("0", "")
 ALIAS_POSITIONS = os.environ.get("A3D_ALIAS_POSITIONS", "1") != "0"  # the clip transform's node feeds the G-buffer's position attribute too (one accumulation launch less)
 FIELD_INPUTS_FROM_GBUFFER = os.environ.get("A3D_FIELD_INPUTS", "1") != "0"  # the fields' padded input rows + image index written by the G-buffer launch (round 6)
 SHADE_IN_COMPOSITOR = os.environ.get("A3D_SHADE_IN_COMPOSITOR", "1") != "0"  # no a3d_shade_fwd launch when only the composited colour reads its output  # shading normal + camera normal + directional light of the covered pixels in one HIP kernel (csrc/shade.hip)
@@ -447,7 +452,11 @@ def _plan_route(render_modes, mesh, w2c, resolution, spp=1, num_layers=1, msaa=F
     flow_delta = top and "flow" in modes and FUSED_FLOW_DELTA and clip_gpu and num_frames > 1 and clip_b % num_frames == 0 and not autocast
     if num_layers != 1:  # depth peeling: never used by a config (AnimalModel.py:247); every layer on the dense path
         return _Route("layers", flow_delta=flow_delta)
-    can_composite = top and FUSED_COMPOSITE and (background is None or not background.requires_grad)  # (the compositor gives the background no gradient)
+    # the fused compositor: a background that requires grad only under FUSED_BACKGROUND_GRAD, at spp 1, and not in a mask-shaped call (the
+    # mask render has no background gradient, and such a call keeps the route it has with the switch off)
+    bg_grad = background is not None and background.requires_grad
+    mask_shaped = material is None and lgt is None and dino_net is None and list(render_modes) == ["shaded"] and spp == 1
+    can_composite = top and FUSED_COMPOSITE and (not bg_grad or (FUSED_BACKGROUND_GRAD and spp == 1 and not (FUSED_MASK_RENDER and mask_shaped)))
 
     asked, served = _DEPTH_TANGENT.intersection(modes), frozenset()
     if asked and top and clip_b == b and FUSED_DEPTH_TANGENT and spp == 1 and not autocast and _on_gpu_f32(mesh.v_pos):
@@ -467,7 +476,7 @@ def _plan_route(render_modes, mesh, w2c, resolution, spp=1, num_layers=1, msaa=F
 
     if top and FUSED_MSAA and msaa and 2 <= spp <= 8 and one_launch and can_composite and clip_gpu and not autocast and flow_cols <= 3:
         return _Route("msaa", one_launch=True, extra=extra, composite=True, flow_delta=flow_delta)  # (the point list lives on the shading grid: spp 1 there)
-    if can_composite and FUSED_MASK_RENDER and material is None and lgt is None and dino_net is None and list(render_modes) == ["shaded"] and spp == 1:
+    if can_composite and FUSED_MASK_RENDER and mask_shaped:
         return _Route("mask", alias=alias)
     if rows and spp == 1:
         return _Route("covered", one_launch, DEFER_RESOLVE and top and one_launch, extra, served, can_composite, alias, flow_delta)

@@ -1726,11 +1726,13 @@ class _CaBuf:
     contiguous in the channels the caller keeps, and its gradient arrives without a SliceBackward (a zero fill and a strided copy of the
     whole image) in front of it.
     ``vals`` may have MORE rows than the list (the fields' padded point list): the extra rows are never read and their gradient rows are
-    written as zeros by the same launches."""
-    __slots__ = ("C", "k", "rows", "grid", "spp")
+    written as zeros by the same launches.
+    ``bg_grad``: the background is a differentiable input of the node (spp 1 only): the backward allocates its gradient and asks the
+    library for it (a3d_ca_buffer.g_null at spp 1); False: nothing is allocated and nothing more is launched."""
+    __slots__ = ("C", "k", "rows", "grid", "spp", "bg_grad")
 
     @staticmethod
-    def of(vals, null_vals, background, keep, grid, P, spp, C=None):
+    def of(vals, null_vals, background, keep, grid, P, spp, C=None, bg_grad=False):
         """(description, (vals, null_vals, background) as float32 contiguous tensors); ``spp``: None or (s, aa)."""
         B, h, w = grid
         if vals is not None:
@@ -1745,7 +1747,8 @@ class _CaBuf:
             assert background.shape[1:3] == (h, w) and background.shape[3] <= C + 1 and background.shape[0] in (1, B)
         b = _CaBuf()
         b.C, b.k, b.rows, b.grid, b.spp = C, (C + 1 if keep is None else int(keep)), (P if vals is None else vals.shape[0]), grid, spp
-        assert 1 <= b.k <= C + 1
+        b.bg_grad = bool(bg_grad)
+        assert 1 <= b.k <= C + 1 and not (b.bg_grad and (background is None or spp is not None))
         return b, (vals, null_vals, background)
 
     def struct(self, tensors, rast_full):
@@ -1765,8 +1768,8 @@ class _CaBuf:
         return st, out
 
     def backward(self, tensors, g_out, rast_full, dev):
-        """(the struct of the backward call, g_vals, g_null or None, the gradient image the struct points to) for the saved ``tensors``
-        and the incoming gradient ``g_out``."""
+        """(the struct of the backward call, g_vals, g_null or None, the gradient image the struct points to, g_bg or None) for the saved
+        ``tensors`` and the incoming gradient ``g_out``."""
         if g_out is None:
             # an output nobody differentiated: zeros in the shape of the image that was handed out, which is what autograd itself would
             # materialise (k channels; the channels past g_channels have no gradient anyway)
@@ -1779,7 +1782,11 @@ class _CaBuf:
         if self.spp is not None:
             g_null = torch.empty_like(tensors[1])
             st.g_null = ptr(g_null)
-        return st, g_vals, g_null, g_out
+        g_bg = None
+        if self.bg_grad:  # (fully written by the call, its zeros included)
+            g_bg = torch.empty_like(tensors[2])
+            st.g_null = ptr(g_bg)  # (at spp 1 the field is the background's gradient: a3d.h)
+        return st, g_vals, g_null, g_out, g_bg
 
     def tag(self, cut):
         """'C17', or 'C17>16' for a 17-channel composite of which 16 channels are materialised (``cut``: the tag says so)."""
@@ -1898,15 +1905,22 @@ _ROWS, _DEPTH, _SHADED = _Source(), _Depth(), (_Shaded(False), _Shaded(True))
 class _Compositor(torch.autograd.Function):
     """The fused compositor (a3d_composite_aa_fwd / _bwd): one or two buffers (vals2 None = one) against the same pixel list and crossing
     records, in the same launches.  ``src`` (a _Source) says what the first buffer is made of.  ``opts`` = (pix, inv, background,
-    background2, analysis, keep, keep2, spp): what autograd need not see; ``spp`` = (s, aa) puts the call in supersampled mode
+    background2, analysis, keep, keep2, spp): what autograd need not see -- a background that requires grad comes as ``bg_diff`` /
+    ``bg2_diff`` instead (spp 1 only; its entry in ``opts`` is then None) and gets the adjoint of the uncovered pixels back
+    (a3d_ca_buffer.g_null at spp 1); ``spp`` = (s, aa) puts the call in supersampled mode
     (a3d_ca_buffer.spp > 1): rows and backgrounds on the SHADING grid [B,h,w], composited with the coverage of ``rast_full``,
     antialiased with the full-resolution crossing records and averaged per s x s block -- without any full-resolution image -- with the
     per-image null rows as further differentiable inputs.  Returns (image, second image or None) + the source's further outputs."""
 
     @staticmethod
-    def forward(ctx, src, opts, vals, null_vals, vals2, null_vals2, clip, gb, w2c, view, light, all_tex, rast_full):
+    def forward(ctx, src, opts, vals, null_vals, vals2, null_vals2, clip, gb, w2c, view, light, all_tex, rast_full, bg_diff=None, bg2_diff=None):
         pix, inv, bg, bg2, a, keep, keep2, spp = opts
-        require_device(vals, null_vals, vals2, null_vals2, pix, inv, rast_full, gb, w2c, all_tex, what=src.what if spp is None else "msaa_composite_antialias")
+        assert (bg is None or bg_diff is None) and (bg2 is None or bg2_diff is None) and (spp is None or (bg_diff is None and bg2_diff is None))
+        ask, ask2 = bg_diff is not None and ctx.needs_input_grad[13], bg2_diff is not None and ctx.needs_input_grad[14]
+        ctx.bg_dtypes = (None if bg_diff is None else bg_diff.dtype, None if bg2_diff is None else bg2_diff.dtype)
+        bg, bg2 = (bg if bg_diff is None else bg_diff), (bg2 if bg2_diff is None else bg2_diff)
+        require_device(vals, null_vals, vals2, null_vals2, pix, inv, rast_full, gb, w2c, all_tex, bg_diff, bg2_diff,
+                       what=src.what if spp is None else "msaa_composite_antialias")
         P, dev = pix.shape[0], pix.device
         grid = (a.B, a.H, a.W)
         assert src.C is None or (vals is None and spp is None)
@@ -1917,8 +1931,8 @@ class _Compositor(torch.autograd.Function):
             grid, rast_full, spp = (a.B, a.H // s, a.W // s), f32c(rast_full.detach()), (s, int(bool(spp[1])))
             assert rast_full.shape == (a.B, a.H, a.W, 4)
         assert pix.dtype == torch.int64 and inv.shape == (grid[0] * grid[1] * grid[2],) and inv.dtype == torch.int32
-        first, t1 = _CaBuf.of(vals, null_vals, bg, keep, grid, P, spp, C=src.C)
-        second, t2 = (None, (None,) * 3) if vals2 is None else _CaBuf.of(vals2, null_vals2, bg2, keep2, grid, P, spp)
+        first, t1 = _CaBuf.of(vals, null_vals, bg, keep, grid, P, spp, C=src.C, bg_grad=ask)
+        second, t2 = (None, (None,) * 3) if vals2 is None else _CaBuf.of(vals2, null_vals2, bg2, keep2, grid, P, spp, bg_grad=ask2)
         sh, kept, outputs, src_saved = src.forward(ctx, (gb, w2c, view, light, all_tex), pix, grid, dev)
         cut = src.cut_in_tag and spp is None
         tag = ("" if spp is None else f"[spp{spp[0]}]") + "[" + (src.name or first.tag(cut)) + ("" if second is None else "+" + second.tag(cut)) + "]"
@@ -1940,15 +1954,17 @@ class _Compositor(torch.autograd.Function):
     def backward(ctx, g_out, g_out2=None, *_):
         pix, inv, rast_full, *t = ctx.saved_tensors
         a, src, first, second, P, dev = ctx.analysis, ctx.src, ctx.first, ctx.second, pix.shape[0], pix.device
-        sa, g_vals, g_null, g_out = first.backward(t[0:3], g_out, rast_full, dev)
-        sb, g_vals2, g_null2, g_out2 = (None,) * 4 if second is None else second.backward(t[3:6], g_out2, rast_full, dev)
+        sa, g_vals, g_null, g_out, g_bg = first.backward(t[0:3], g_out, rast_full, dev)
+        sb, g_vals2, g_null2, g_out2, g_bg2 = (None,) * 5 if second is None else second.backward(t[3:6], g_out2, rast_full, dev)
         g_clip = torch.empty_like(a.clip)
         sh, state = src.backward(ctx, t[0], t[6:], pix, dev)
         call("a3d_composite_aa_bwd", ctypes.addressof(sa), None if sb is None else ctypes.addressof(sb), ptr(pix), P, ptr(inv), ptr(a.work),
              ptr(a.count), a.capacity, ptr(a.clip), a.clip.shape[0], ptr(a.topo.tri), a.B, a.clip.shape[1], a.topo.tri.shape[0], a.H, a.W, ptr(g_clip),
              None if sh is None else ctypes.addressof(sh), stream(), tag=ctx.tag)
         g_src = src.finish(ctx, state, g_vals, t[6:], pix, first.grid, dev)
-        return (None, None, None if src.C is not None else g_vals, g_null, g_vals2, g_null2, g_clip) + g_src + (None,)
+        # (a background that came in another dtype went through f32c's cast: its gradient goes back in that dtype)
+        g_bg, g_bg2 = (g if g is None or g.dtype == d else g.to(d) for g, d in zip((g_bg, g_bg2), ctx.bg_dtypes))
+        return (None, None, None if src.C is not None else g_vals, g_null, g_vals2, g_null2, g_clip) + g_src + (None, g_bg, g_bg2)
 
 
 def _shade_params(w2c, view, light):
@@ -1968,33 +1984,40 @@ def _depth_source(gb, w2c, pix, state, rows, g_gb, slots=None):
 
 def _composite(src, pix, inv, clip, analysis, vals=None, vals2=None, background=None, background2=None, keep=None, keep2=None, null_vals=None,
                null_vals2=None, recipe=(None,) * 5, rast_full=None, msaa=None):
-    """What the public functions below share: the backgrounds get no gradient, one clip batch, (image[, second image]) + further outputs."""
-    assert background is None or not background.requires_grad
-    assert background2 is None or not background2.requires_grad
+    """What the public functions below share: one clip batch, (image[, second image]) + further outputs; a background that requires grad
+    goes to the node as a differentiable input (the others stay out of autograd's sight: nothing is allocated or launched for them) --
+    at spp 1; in supersampled mode it is refused."""
+    diff = [b if b is not None and b.requires_grad else None for b in (background, background2)]
+    assert msaa is None or (diff[0] is None and diff[1] is None), ("msaa_composite_antialias: a background that requires grad gets no gradient in supersampled mode -- "
+                                                            "composite with torch and call antialias (render_mesh sends such a call down its generic path)")
     if clip.dim() == 2:
         clip = clip[None]
-    o1, o2, *more = _Compositor.apply(src, (pix, inv, background, background2, analysis, keep, keep2, msaa), vals, null_vals, vals2, null_vals2, clip, *recipe,
-                                      rast_full)
+    plain = [None if d is not None else b for b, d in zip((background, background2), diff)]
+    o1, o2, *more = _Compositor.apply(src, (pix, inv, plain[0], plain[1], analysis, keep, keep2, msaa), vals, null_vals, vals2, null_vals2, clip, *recipe,
+                                      rast_full, *diff)
     return (o1 if vals2 is None else (o1, o2)), more
 
 
 def composite_antialias(vals, pix, inv, background, clip, analysis, vals2=None, background2=None, keep=None, keep2=None):
     """antialias(lerp(background, [vals, 1], coverage)) for a buffer given as rows ``vals`` [>= P,C] at the covered pixels ``pix`` (``inv`` =
     the pixel -> row map of covered_pixels(return_inverse=True)): [B,H,W,C+1].  ``background`` [1|B,H,W,<= C+1] (missing trailing channels
-    = 0: the reference's 3-channel background as it is) or None (zeros); it gets no gradient (callers with a differentiable background
-    composite with torch and call antialias).  With ``vals2`` (and ``background2``) a second buffer over the same pixels is composited
+    = 0: the reference's 3-channel background as it is) or None (zeros).  A background that requires grad gets its gradient from the same
+    backward call: the adjoint of the uncovered pixels -- the incoming gradient plus the blend adjoints of the crossing records -- summed
+    over the images when it is shared; a covered pixel contributes exactly zero (a3d_ca_buffer.g_null at spp 1; one that does not require grad
+    costs nothing).  With ``vals2`` (and ``background2``, differentiable alike) a second buffer over the same pixels is composited
     and antialiased by the same launches: returns the pair of images.  ``keep`` / ``keep2``: see _CaBuf."""
     return _composite(_ROWS, pix, inv, clip, analysis, vals, vals2, background, background2, keep, keep2)[0]
 
 
 def shade_composite_antialias(recipe, pix, inv, background, clip, analysis, vals2=None, background2=None, keep2=None):
     """composite_antialias for the shaded colour of ``recipe`` (a ShadeRecipe) as first buffer: the colour is computed inside the launches,
-    and one backward node runs compositor gather + shading adjoint (see _Shaded)."""
+    and one backward node runs compositor gather + shading adjoint (see _Shaded).  The backgrounds as in composite_antialias, their
+    gradients included."""
     r = recipe
     if background is not None:
         background = f32c(background)
         if background.shape[3] == 4 and background.data_ptr() % 16:  # (an offset view: the compose kernel reads 4-channel texels as 16-byte loads)
-            background = background.clone()
+            background = background.clone()  # (a differentiable copy: a background that requires grad keeps its graph)
     return _composite(_SHADED[bool(r.two_sided)], pix, inv, clip, analysis, None, vals2, background, background2, None, keep2,
                       recipe=(r.gb, r.w2c, r.view_pos, r.light, r.all_tex))[0]
 
@@ -2016,7 +2039,8 @@ def msaa_composite_antialias(vals, null_vals, pix, inv, rast_full, background, c
     rows ``vals`` [>= P,C] at the covered texels ``pix`` of the shading-sample raster rast_full[:, ::s, ::s] (``inv`` [B*h*w] its pixel ->
     row map) and ``null_vals`` [B,C], the value of a shading sample that is NOT covered: avg_pool(antialias(lerp(background, up([v, 1]),
     coverage of ``rast_full``))) as [B,h,w,C+1].  ``analysis``: the AAAnalysis of (rast_full, clip), full resolution.  ``background``
-    [1|B,h,w,<= C+1] on the shading grid (its nearest up-scale is what the reference composites over) or None; no gradient.
+    [1|B,h,w,<= C+1] on the shading grid (its nearest up-scale is what the reference composites over) or None; no gradient: one that
+    requires grad is refused (the background's gradient exists at spp 1 only: composite_antialias).
     ``antialias`` False: composite and average only.  A second buffer and ``keep`` / ``keep2`` as in composite_antialias."""
     return _composite(_ROWS, pix, inv, clip, analysis, vals, vals2, background, background2, keep, keep2, null_vals,
                       null_vals2, rast_full=rast_full, msaa=(spp, antialias))[0]
@@ -2073,7 +2097,10 @@ class _MaskAntialias(torch.autograd.Function):
 
 def mask_antialias(rast, clip, background, analysis, channels=3):
     """[B,H,W,channels+1]: ones where ``rast`` is covered, ``background`` ([1|B,H,W,channels+1] or None = zeros) elsewhere, antialiased
-    with ``analysis`` (an AAAnalysis of the same rast / clip; may still be pending: it then runs inside this op's first launch)."""
+    with ``analysis`` (an AAAnalysis of the same rast / clip; may still be pending: it then runs inside this op's first launch).  Only
+    the silhouette is differentiated: a background that requires grad is refused."""
+    assert background is None or not background.requires_grad, ("mask_antialias: the background gets no gradient here -- a call with a background that "
+                                                                "requires grad goes through covered_pixels + composite_antialias (render_mesh: its covered-point path)")
     assert analysis.rast.data_ptr() == f32c(rast.detach()).data_ptr(), "the analysis must belong to this raster buffer"
     return _MaskAntialias.apply(rast.detach(), clip, background, analysis, int(channels))  # (coverage carries no gradient)
 

@@ -562,7 +562,8 @@ int a3d_aa_bwd(const float* g_out, const float* color, int C, const void* work, 
  * A second buffer (vals2 / C2 / bg2 / out2; null = none) against the same pixel list and crossing records rides in the same launches
  * (render_mesh antialiases the colour and the feature image of a step).
  * bwd: g_vals[P,C] (fully written: g_out at the covered pixels + the blend adjoints; no dense colour gradient exists) -- likewise
- *   g_vals2 -- and g_clip[clip_batch,V,4] (zeroed by callee; both buffers add to it).  The backgrounds receive no gradient. */
+ *   g_vals2 -- and g_clip[clip_batch,V,4] (zeroed by callee; both buffers add to it).  A background receives its gradient where the
+ *   buffer asks for it (a3d_ca_buffer.g_null at spp 1): the adjoint of the uncovered pixels; otherwise none is computed. */
 /* The silhouette analysis riding in the first launch of a compositor call (round 4: by name instead of ten positional arguments): the
  * arguments of a3d_aa_analyze(prepared = 1) -- rast, the `screen` and zeroed `count` that a3d_rast_fwd left (count is the compositor's own
  * argument), tri, opp or the vertex -> face lists. */
@@ -658,7 +659,18 @@ typedef struct a3d_ca_buffer {
     int32_t aa;          /* spp > 1: 0 = composite and average only (the modes the reference does not antialias: kd, ks, normal, geo_normal) */
     const float* cover_rast; /* [B,H,W,4] full-resolution raster texels (covered <=> id channel > 0) */
     const float* null_vals;  /* [B,C] value of a block whose shading sample is uncovered */
-    float* g_null;       /* backward: [B,C], fully written */
+    float* g_null;       /* backward, spp > 1: [B,C], fully written.
+                          * spp 0 or 1 (no null row exists: what an uncovered pixel shows is the background): the BACKGROUND's gradient,
+                          * [bg_batch,H,W,bg_channels], fully written; NULL = none, the behaviour above, bit for bit -- as for a caller whose
+                          * `size` ends at vals_rows.  No field, struct or export was added for it and a3d_version() stays 405.  With g_pre =
+                          * g_out (through g_stride / g_channels: the channels without a gradient zero) + the blend adjoints of the crossing
+                          * records w.r.t. the pre-antialias colour, element [b',p,c], c < bg_channels, = the sum of g_pre[b,p,c] over the images
+                          * b that read background image b' and whose pixel p is UNCOVERED (inv < 0); a covered pixel contributes exactly 0 (its
+                          * alpha is 1: render.py:261-262); bg_batch == 1: the B images summed into the one.  The dense part is summed in a fixed
+                          * order by a launch of its own (a thread per element, over the images), then the records' terms are added with float
+                          * atomics by a second one; the launches that write g_vals and g_clip are the same, with the same arguments, whether
+                          * a buffer asks or not.  Either buffer of a call may ask.  Non-NULL at spp 0 / 1 with bg == NULL is A3D_EINVAL before
+                          * anything is launched; a supersampled call has no background gradient (there the field is the null rows'). */
 } a3d_ca_buffer;
 int a3d_composite_aa_fwd(const a3d_ca_buffer* first, const a3d_ca_buffer* second_or_null, const int32_t* inv, void* work, int32_t* count,
                          int capacity, int B, int H, int W, const a3d_aa_ride* analyze_or_null, const a3d_ca_shade* shade_or_null,
