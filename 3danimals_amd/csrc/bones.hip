@@ -417,12 +417,33 @@ __global__ __launch_bounds__(EB_THREADS) void eb_kernel(const EbParams a) {
 
 extern "C" int a3d_estimate_bones(const a3d_estimate_bones_args* args, a3d_stream_t stream) {
     A3D_CHECK_ARG(args && args->size >= sizeof(a3d_estimate_bones_args));
+    // the resample tail (eb_common.h, include/a3d.h): the clouds are sampled first (fps.hip) and the bones come from the sampled points
+    const a3d_estimate_bones_args* const whole = args;  // the caller's clouds
+    const a3d_eb_fps_tail* tail = nullptr;
+    a3d_estimate_bones_args resampled;
+    if (args->size > sizeof(a3d_estimate_bones_args)) {
+        A3D_CHECK_ARG(args->size >= sizeof(a3d_estimate_bones_args) + sizeof(a3d_eb_fps_tail));
+        tail = reinterpret_cast<const a3d_eb_fps_tail*>(reinterpret_cast<const char*>(args) + sizeof(a3d_estimate_bones_args));
+        A3D_CHECK_ARG(args->pos && args->N > 0 && args->V > 0);
+        A3D_CHECK_ARG(args->V <= A3D_FPS_MAX_V && (long long)args->N * args->V <= A3D_EB_WIDE_MAX_POINTS);
+        A3D_CHECK_ARG(tail->k >= 1 && tail->k <= args->V);
+        A3D_CHECK_ARG(tail->start && tail->sampled);
+        A3D_CHECK_ARG(args->V <= A3D_FPS_REG_MAX_V || args->workspace);  // (beyond the register regime the running distances live there)
+        if (tail->sample_only) return a3d_eb_fps_launch(whole, tail, (hipStream_t)stream);
+        resampled = *args;  // the bones of the sampled clouds: validated below like any call, before the sampler is launched
+        resampled.size = sizeof(a3d_estimate_bones_args); resampled.pos = tail->sampled; resampled.V = tail->k;
+        args = &resampled;
+    }
     // one work-group (eb_kernel) for the calls it has always taken, the multi-work-group path (bones_wide.hip) for the others: N and V decide
     const bool wide = args->N > A3D_EB_ONE_GROUP_MAX_N || (long long)args->N * args->V > A3D_EB_ONE_GROUP_MAX_POINTS;
     A3D_CHECK_ARG(args->pos && args->bones && args->nearest && args->ok && args->workspace && args->N > 0 && args->V > 0);
     A3D_CHECK_ARG((long long)args->N * args->V <= A3D_EB_WIDE_MAX_POINTS && args->n_body >= 2 && args->n_body % 2 == 0 && args->n_body <= 32 && args->n_leg >= 0 && args->n_leg <= 8);
     A3D_CHECK_ARG(!wide || ((uintptr_t)args->workspace & 15) == 0);  // (histogram rows are read 16 bytes at a time, keys and sums are 8-byte words)
     A3D_CHECK_ARG(args->n_leg == 0 || (args->attach[0] < args->n_body && args->attach[1] < args->n_body && args->attach[2] < args->n_body && args->attach[3] < args->n_body));
+    if (tail) {
+        const int rc = a3d_eb_fps_launch(whole, tail, (hipStream_t)stream);
+        if (rc != A3D_OK) return rc;
+    }
     if (wide) return a3d_eb_wide_launch(args, (hipStream_t)stream);
     EbParams p;
     p.pos = args->pos; p.N = args->N; p.V = args->V; p.n_body = args->n_body; p.n_leg = args->n_leg; p.yplus = args->body_mode_y_plus;

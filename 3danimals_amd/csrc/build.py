@@ -26,6 +26,7 @@ SOURCES = {
     "skin.hip": [],
     "bones.hip": [],
     "bones_wide.hip": ["-ffp-contract=off"],
+    "fps.hip": ["-ffp-contract=off"],
     "normals.hip": ["-ffp-contract=off"],
     "raster.hip": ["-ffp-contract=off"],
     "cover.hip": [],

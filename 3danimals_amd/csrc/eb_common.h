@@ -1,11 +1,30 @@
 // estimate_bones on the device: what the one-group kernel (bones.hip, eb_kernel) and the multi-group path (bones_wide.hip) share -- the
 // monotone keys of the radix select, torch.quantile's rank arithmetic and torch.lerp, the bin search of one select pass, and the closed
-// forms of phase D (spine joints, body bone ends, attachment joint, leg bone ends; reference skinning.py:118-141, :187-215).  Device code only.
+// forms of phase D (spine joints, body bone ends, attachment joint, leg bone ends; reference skinning.py:118-141, :187-215) -- device code; and what the
+// entry point needs of the other files: the launcher of the wide path, the resample tail and the launcher of the sampler (fps.hip).
 #pragma once
+#include <stddef.h>
+
 #include "a3d_common.h"
 
 // the launches of a call on the multi-work-group path (bones_wide.hip); a3d_estimate_bones (bones.hip) has validated ``args``
 int a3d_eb_wide_launch(const a3d_estimate_bones_args* args, hipStream_t stream);
+
+// The resample tail of a3d_estimate_bones (include/a3d.h describes it in words: the public struct stays as it is).  A caller that wants
+// the clouds resampled first passes  size >= sizeof(a3d_estimate_bones_args) + A3D_FPS_TAIL_SIZE  and these bytes behind the public struct.
+typedef struct a3d_eb_fps_tail {
+    int32_t k;             /* points kept per cloud, 1 <= k <= V */
+    int32_t sample_only;   /* non-zero: the sampler alone; bones, nearest, ok are not touched and may be null */
+    const int64_t* start;  /* [N] on the device: each cloud's first pick (clamped into [0, V)) */
+    float* sampled;        /* [N, k, 3]: the picked points, in the order picked */
+    int64_t* idx;          /* [N, k]: their indices, or null */
+} a3d_eb_fps_tail;
+static_assert(sizeof(a3d_estimate_bones_args) % 8 == 0, "the tail follows the public struct without padding");
+static_assert(sizeof(a3d_eb_fps_tail) == A3D_FPS_TAIL_SIZE, "include/a3d.h states the tail's size");
+static_assert(offsetof(a3d_eb_fps_tail, k) == 0 && offsetof(a3d_eb_fps_tail, sample_only) == 4 && offsetof(a3d_eb_fps_tail, start) == 8 &&
+              offsetof(a3d_eb_fps_tail, sampled) == 16 && offsetof(a3d_eb_fps_tail, idx) == 24, "include/a3d.h states the tail's byte layout");
+// the sampler of a call with the tail (fps.hip); a3d_estimate_bones (bones.hip) has validated both
+int a3d_eb_fps_launch(const a3d_estimate_bones_args* args, const a3d_eb_fps_tail* tail, hipStream_t stream);
 
 #define EB_MAXSEL 12   // ranks looked for at once: 2 coordinates x 3 quantiles x the two neighbours a quantile interpolates between
 #define EB_MAXGROUP 6  // ... of one coordinate

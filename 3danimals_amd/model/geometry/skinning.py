@@ -81,6 +81,9 @@ DEVICE_ESTIMATE_BONES = os.environ.get("A3D_DEVICE_ESTIMATE_BONES", "1") != "0" 
 # ... also for the calls one work-group does not take (more than 32 instances or 2^22 points: csrc/bones_wide.hip); off: those go to the torch restatement
 DEVICE_ESTIMATE_BONES_WIDE = os.environ.get("A3D_ESTIMATE_BONES_WIDE", "1") != "0"
 
+# farthest-point sampling (estimate_bones(resample=True), util.sample_farthest_points) as a HIP kernel (csrc/fps.hip); off: the reference's torch loop
+DEVICE_FPS = os.environ.get("A3D_DEVICE_FPS", "1") != "0"
+
 
 def _body_chain(n_body_bones):
     """(bones_to_joints, kinematic_chain) of the spine (reference :128-141)."""
@@ -102,10 +105,11 @@ def _body_chain(n_body_bones):
 
 
 def _estimate_bones_device(seq_shape, n_body_bones, n_leg_bones, body_bones_mode, compute_kinematic_chain, aux, attach_legs_to_body,
-                           legs_to_body_joint_indices, bone_y_threshold):
+                           legs_to_body_joint_indices, bone_y_threshold, resample=None):
     """estimate_bones through a3d_estimate_bones (csrc/bones.hip, bones_wide.hip): ONE launch (a dozen beyond 32 instances) for the ~245 torch launches of the restatement below; the
     kinematic chain -- a Python structure -- is built here from the two attachment joints the launch hands back (the one read-back of a
-    chain rebuild, as before; none with a cached chain).  None: a cached ``aux`` this form does not cover (the caller takes the torch path)."""
+    chain rebuild, as before; none with a cached chain).  ``resample`` (k, start): the same call first samples k points of every mesh
+    (the resample tail of a3d_estimate_bones, csrc/fps.hip) and estimates the bones of those.  None: a cached ``aux`` this form does not cover (the caller takes the torch path)."""
     from ..._lib import defer_check, read_back
 
     b2j_body, chain_body = _body_chain(n_body_bones)
@@ -117,7 +121,8 @@ def _estimate_bones_device(seq_shape, n_body_bones, n_leg_bones, body_bones_mode
         if list(aux["bones_to_joints"]) != b2j_body or (n_leg_bones > 0 and any(list(l["leg_bones_to_joints"]) != leg_b2j for l in aux["legs"])):
             return None
         attach = [int(l["body_bone_idx"]) for l in aux["legs"]] if n_leg_bones > 0 else [0, 0, 0, 0]
-    bones, nearest, ok = ops.estimate_bones_device(seq_shape, n_body_bones, n_leg_bones, body_bones_mode == "z_minmax_y+", bone_y_threshold, attach)
+    bones, nearest, ok = ops.estimate_bones_device(seq_shape, n_body_bones, n_leg_bones, body_bones_mode == "z_minmax_y+", bone_y_threshold, attach,
+                                                   resample=resample)
     if n_leg_bones > 0:
         defer_check(ok[0], "estimate_bones: no vertex in a leg quadrant (the reference drops into pdb here, skinning.py:183)")
     if not compute_kinematic_chain:
@@ -158,7 +163,18 @@ def estimate_bones(seq_shape, n_body_bones, resample=False, n_legs=4, n_leg_bone
     """
     if resample:
         b, _, n, _ = seq_shape.shape
-        pts = util.sample_farthest_points(seq_shape.reshape(-1, n, 3).transpose(1, 2), n // 4)
+        clouds = seq_shape.reshape(-1, n, 3)
+        start = None
+        if (DEVICE_FPS and DEVICE_ESTIMATE_BONES and QUADRANT_POPULATION is None and body_bones_mode in ("z_minmax", "z_minmax_y+")
+                and ops.fps_device_ok(clouds, n // 4)
+                and ops.estimate_bones_device_ok(seq_shape[:, :, :n // 4], n_body_bones, n_leg_bones, n_legs, wide=DEVICE_ESTIMATE_BONES_WIDE)):
+            # sampler and bones in ONE a3d_estimate_bones call (the resample tail); the first picks are drawn as the torch path draws them
+            start = torch.randint(n, [clouds.shape[0]], device=seq_shape.device)
+            out = _estimate_bones_device(seq_shape, n_body_bones, n_leg_bones, body_bones_mode, compute_kinematic_chain, aux, attach_legs_to_body,
+                                         legs_to_body_joint_indices, bone_y_threshold, resample=(n // 4, start))
+            if out is not None:
+                return out
+        pts = util.sample_farthest_points(clouds.transpose(1, 2), n // 4, start=start)
         seq_shape = pts.transpose(1, 2).reshape(b, -1, n // 4, 3)
 
     if (DEVICE_ESTIMATE_BONES and QUADRANT_POPULATION is None and body_bones_mode in ("z_minmax", "z_minmax_y+")

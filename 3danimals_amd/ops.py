@@ -9,6 +9,7 @@ from __future__ import annotations
 import ctypes
 import math
 import os
+import struct
 from collections import OrderedDict
 
 import torch
@@ -440,10 +441,66 @@ def _linspace01(n):
     return _linspace_cache[n]
 
 
-def estimate_bones_device(seq_shape, n_body_bones, n_leg_bones, body_mode_y_plus, y_threshold, attach):
+# ---- the resample tail of a3d_estimate_bones (include/a3d.h; csrc/eb_common.h: a3d_eb_fps_tail).  Packed here, behind the public struct:
+# the registry of _lib mirrors the public headers and the tail is in none of them.
+FPS_TAIL = struct.Struct("<iiQQQ")  # k, sample_only, start, sampled, idx
+FPS_TAIL_FIELDS = ("k", "sample_only", "start", "sampled", "idx")
+FPS_TAIL_SIZE = 32   # A3D_FPS_TAIL_SIZE
+FPS_MAX_V = 131072   # A3D_FPS_MAX_V
+FPS_REG_MAX_V = 16384  # A3D_FPS_REG_MAX_V: beyond it the sampler keeps its running distances in the workspace
+
+
+def pack_fps_block(public, k, sample_only, start, sampled, idx):
+    """The bytes a3d_estimate_bones takes for a call that resamples first: ``public`` (an _lib.EstimateBonesArgs; its ``size`` is set
+    here) followed by the tail -- k, the sample-only flag and three device addresses (0 = null).  8-byte aligned, like the struct."""
+    n_public = ctypes.sizeof(_lib.EstimateBonesArgs)
+    assert n_public % 8 == 0 and FPS_TAIL.size == FPS_TAIL_SIZE
+    public.size = n_public + FPS_TAIL_SIZE
+    block = (ctypes.c_uint64 * ((n_public + FPS_TAIL_SIZE) // 8))()
+    ctypes.memmove(block, ctypes.addressof(public), n_public)
+    FPS_TAIL.pack_into(block, n_public, int(k), int(bool(sample_only)), start or 0, sampled or 0, idx or 0)
+    return block
+
+
+def fps_workspace_words(N, V):
+    """4-byte words of workspace the sampler itself needs (include/a3d.h: the running distances, beyond the register regime)."""
+    return N * V if V > FPS_REG_MAX_V else 0
+
+
+def fps_device_ok(pts, k):
+    """Whether the device sampler takes ``pts`` [N,V,3] (else: the torch loop of geometry/util.py)."""
+    return (pts.is_cuda and pts.dtype == torch.float32 and pts.dim() == 3 and pts.shape[2] == 3 and pts.shape[0] > 0
+            and 1 <= k <= pts.shape[1] <= FPS_MAX_V and pts.shape[0] * pts.shape[1] <= _lib.EB_WIDE_MAX_POINTS)
+
+
+def farthest_point_sample(pts, k, start, return_points=False):
+    """Greedy farthest-point sampling on the GPU (csrc/fps.hip): pts [N,V,3] float32, start int64 [N] on the same device (each cloud's
+    first pick) -> indices int64 [N,k]; with ``return_points`` also the points [N,k,3] (bit copies of pts).  One sample-only
+    a3d_estimate_bones call: one launch, one work-group per cloud, no host synchronisation.  Ties go to the lowest index; a NaN
+    distance counts as the greatest (csrc/fps.hip)."""
+    require_device(pts, start, what="farthest_point_sample")
+    if not fps_device_ok(pts, k):
+        raise _lib.A3DError(f"farthest_point_sample: pts {tuple(pts.shape)} {pts.dtype}, k = {k}: needs [N,V,3] float32 with 1 <= k <= V <= {FPS_MAX_V} "
+                            f"and N V <= {_lib.EB_WIDE_MAX_POINTS}")
+    pos = f32c(pts.detach())
+    N, V = pos.shape[:2]
+    start = start.to(torch.int64).contiguous()
+    assert start.shape == (N,)
+    idx = torch.empty((N, k), dtype=torch.int64, device=pos.device)
+    sampled = torch.empty((N, k, 3), dtype=torch.float32, device=pos.device)
+    words = fps_workspace_words(N, V)
+    work = torch.empty(words, dtype=torch.float32, device=pos.device) if words else None
+    a = _lib.EstimateBonesArgs(N=N, pos=ptr(pos), V=V, workspace=ptr(work))
+    block = pack_fps_block(a, k, True, ptr(start), ptr(sampled), ptr(idx))
+    call("a3d_estimate_bones", ctypes.addressof(block), stream())
+    return (idx, sampled) if return_points else idx
+
+
+def estimate_bones_device(seq_shape, n_body_bones, n_leg_bones, body_mode_y_plus, y_threshold, attach, resample=None):
     """a3d_estimate_bones: seq_shape [B,F,V,3] (float32, on the GPU) -> (bones [B,F,K,2,3], nearest int32 [2], ok int32 [1]) -- one launch
     of one work-group, or (estimate_bones_is_wide) a dozen launches of many; no host synchronisation either way.  ``attach``: the four legs' body joints (negative = found on the device, see include/a3d.h); ``y_threshold``
-    None or Fauna's bone_y_threshold."""
+    None or Fauna's bone_y_threshold.  ``resample`` (k, start int64 [B F]): the same call first reduces every cloud to k points by
+    farthest-point sampling (the resample tail, csrc/fps.hip) and estimates the bones of those."""
     require_device(seq_shape, what="estimate_bones")
     pos = f32c(seq_shape)
     B, Fr, V = pos.shape[:3]
@@ -452,9 +509,12 @@ def estimate_bones_device(seq_shape, n_body_bones, n_leg_bones, body_mode_y_plus
     bones = torch.empty((B, Fr, K, 2, 3), dtype=torch.float32, device=dev)
     nearest = torch.empty(2, dtype=torch.int32, device=dev)
     ok = torch.empty(1, dtype=torch.int32, device=dev)
+    Vb = V if resample is None else int(resample[0])  # the vertices the bones are estimated from
     # the workspace by the header's rule: 3 N V floats for the one work-group, A3D_EB_WIDE_WORKSPACE_WORDS(N, V) words for the wide path
-    work = torch.empty(_lib.eb_wide_workspace_words(B * Fr, V) if estimate_bones_is_wide(B * Fr, V) else 3 * B * Fr * V, dtype=torch.float32,
-                       device=dev)
+    words = _lib.eb_wide_workspace_words(B * Fr, Vb) if estimate_bones_is_wide(B * Fr, Vb) else 3 * B * Fr * Vb
+    if resample is not None:
+        words = max(words, fps_workspace_words(B * Fr, V))
+    work = torch.empty(words, dtype=torch.float32, device=dev)
     a = _lib.EstimateBonesArgs(size=ctypes.sizeof(_lib.EstimateBonesArgs), N=B * Fr, pos=ptr(pos), bones=ptr(bones), nearest=ptr(nearest), ok=ptr(ok), V=V,
                                workspace=ptr(work),
                                n_body=n_body_bones, n_leg=n_leg_bones, body_mode_y_plus=int(bool(body_mode_y_plus)),
@@ -465,7 +525,15 @@ def estimate_bones_device(seq_shape, n_body_bones, n_leg_bones, body_mode_y_plus
         a.blend[i] = v
     for i, v in enumerate(_linspace01(n_leg_bones + 1)):
         a.ramp[i] = v
-    call("a3d_estimate_bones", ctypes.addressof(a), stream())
+    if resample is None:
+        call("a3d_estimate_bones", ctypes.addressof(a), stream())
+    else:
+        k, start = resample
+        require_device(start, what="estimate_bones")
+        start = start.to(torch.int64).contiguous()
+        sampled = torch.empty((B * Fr, Vb, 3), dtype=torch.float32, device=dev)
+        block = pack_fps_block(a, k, False, ptr(start), ptr(sampled), None)
+        call("a3d_estimate_bones", ctypes.addressof(block), stream())
     return bones, nearest, ok
 
 

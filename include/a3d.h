@@ -198,7 +198,26 @@ int a3d_skin_bwd(const float* g_out, const float* v, int v_batch, const float* b
  *   state, A3D_EB_WIDE_WORDS_PER_INSTANCE per instance (six 64-bit arg-extremum keys, the centroid) and A3D_EB_WIDE_WORDS_PER_SLAB per
  *   (instance, slab) (three partial sums in double) -- for small V more than the 3 N V floats of the one-group path.  The call clears
  *   what it needs of it.
- * Either way the call validates before it launches, synchronises nothing and allocates nothing; a null workspace is refused. */
+ * Either way the call validates before it launches, synchronises nothing and allocates nothing; a null workspace is refused.
+ *
+ * The resample tail (estimate_bones(resample=True), reference skinning.py:65-67).  The struct below does not change.  A caller that wants
+ * every cloud reduced to k points by farthest-point sampling first (geometry/util.py:5-27; csrc/fps.hip states the semantics, ties and
+ * NaN included) passes  size = sizeof(a3d_estimate_bones_args) + A3D_FPS_TAIL_SIZE  (or more) and, directly behind the struct, these
+ * A3D_FPS_TAIL_SIZE bytes (csrc/eb_common.h defines them once in C, with their offsets asserted):
+ *   byte  0  int32_t k             points kept per cloud, 1 <= k <= V
+ *   byte  4  int32_t sample_only   non-zero: run the sampler alone (bones, nearest, ok are not touched and may be null)
+ *   byte  8  const int64_t* start  [N] on the device: the first pick of each cloud (clamped into [0, V)); never read on the host
+ *   byte 16  float* sampled        [N, k, 3]: the picked points, in the order picked -- bit copies of pos
+ *   byte 24  int64_t* idx          [N, k]: their indices, or null
+ * One work-group per cloud samples it in ONE launch; unless sample_only, the one-group or wide path above then runs on ``sampled`` with
+ * V = k (N and k decide which, by the rule above; workspace sized for (N, k)).  V <= A3D_FPS_MAX_V, N V <= A3D_EB_WIDE_MAX_POINTS; for
+ * V > A3D_FPS_REG_MAX_V the sampler keeps its N V running distances in ``workspace``, which then holds N V words or what the bones path
+ * needs for (N, k), whichever is more (up to A3D_FPS_REG_MAX_V a sample_only call may pass none).  Refused with A3D_EINVAL before anything
+ * launches: a size between the two sizes, k out of range, a null start or sampled, V over the limit.  size == sizeof(the struct): no
+ * tail, exactly the launches described above. */
+#define A3D_FPS_TAIL_SIZE 32
+#define A3D_FPS_MAX_V 131072
+#define A3D_FPS_REG_MAX_V 16384
 #define A3D_EB_ONE_GROUP_MAX_N 32
 #define A3D_EB_ONE_GROUP_MAX_POINTS 4194304
 #define A3D_EB_WIDE_MAX_POINTS 16777216
