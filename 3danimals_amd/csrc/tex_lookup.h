@@ -58,13 +58,72 @@ __device__ __forceinline__ void cube_dir(int face, float s, float t, float& x, f
 
 __device__ __forceinline__ float comp(const float* v, int i) { return i == 0 ? v[0] : (i == 1 ? v[1] : v[2]); }
 
-__device__ __forceinline__ Lookup make_lookup(const TexK& k, const float* __restrict__ uv, long long i, long long per_image) {
+// Where a lookup's coordinates come from.  GEN = false: the caller's uv in memory.  GEN = true: generated from the element index of an
+// [B, H, W] grid -- the two environment-probe resamplers (include/a3d.h "Texture sampling", generated coordinates; reference
+// model/render/util.py:105-133), every statement rounded once in float32 (the files that include this header build with
+// -ffp-contract=off) with the full-precision sinf / cosf / atan2f / acosf:
+//   2-D texture:  B = 6 faces; uv of (face, y, x) = the lat-long coordinates of normalize(cube_to_dir(face, gx, gy));
+//   cube texture: the direction of (b, y, x) = (sin(theta) sin(phi), cos(theta), -sin(theta) cos(phi)), theta = gy pi, phi = gx pi.
+// lin_at is torch.linspace's two-sided rule; the end points are the reference's Python doubles rounded to float32 once.
+__device__ __forceinline__ float lin_at(float a, float b, int n, int i) {
+    if (n == 1) return a;
+    const float step = (b - a) / (float)(n - 1);
+    return i < n / 2 ? a + step * (float)i : b - step * (float)(n - 1 - i);
+}
+
+template <bool GEN>
+struct UvSrc {
+    const float* __restrict__ uv;  // GEN = false
+    int H, W;                      // GEN = true: the lookup grid
+
+    __device__ __forceinline__ void grid(long long i, int& p, float& gx, float& gy, double y_first) const {
+        const long long per = (long long)H * W, r = i % per;
+        const int y = (int)(r / W), x = (int)(r % W);
+        p = (int)(i / per);
+        const double ry = 1.0 / (double)H, rx = 1.0 / (double)W;
+        gy = lin_at((float)(y_first + ry), (float)(1.0 - ry), H, y);
+        gx = lin_at((float)(-1.0 + rx), (float)(1.0 - rx), W, x);
+    }
+    // the direction of a cube lookup
+    __device__ __forceinline__ void dir(long long i, float* d) const {
+        if constexpr (GEN) {
+            int b;
+            float gx, gy;
+            grid(i, b, gx, gy, 0.0);
+            const float pi = 3.14159265358979323846f;
+            const float theta = gy * pi, phi = gx * pi;
+            const float st = sinf(theta), ct = cosf(theta), sp = sinf(phi), cp = cosf(phi);
+            d[0] = st * sp; d[1] = ct; d[2] = -(st * cp);
+        } else {
+            d[0] = uv[3 * i]; d[1] = uv[3 * i + 1]; d[2] = uv[3 * i + 2];
+        }
+    }
+    // the coordinates of a 2-D lookup
+    __device__ __forceinline__ void uv2(long long i, float& u, float& v) const {
+        if constexpr (GEN) {
+            int face;
+            float gx, gy, d[3];
+            grid(i, face, gx, gy, -1.0);
+            cube_dir(face, gx, gy, d[0], d[1], d[2]);
+            const float len = sqrtf(fmaxf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2], 1e-20f));
+            const float vx = d[0] / len, vy = d[1] / len, vz = d[2] / len;
+            u = atan2f(vx, -vz) / 6.28318530717958647692f + 0.5f;  // (-vz: an exact negation, atan2f(+0, -0) = pi)
+            v = acosf(fminf(fmaxf(vy, -1.f), 1.f)) / 3.14159265358979323846f;
+        } else {
+            u = uv[2 * i]; v = uv[2 * i + 1];
+        }
+    }
+};
+
+template <bool GEN>
+__device__ __forceinline__ Lookup make_lookup(const TexK& k, const UvSrc<GEN>& src, long long i, long long per_image) {
     Lookup L;
     L.valid = true;
     L.b = k.tex_batch == 1 ? 0 : (int)(i / per_image);
     L.face = 0; L.s = L.t = 0.f; L.inv_m = 0.f; L.ia = L.ib = L.im = 0; L.sa = L.sb = L.sm = 1.f;
     if (k.cube) {
-        const float d[3] = {uv[3 * i], uv[3 * i + 1], uv[3 * i + 2]};
+        float d[3];
+        src.dir(i, d);
         cube_face(d[0], d[1], d[2], L.face, L.ia, L.ib, L.im, L.sa, L.sb, L.sm);
         const float m = fabsf(comp(d, L.im));
         if (!(m > 0.f) || !(m < INFINITY)) {  // zero or non-finite direction: output 0, no gradient
@@ -76,6 +135,9 @@ __device__ __forceinline__ Lookup make_lookup(const TexK& k, const float* __rest
         L.t = L.sb * comp(d, L.ib) / m;
     }
     return L;
+}
+__device__ __forceinline__ Lookup make_lookup(const TexK& k, const float* __restrict__ uv, long long i, long long per_image) {
+    return make_lookup(k, UvSrc<false>{uv, 0, 0}, i, per_image);
 }
 
 // texel row of a cube tap (ix, iy) on the lookup's face at size S, after the edge walk; -1 = a corner tap (both coordinates outside)
@@ -125,7 +187,8 @@ struct Quad {
     float w[4], wx[4], wy[4];
 };
 
-__device__ __forceinline__ void level_quad(const TexK& k, const Lookup& L, const float* __restrict__ uv, long long i, int l, bool nearest,
+template <bool GEN>
+__device__ __forceinline__ void level_quad(const TexK& k, const Lookup& L, const UvSrc<GEN>& src, long long i, int l, bool nearest,
                                            Quad& q) {
     const int H = k.h[l], W = k.w[l];
     float x, y;
@@ -133,7 +196,8 @@ __device__ __forceinline__ void level_quad(const TexK& k, const Lookup& L, const
         x = (L.s + 1.f) * 0.5f * (float)W - 0.5f;
         y = (L.t + 1.f) * 0.5f * (float)W - 0.5f;
     } else {
-        const float u = uv[2 * i], v = uv[2 * i + 1];
+        float u, v;
+        src.uv2(i, u, v);
         x = u * (float)W - 0.5f;
         y = v * (float)H - 0.5f;
         if (fabsf(x) > TX_FAR) x = far_coord(u, W, k.boundary, x);
@@ -182,6 +246,11 @@ __device__ __forceinline__ void level_quad(const TexK& k, const Lookup& L, const
         q.row[2] = zero && !(in0 && jn1) ? -1 : (base + y_1) * W + x_0;
         q.row[3] = zero && !(in1 && jn1) ? -1 : (base + y_1) * W + x_1;
     }
+}
+
+__device__ __forceinline__ void level_quad(const TexK& k, const Lookup& L, const float* __restrict__ uv, long long i, int l, bool nearest,
+                                           Quad& q) {
+    level_quad(k, L, UvSrc<false>{uv, 0, 0}, i, l, nearest, q);
 }
 
 // Level of detail and the two level slots.  lw[j] = weight of level lv[j]; dlod[4] = d level / d (J00, J01, J10, J11) (0 when the level is

@@ -11,18 +11,22 @@
 // Mip stack: the box-filter chain is built one level per launch (thread = output element, float4 when C % 4 == 0); its backward walks
 // from the coarsest level down, each fine element reading its one coarse parent (no atomics).
 // The lookup itself (descriptor, cube face rule, quads, level of detail) is tex_lookup.h, shared with envshade.hip.
+// Generated coordinates (uv == NULL): the forward and backward kernels are also instantiated with the coordinates computed from the
+// element index -- the environment-probe resamplers latlong_to_cubemap / cubemap_to_latlong in one launch each way (tex_lookup.h UvSrc).
 #include "a3d_common.h"
 #include "tex_lookup.h"
 #include "tile_scatter.h"
 
 namespace {
 
-template <bool VEC>
-__global__ __launch_bounds__(256) void tex_fwd_kernel(const TexK k, const float* __restrict__ uv, const float* __restrict__ uv_da,
-                                                      const float* __restrict__ bias, long long n, long long per_image,
+// GEN: the coordinates are generated from the element index of the [B, gh, gw] grid instead of read from uv (tex_lookup.h UvSrc)
+template <bool VEC, bool GEN>
+__global__ __launch_bounds__(256) void tex_fwd_kernel(const TexK k, const float* __restrict__ uv_ptr, const float* __restrict__ uv_da,
+                                                      const float* __restrict__ bias, long long n, long long per_image, int gh, int gw,
                                                       float* __restrict__ out) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    const UvSrc<GEN> uv{uv_ptr, gh, gw};
     const int C = k.C;
     float* o = out + i * C;
     const Lookup L = make_lookup(k, uv, i, per_image);
@@ -59,8 +63,8 @@ __global__ __launch_bounds__(256) void tex_fwd_kernel(const TexK k, const float*
 // Backward: a wave = an 8 x 8 block of lookups of one image when W >= 8 (lane bits 0..2 = x, 3..5 = y: ts_merge's partner lanes are
 // neighbours), 64 consecutive lookups otherwise.  Every lane runs every merge (the merge needs the whole wave); lanes without a lookup
 // carry key -1.
-template <bool VEC>
-__global__ __launch_bounds__(256) void tex_bwd_kernel(const TexK k, const float* __restrict__ g_out, const float* __restrict__ uv,
+template <bool VEC, bool GEN>
+__global__ __launch_bounds__(256) void tex_bwd_kernel(const TexK k, const float* __restrict__ g_out, const float* __restrict__ uv_ptr,
                                                       const float* __restrict__ uv_da, const float* __restrict__ bias, int B, int H, int W,
                                                       int tiles_x, int tiles_y, float* __restrict__ g_uv, float* __restrict__ g_uv_da,
                                                       float* __restrict__ g_bias) {
@@ -81,6 +85,7 @@ __global__ __launch_bounds__(256) void tex_bwd_kernel(const TexK k, const float*
     }
     if (!valid) i = 0;
     const int C = k.C;
+    const UvSrc<GEN> uv{uv_ptr, H, W};
     Lookup L = make_lookup(k, uv, i, per_image);
     L.valid = L.valid && valid;
     Lod lod;
@@ -95,7 +100,7 @@ __global__ __launch_bounds__(256) void tex_bwd_kernel(const TexK k, const float*
     const float* g = g_out + i * C;
     // ---- the lookup's own gradients: d out / d x, d y per level slot, and the two levels' difference for d out / d level
     float gx[2] = {0.f, 0.f}, gy[2] = {0.f, 0.f}, gs[2] = {0.f, 0.f};
-    if (L.valid && !nearest) {
+    if (!GEN && L.valid && !nearest) {  // (generated coordinates have no gradient of their own: only the texel scatter below)
         for (int c = 0; c < C; c += 4) {
             const float4 gc = load4<VEC>(g, c, C);
 #pragma unroll
@@ -303,6 +308,23 @@ int tex_halving_ok(const a3d_tex_desc* d, const char* fn) {
     return A3D_OK;
 }
 
+// uv == NULL: the coordinates are generated (include/a3d.h).  Every rule is checked before any launch and named in the message.
+int tex_generated_check(const TexK& k, const void* uv_da, const void* bias, const void* g_uv, const void* g_uv_da, const void* g_bias, int B,
+                        const char* fn) {
+    const char* rule = nullptr;
+    if (uv_da || bias || g_uv_da || g_bias) rule = "uv_da, bias and their gradients must be NULL";
+    else if (g_uv) rule = "g_uv must be NULL";
+    else if (k.filter != A3D_TEX_LINEAR) rule = "filter must be A3D_TEX_LINEAR";
+    else if (k.levels != 1) rule = "only level 0 is read: levels must be 1";
+    else if (k.boundary != A3D_TEX_WRAP && k.boundary != A3D_TEX_CUBE) rule = "boundary must be A3D_TEX_WRAP (lat-long -> cube) or A3D_TEX_CUBE (cube -> lat-long)";
+    else if (!k.cube && k.tex_batch != 1) rule = "a 2-D texture needs tex_batch == 1";
+    else if (!k.cube && B != 6) rule = "a 2-D texture needs B == 6 (the faces of the cube)";
+    else if (k.cube && B != k.tex_batch) rule = "a cube texture needs B == tex_batch";
+    if (!rule) return A3D_OK;
+    a3d_set_error("%s: invalid argument: generated coordinates (uv == NULL): %s", fn, rule);
+    return A3D_EINVAL;
+}
+
 }  // namespace
 
 extern "C" int a3d_texture_fwd(const a3d_tex_desc* desc, const float* uv, const float* uv_da_or_null, const float* bias_or_null, int B, int H,
@@ -310,16 +332,24 @@ extern "C" int a3d_texture_fwd(const a3d_tex_desc* desc, const float* uv, const 
     TexK k;
     const int rc = tex_check(desc, k, __func__);
     if (rc) return rc;
-    A3D_CHECK_ARG(uv && out && B > 0 && H > 0 && W > 0);
+    A3D_CHECK_ARG(out && B > 0 && H > 0 && W > 0);
+    if (!uv) {
+        const int rg = tex_generated_check(k, uv_da_or_null, bias_or_null, nullptr, nullptr, nullptr, B, __func__);
+        if (rg) return rg;
+    }
     A3D_CHECK_ARG(k.tex_batch == 1 || k.tex_batch == B);
     const long long per_image = (long long)H * W, n = per_image * B;
     const bool vec = tex_vec(k) && (uintptr_t)out % 16 == 0;
-    if (vec)
-        hipLaunchKernelGGL(tex_fwd_kernel<true>, dim3(a3d_div_up(n, 256)), dim3(256), 0, (hipStream_t)stream, k, uv, uv_da_or_null, bias_or_null,
-                           n, per_image, out);
-    else
-        hipLaunchKernelGGL(tex_fwd_kernel<false>, dim3(a3d_div_up(n, 256)), dim3(256), 0, (hipStream_t)stream, k, uv, uv_da_or_null, bias_or_null,
-                           n, per_image, out);
+    const dim3 grid(a3d_div_up(n, 256));
+#define TEX_FWD(VEC, GEN)                                                                                                                \
+    hipLaunchKernelGGL((tex_fwd_kernel<VEC, GEN>), grid, dim3(256), 0, (hipStream_t)stream, k, uv, uv_da_or_null, bias_or_null, n, per_image, H, \
+                       W, out)
+    if (uv) {
+        if (vec) TEX_FWD(true, false); else TEX_FWD(false, false);
+    } else {
+        if (vec) TEX_FWD(true, true); else TEX_FWD(false, true);
+    }
+#undef TEX_FWD
     A3D_LAUNCH_CHECK();
     return A3D_OK;
 }
@@ -330,7 +360,11 @@ extern "C" int a3d_texture_bwd(const a3d_tex_desc* desc, const float* g_out, con
     TexK k;
     const int rc = tex_check(desc, k, __func__);
     if (rc) return rc;
-    A3D_CHECK_ARG(g_out && uv && B > 0 && H > 0 && W > 0);
+    A3D_CHECK_ARG(g_out && B > 0 && H > 0 && W > 0);
+    if (!uv) {
+        const int rg = tex_generated_check(k, uv_da_or_null, bias_or_null, g_uv_or_null, g_uv_da_or_null, g_bias_or_null, B, __func__);
+        if (rg) return rg;
+    }
     A3D_CHECK_ARG(k.tex_batch == 1 || k.tex_batch == B);
     A3D_CHECK_ARG(!g_uv_da_or_null || uv_da_or_null);
     A3D_CHECK_ARG(!g_bias_or_null || bias_or_null);
@@ -338,12 +372,16 @@ extern "C" int a3d_texture_bwd(const a3d_tex_desc* desc, const float* g_out, con
     const int tiles_x = a3d_div_up(W, 8), tiles_y = a3d_div_up(H, 8);
     const long long waves = W >= 8 ? (long long)tiles_x * tiles_y * B : (n + 63) / 64;
     const bool vec = tex_vec(k) && (uintptr_t)g_out % 16 == 0;
-    if (vec)
-        hipLaunchKernelGGL(tex_bwd_kernel<true>, dim3(a3d_div_up(waves, 4)), dim3(256), 0, (hipStream_t)stream, k, g_out, uv, uv_da_or_null,
-                           bias_or_null, B, H, W, tiles_x, tiles_y, g_uv_or_null, g_uv_da_or_null, g_bias_or_null);
-    else
-        hipLaunchKernelGGL(tex_bwd_kernel<false>, dim3(a3d_div_up(waves, 4)), dim3(256), 0, (hipStream_t)stream, k, g_out, uv, uv_da_or_null,
-                           bias_or_null, B, H, W, tiles_x, tiles_y, g_uv_or_null, g_uv_da_or_null, g_bias_or_null);
+    const dim3 grid(a3d_div_up(waves, 4));
+#define TEX_BWD(VEC, GEN)                                                                                                                  \
+    hipLaunchKernelGGL((tex_bwd_kernel<VEC, GEN>), grid, dim3(256), 0, (hipStream_t)stream, k, g_out, uv, uv_da_or_null, bias_or_null, B, H, W, \
+                       tiles_x, tiles_y, g_uv_or_null, g_uv_da_or_null, g_bias_or_null)
+    if (uv) {
+        if (vec) TEX_BWD(true, false); else TEX_BWD(false, false);
+    } else {
+        if (vec) TEX_BWD(true, true); else TEX_BWD(false, true);
+    }
+#undef TEX_BWD
     A3D_LAUNCH_CHECK();
     return A3D_OK;
 }

@@ -1,8 +1,9 @@
 """Light sources -- reference model/render/light.py: the directional light of the hot path (:169-193) and the split-sum environment
 light (:27-162), whose prefilters run as HIP kernels (renderutils.diffuse_cubemap / specular_cubemap, csrc/envlight.hip) and whose
 shade() is one HIP launch each way (ops.env_shade, csrc/envshade.hip; its torch statements, with the lookups through ops.texture, stay
-as the specification and as the route of everything the kernel does not take).  load_env / save_env_map stay the reference's (they
-need its image I/O).
+as the specification and as the route of everything the kernel does not take).  load_env / save_env_map (:135-154) read and write
+Radiance .hdr probes through 3danimals_amd.hdrio and resample them with util.latlong_to_cubemap / cubemap_to_latlong, one HIP launch
+each (csrc/texture.hip with generated coordinates).
 """
 import math
 import os
@@ -235,6 +236,30 @@ class EnvironmentLight(torch.nn.Module):
             shaded_col = shaded_col + spec * reflectance
 
         return shaded_col * (1.0 - ks[..., 0:1])  # modulate by hemisphere visibility
+
+
+def _load_env_hdr(fn, scale=1.0, res=512, device=None):
+    """A lat-long .hdr probe -> EnvironmentLight with its mips built (reference light.py:135-142).  ``res``: the cube's face size;
+    ``device``: where the light lives (default: the current CUDA device)."""
+    latlong_img = torch.tensor(util.load_image(fn), dtype=torch.float32, device="cuda" if device is None else device) * scale
+    cubemap = util.latlong_to_cubemap(latlong_img, [res, res])
+
+    l = EnvironmentLight(cubemap)
+    l.build_mips()
+
+    return l
+
+
+def load_env(fn, scale=1.0):
+    if os.path.splitext(fn)[1].lower() == ".hdr":
+        return _load_env_hdr(fn, scale)
+    assert False, "Unknown envlight extension %s" % os.path.splitext(fn)[1]
+
+
+def save_env_map(fn, light):
+    assert isinstance(light, EnvironmentLight), "Can only save EnvironmentLight currently"
+    color = util.cubemap_to_latlong(light.base, [512, 1024])
+    util.save_image_raw(fn, color.detach().cpu().numpy())
 
 
 def create_trainable_env_rnd(base_res, scale=0.5, bias=0.25):

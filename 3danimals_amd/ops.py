@@ -2585,6 +2585,64 @@ def cube_box_down_adjoint(g_coarse):
     return fine[0]
 
 
+# ---------------------------------------------------------------------------------------------- environment probes
+def envmap_device_ok(t):
+    """True when ``t`` can take the generated-coordinate resamplers below: a CUDA float32 tensor."""
+    return torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32
+
+
+def _envmap_res(res, what):
+    if len(res) != 2 or int(res[0]) < 1 or int(res[1]) < 1:
+        raise ValueError(f"{what}: res must be [height, width] with both >= 1, got {res!r}")
+    return int(res[0]), int(res[1])
+
+
+class _EnvResample(torch.autograd.Function):
+    """a3d_texture_fwd / a3d_texture_bwd with uv == NULL (include/a3d.h, generated coordinates): ``tex`` is [1,H,W,C] with boundary
+    wrap (-> the cube [6,h,w,C]) or [1,6,S,S,C] with boundary cube (-> the lat-long map [1,h,w,C]).  One launch each way; the
+    gradient goes to the map only (float atomics after the in-wave merge: its last bits depend on the order)."""
+
+    @staticmethod
+    def forward(ctx, tex, boundary, B, h, w):
+        require_device(tex, what="envmap resample")
+        tex = f32c(tex)
+        C = tex.shape[-1]
+        out = torch.empty((B, h, w, C), dtype=torch.float32, device=tex.device)
+        call("a3d_texture_fwd", ctypes.byref(_tex_desc([tex], C, 1, _TEX_FILTERS["linear"], boundary)), None, None, None, B, h, w, ptr(out), stream(),
+             tag=f"[gen C{C}]")
+        ctx.cfg = (boundary, tuple(tex.shape), B, h, w)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out):
+        boundary, shape, B, h, w = ctx.cfg
+        g_out = f32c(g_out)
+        g_tex = torch.zeros(shape, dtype=torch.float32, device=g_out.device)
+        call("a3d_texture_bwd", ctypes.byref(_tex_desc([g_tex], shape[-1], 1, _TEX_FILTERS["linear"], boundary, [g_tex])), ptr(g_out), None, None,
+             None, B, h, w, None, None, None, stream(), tag=f"[gen C{shape[-1]}]")
+        return g_tex, None, None, None, None
+
+
+def latlong_to_cubemap(latlong, res):
+    """[H,W,C] lat-long map -> [6,res[0],res[1],C] cube, the reference's util.latlong_to_cubemap (model/render/util.py:105-118) in one
+    launch (csrc/texture.hip with generated coordinates; the arithmetic is spelled out in include/a3d.h).  CUDA float32; differentiable
+    in the map."""
+    if not envmap_device_ok(latlong) or latlong.dim() != 3:
+        raise ValueError("latlong_to_cubemap: the map must be a CUDA float32 tensor of shape [H, W, C]")
+    h, w = _envmap_res(res, "latlong_to_cubemap")
+    return _EnvResample.apply(latlong[None], _TEX_BOUNDARIES["wrap"], 6, h, w)
+
+
+def cubemap_to_latlong(cubemap, res):
+    """[6,S,S,C] cube -> [res[0],res[1],C] lat-long map, the reference's util.cubemap_to_latlong (model/render/util.py:120-133) in one
+    launch.  CUDA float32; differentiable in the cube."""
+    if not envmap_device_ok(cubemap) or cubemap.dim() != 4 or cubemap.shape[0] != 6 or cubemap.shape[1] != cubemap.shape[2]:
+        raise ValueError("cubemap_to_latlong: the map must be a CUDA float32 tensor of shape [6, S, S, C]")
+    h, w = _envmap_res(res, "cubemap_to_latlong")
+    return _EnvResample.apply(cubemap[None], _TEX_BOUNDARIES["cube"], 1, h, w)[0]
+
+
 # ---------------------------------------------------------------------------------------------- environment light
 ENV_MAX_RES = 4096  # ENV_MAX_N of csrc/envlight.hip
 ENV_MAX_DIFFUSE_RES = 256  # ENV_MAX_DIFFUSE_N: the diffuse filter is all pairs, 36 N^4 (the light runs it at 16)

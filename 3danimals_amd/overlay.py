@@ -5,10 +5,11 @@ Each replaced reference module keeps its own source and gets ONE line appended a
     from importlib import import_module as _im; _im("3danimals_amd.overlay").apply(globals(), "model.render.util")
 
 ``apply`` puts the public names of the mirror module (``3danimals_amd.model...``) on top of the reference module's own: functions
-and classes this package implements replace the reference's, everything it does not implement (``util.save_image``,
-``light.load_env``, ``obj.load_obj``, the texture helpers ...) stays the reference's -- the reference's remaining
-``texture.py`` / ``material.py`` / light-loading code keeps working.  Names the mirror only defines as stand-alone placeholders
-(``_STANDALONE_ONLY`` in the mirror module) are never exported.
+and classes this package implements replace the reference's (``light.load_env`` / ``save_env_map`` and the probe resamplers
+``util.latlong_to_cubemap`` / ``cubemap_to_latlong`` among them), everything it does not implement (``obj.load_obj``, the texture
+helpers ...) stays the reference's -- the reference's remaining ``texture.py`` / ``material.py`` code keeps working.  Names the
+mirror only defines for stand-alone use (``_STANDALONE_ONLY`` in the mirror module: placeholders, and ``util``'s ``imageio``-free
+``load_image`` / ``save_image`` family, which must not take the reference's versions away from its own callers) are never exported.
 """
 from importlib import import_module
 

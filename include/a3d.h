@@ -816,6 +816,22 @@ int a3d_flow_delta_bwd(const float* g_delta, int g_stride /* floats between two 
  *   a3d_texture_mip_fwd : levels 1 .. levels-1 from level 0, each a 2 x 2 (2 x 1, 1 x 2) box mean of the one before (written).
  *   a3d_texture_mip_bwd : grad[levels-1] .. grad[1] pushed down the box filter into grad[levels-2] .. grad[0] (accumulated, in place).
  * Level sizes must follow the halving rule for the mip entry points: a dimension > 1 is even and halves, a dimension of 1 stays.
+ * Generated coordinates (the environment-probe resamplers, reference model/render/util.py:105-133): uv == NULL in a3d_texture_fwd /
+ * a3d_texture_bwd means the lookups of the [B,H,W] grid are computed from the element index instead of read.  It requires uv_da, bias,
+ * g_uv, g_uv_da and g_bias NULL, filter == A3D_TEX_LINEAR and levels == 1 (only level 0 is read); anything else is A3D_EINVAL before
+ * any launch, with the rule in a3d_last_error().  lin(a, b, n)[i] below is torch.linspace's two-sided rule in float32: step =
+ * (b - a) / (n - 1), a + step i for i < n / 2, else b - step (n - 1 - i), a for n == 1; its end points (-1 + 1/n ...) are evaluated in
+ * double and rounded to float32 once, as the reference's Python does.  Every other statement rounds once in float32, without
+ * contraction, with sinf / cosf / atan2f / acosf (not the fast intrinsics).
+ *   boundary == A3D_TEX_WRAP (needs tex_batch == 1, B == 6): out[6,H,W,C] = latlong_to_cubemap(level 0, [H,W]).  Face s, row y, column
+ *     x: gy = lin(-1 + 1/H, 1 - 1/H, H)[y], gx = lin(-1 + 1/W, 1 - 1/W, W)[x], d = cube_to_dir(s, gx, gy), v = d / sqrt(max(d.d, 1e-20)),
+ *     tu = atan2f(v.x, -v.z) / float(2 pi) + 0.5 (-v.z an exact negation: atan2f(+0, -0) = pi), tv = acosf(clamp(v.y, -1, 1)) / float(pi),
+ *     then the bilinear wrap tap at (tu, tv).
+ *   boundary == A3D_TEX_CUBE (needs B == tex_batch): out[B,H,W,C] = cubemap_to_latlong(level 0 of image b, [H,W]).  gy = lin(1/H,
+ *     1 - 1/H, H)[y], gx = lin(-1 + 1/W, 1 - 1/W, W)[x], theta = gy float(pi), phi = gx float(pi), direction (sin(theta) sin(phi),
+ *     cos(theta), -sin(theta) cos(phi)), then the seamless linear cube lookup.
+ *   a3d_texture_bwd with uv == NULL regenerates the coordinates and accumulates grad[0] through the same wave-merged texel scatter
+ *   (the caller zeroes it).
  */
 #define A3D_TEX_MAX_LEVELS 16
 #define A3D_TEX_NEAREST 0
