@@ -300,6 +300,19 @@ SURFACES = (
 SIGNATURES = {name: sig for s in SURFACES for name, sig in s.signatures.items()}  # every entry point of the library: what lib() binds
 assert len(SIGNATURES) == sum(len(s.signatures) for s in SURFACES), "an entry point is registered in two surfaces"
 
+# Internal entry points (csrc/fieldgrad.h): the SDF input-gradient route of hostnets.USE_FIELD_GRAD.  Bound by lib() like the public ones,
+# no part of the public surface: no header under include/ declares them, SURFACES / SIGNATURES and a3d_version() do not change.
+FIELD_GRAD_SIGNATURES = {
+    "a3d_gemm_nt_relumask": (_c_int, [_p, _p, _p, ctypes.c_int64, _c_int, _c_int, _p, _p]),
+    "a3d_harmonic_embed_jvp": (_c_int, [_p, _p, _p, _c_int, _c_int, _c_int, ctypes.c_int64, _p, _p]),
+    "a3d_field_grad_head_fwd": (_c_int, [_p, _p, _p, ctypes.c_int64, _p, _p]),
+    "a3d_field_grad_head_scratch_bytes": (_c_size_t, [ctypes.c_int64]),
+    "a3d_field_grad_head_bwd": (_c_int, [_p, _p, _p, ctypes.c_int64, _p, _p, _p, _p]),
+    "a3d_gemm_tn_splitk_scratch_bytes": (_c_size_t, [ctypes.c_int64, _c_int, _c_int]),
+    "a3d_gemm_tn_splitk": (_c_int, [_p, _p, ctypes.c_int64, _c_int, _c_int, _p, _p, _p]),
+}
+assert not set(FIELD_GRAD_SIGNATURES) & set(SIGNATURES)
+
 ABI_VERSION = 405  # a3d_version() of the library these signatures belong to (include/a3d.h)
 _lib = None
 
@@ -318,7 +331,7 @@ def lib():
                 "(or __graft_entry__.build()).  There is no CPU fallback for the HIP hot path."
             )
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(FIELD_GRAD_SIGNATURES.items()):
             fn = getattr(handle, name)  # AttributeError here == ABI drift
             fn.restype, fn.argtypes = res, args
         if handle.a3d_version() != ABI_VERSION:  # same symbols, other argument lists: a stale build must not be called
@@ -385,9 +398,17 @@ def set_guard(level):
     return prev
 
 
+def _capturing():
+    """The current stream is being captured into a HIP graph (the eikonal regulariser's chains call entry points under capture since
+    DESIGN.md section 35): the debugging aids below must not synchronise, and they have nothing to look at before the graph is replayed."""
+    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+
+
 def guarded_empty(shape, dtype, device, zero=False, site=""):
     dtype = dtype or torch.get_default_dtype()
     shape = tuple(int(v) for v in shape)
+    if _capturing():  # a captured launch does not run now: there is no canary to compare after it, and a replay passes through no call()
+        return torch.zeros(shape, dtype=dtype, device=device) if zero else torch.empty(shape, dtype=dtype, device=device)
     n = 1
     for v in shape:
         n *= v
@@ -500,6 +521,9 @@ _TRACE_FILE = open(os.environ["A3D_TRACE_CALLS"], "w") if os.environ.get("A3D_TR
 def call(name: str, *args, tag: str = ""):
     """Invoke an int-returning entry point and raise on a non-zero status (``tag`` only labels KernelTimer records)."""
     timer = KernelTimer.active
+    aids = (GUARD or _SYNC_EVERY_CALL or timer is not None) and not _capturing()  # (the product path: one flag test per call)
+    if not aids:
+        timer = None
     if _TRACE_FILE is not None:
         _TRACE_FILE.write(f"{name}{tag} {args}\n")
         _TRACE_FILE.flush()
@@ -508,9 +532,9 @@ def call(name: str, *args, tag: str = ""):
         a.record()
     rc = getattr(lib(), name)(*args)
     del _HELD[:]
-    if GUARD and rc == 0:
+    if GUARD and rc == 0 and aids:
         guard_check(name + tag)
-    if _SYNC_EVERY_CALL:  # debugging aid (A3D_SYNC_CALLS=1): a device fault is reported at the entry point that caused it
+    if _SYNC_EVERY_CALL and aids:  # debugging aid (A3D_SYNC_CALLS=1): a device fault is reported at the entry point that caused it
         try:
             torch.cuda.synchronize()
         except Exception as e:

@@ -5,7 +5,9 @@
 // gradient GEMM.  The reference runs abs / cat / mul / sin / cos / cat / cat (7 launches over [P, <=63]) forward and ~10 backward.
 //   fwd: one thread per output element (coalesced stores; x rows come from L1/L2)
 //   bwd: one thread per (point, coordinate): g_x = g[x part] + sum_k f_k (g_sin cos(x f_k) - g_cos sin(x f_k)), recomputing sin/cos
+//   jvp: d_emb = J_e(x) lam for a tangent lam [P,3] (what the SDF regulariser's second-order pass feeds forward), threads as in fwd
 #include "a3d_common.h"
+#include "fieldgrad.h"
 
 namespace {
 
@@ -58,7 +60,48 @@ __global__ __launch_bounds__(256) void he_bwd_kernel(const float* __restrict__ g
     g_x[i] = acc;
 }
 
+// the tangent of the forward: d_emb = J_e(x) lam, one thread per (point, slot) like he_fwd_kernel.  d|x_0|/dx_0 is 0 at +-0 (he_bwd_kernel,
+// torch.abs) and the ones column is a constant: its tangent is 0.
+__global__ __launch_bounds__(256) void he_jvp_kernel(const float* __restrict__ x, const float* __restrict__ lam, const float* __restrict__ freq,
+                                                     int n, int symmetrize, int ones, long long total, int C, float* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int slots = 3 * n + 3 + ones;
+    const long long p = i / slots;
+    const int q = (int)(i - p * slots);
+    float* o = out + p * C;
+    if (q == 3 * n + 3) {
+        o[C - 1] = 0.f;
+        return;
+    }
+    const int c = q < 3 * n ? q / n : q - 3 * n;
+    const float raw = x[3 * p + c];
+    float l = lam[3 * p + c];
+    if (symmetrize && c == 0) l *= raw > 0.f ? 1.f : (raw < 0.f ? -1.f : 0.f);
+    if (q < 3 * n) {
+        const float f = freq[q - c * n];
+        float sn, cs;
+        sincosf(((symmetrize && c == 0) ? fabsf(raw) : raw) * f, &sn, &cs);
+        o[3 + q] = l * (f * cs);
+        o[3 + 3 * n + q] = -(l * (f * sn));
+    } else {
+        o[c] = l;
+    }
+}
+
 }  // namespace
+
+extern "C" int a3d_harmonic_embed_jvp(const float* x, const float* lam, const float* freq, int n, int symmetrize, int ones, int64_t P,
+                                      float* d_emb, a3d_stream_t stream) {
+    A3D_CHECK_ARG(P >= 0 && n > 0 && (ones == 0 || ones == 1));
+    if (P == 0) return A3D_OK;
+    A3D_CHECK_ARG(x && lam && freq && d_emb);
+    const long long total = (long long)P * (3 * n + 3 + ones);
+    hipLaunchKernelGGL(he_jvp_kernel, dim3(a3d_div_up(total, 256)), dim3(256), 0, (hipStream_t)stream, x, lam, freq, n, symmetrize, ones, total,
+                       3 + 6 * n + ones, d_emb);
+    A3D_LAUNCH_CHECK();
+    return A3D_OK;
+}
 
 extern "C" int a3d_harmonic_embed_fwd(const float* x, const float* freq, int n, int symmetrize, int ones, int64_t P, float* out,
                                       a3d_stream_t stream) {

@@ -15,6 +15,7 @@
 // A wave accumulates g_W over its 8 tiles, the 4 waves of a work-group are added through LDS in wave order and the work-group's
 // [C,256] goes to scratch; fh_reduce_kernel adds the work-groups' partial sums in ascending order.  No atomics.
 #include "../../include/a3d_fields.h"
+#include "fieldgrad.h"
 #include "a3d_common.h"
 
 namespace {
@@ -242,6 +243,46 @@ __global__ __launch_bounds__(16 * FH_RED_SEGS) void fh_reduce_kernel(const float
     }
 }
 
+// ---- the head of the field's INPUT gradient (the SDF regulariser differentiates a Linear(256 -> 1) head with respect to the points) ----
+// forward  b[m,k] = (s[m] w[k]) * (y[m,k] > 0): where the gradient chain of a scalar field starts; one thread per float4 of b.
+__global__ __launch_bounds__(256) void fg_head_fwd_kernel(const float* __restrict__ s, const float* __restrict__ w, const float* __restrict__ y,
+                                                          long long M, float* __restrict__ b) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;  // float4 index
+    if (i >= M * (FH_K / 4)) return;
+    const long long m = i / (FH_K / 4);
+    const int k4 = (int)(i - m * (FH_K / 4));
+    const float sv = s[m];
+    const f32x4 wv = fh_load4(w + 4 * k4), yv = fh_load4(y + 4 * i);
+    f32x4 d;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) d[r] = yv[r] > 0.f ? sv * wv[r] : 0.f;  // strictly positive: a denormal passes, -0.0 and a NaN do not
+    *reinterpret_cast<f32x4*>(b + 4 * i) = d;
+}
+
+// adjoint  g_w[k] = sum_m s[m] t[m,k] and (g_s != NULL) g_s[m] = sum_k t[m,k] w[k].  A work-group takes FG_ROWS rows: thread k adds its
+// column over them in ascending order and leaves the sum in partial[work-group][k] (fh_reduce_kernel adds those, in order); for g_s wave v
+// takes the rows v, v + 4, ..: a lane multiplies its float4 of the row, the wave adds by butterfly -- the same tree on every run.
+constexpr int FG_ROWS = 64;
+
+__global__ __launch_bounds__(FH_K) void fg_head_bwd_kernel(const float* __restrict__ s, const float* __restrict__ t, const float* __restrict__ w,
+                                                           long long M, float* __restrict__ partial, float* __restrict__ g_s) {
+    const int k = threadIdx.x;
+    const long long m0 = (long long)blockIdx.x * FG_ROWS;
+    const int rows = (int)(M - m0 < FG_ROWS ? M - m0 : FG_ROWS);
+    float acc = 0.f;
+    for (int r = 0; r < rows; ++r) acc += s[m0 + r] * t[(m0 + r) * FH_K + k];
+    partial[(size_t)blockIdx.x * FH_K + k] = acc;
+    if (g_s != nullptr) {
+        const int lane = k & 63, wave = k >> 6;
+        const f32x4 wv = fh_load4(w + 4 * lane);
+        for (int r = wave; r < rows; r += FH_K / 64) {
+            const f32x4 tv = fh_load4(t + (m0 + r) * FH_K + 4 * lane);
+            const float v = a3d_wave_sum((tv[0] * wv[0] + tv[1] * wv[1]) + (tv[2] * wv[2] + tv[3] * wv[3]));
+            if (lane == 0) g_s[m0 + r] = v;
+        }
+    }
+}
+
 inline bool fh_sizes_ok(int64_t M, int C) { return M >= 1 && M < (1ll << 31) && C >= 1 && C <= A3D_FIELD_HEAD_MAX_C; }
 inline int fh_work_groups(int64_t M) { return (int)((M + A3D_FIELD_HEAD_WG_ROWS - 1) / A3D_FIELD_HEAD_WG_ROWS); }
 inline bool fh_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
@@ -286,6 +327,32 @@ extern "C" int a3d_field_head_bwd(const float* g_out, const float* s, const floa
     }
     A3D_LAUNCH_CHECK();
     hipLaunchKernelGGL(fh_reduce_kernel, dim3(C * FH_K / 16), dim3(16 * FH_RED_SEGS), 0, st, partial, n_wg, C * FH_K, g_W);
+    A3D_LAUNCH_CHECK();
+    return A3D_OK;
+}
+
+extern "C" size_t a3d_field_grad_head_scratch_bytes(int64_t M) {
+    if (M < 1 || M >= (1ll << 31)) return 0;
+    return (size_t)((M + FG_ROWS - 1) / FG_ROWS) * FH_K * sizeof(float);
+}
+
+extern "C" int a3d_field_grad_head_fwd(const float* s, const float* w, const float* y, int64_t M, float* b, a3d_stream_t stream) {
+    A3D_CHECK_ARG(M >= 1 && M < (1ll << 31));
+    A3D_CHECK_ARG(s && w && y && b && fh_aligned16(w) && fh_aligned16(y) && fh_aligned16(b));
+    hipLaunchKernelGGL(fg_head_fwd_kernel, dim3(a3d_div_up(M * (FH_K / 4), 256)), dim3(256), 0, (hipStream_t)stream, s, w, y, (long long)M, b);
+    A3D_LAUNCH_CHECK();
+    return A3D_OK;
+}
+
+extern "C" int a3d_field_grad_head_bwd(const float* s, const float* t, const float* w, int64_t M, void* scratch, float* g_w, float* g_s,
+                                       a3d_stream_t stream) {
+    A3D_CHECK_ARG(M >= 1 && M < (1ll << 31));
+    A3D_CHECK_ARG(s && t && w && scratch && g_w && fh_aligned16(t) && fh_aligned16(w));
+    const int n_wg = (int)((M + FG_ROWS - 1) / FG_ROWS);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(fg_head_bwd_kernel, dim3(n_wg), dim3(FH_K), 0, st, s, t, w, (long long)M, (float*)scratch, g_s);
+    A3D_LAUNCH_CHECK();
+    hipLaunchKernelGGL(fh_reduce_kernel, dim3(FH_K / 16), dim3(16 * FH_RED_SEGS), 0, st, (const float*)scratch, n_wg, FH_K, g_w);
     A3D_LAUNCH_CHECK();
     return A3D_OK;
 }

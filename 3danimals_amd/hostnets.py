@@ -16,8 +16,9 @@ DESIGN.md "What is not a HIP kernel"): split-K weight gradients (``_LinearSplitK
 (``_LinearReLUSplitK``), the per-image feature as a [B,C] GEMM plus a per-point add folded into the ReLU pass
 (``CoordMLP._forward_indexed``), the input stage [x, sin, cos, 1] from one HIP kernel with the first bias as a weight column
 (``CoordMLP._fused_input``), the output stage Linear(256 -> C <= 16) [+ sigmoid] [+ min_max] and its adjoint as one HIP pass over the
-hidden vectors each way (``_FieldStackHead``, csrc/fieldhead.hip), and the frequency table kept on the device.  Short lists (the SDF regulariser, which needs double
-backward) take the plain torch path.
+hidden vectors each way (``_FieldStackHead``, csrc/fieldhead.hip), and the frequency table kept on the device.  Short lists take the plain
+torch path, except the one that needs double backward: points that require grad through the 256-wide SDF field (the eikonal regulariser)
+take hand-written value / gradient / adjoint chains (``_field_value``, ``USE_FIELD_GRAD``).
 """
 from __future__ import annotations
 
@@ -243,6 +244,141 @@ class _FieldStackHead(torch.autograd.Function):
         return (g_x, g_in, g_rows, None, g_first, g_head, None, None, None, *g_hidden)
 
 
+USE_FIELD_GRAD = True  # a short point list that REQUIRES GRAD through a scalar 256-wide field: value, input gradient and the adjoint of
+# that gradient as the hand-written chains below (_FieldValue / _FieldInputGrad) instead of autograd's general double backward
+
+
+def _tn_products(p, q):
+    """[p_i^T q_i] for stacks p [n,M,256] and q [n,M,C]: the weight gradients of a short list.  Every product has a tiny output and an
+    M-long reduction; all layers go through one split-K launch of csrc/gemm.hip and one that adds the partial products in a fixed order."""
+    from . import ops
+
+    return ops.gemm_tn_splitk(p, q)
+
+
+def _field_grad_chain(s, y, w_head, hidden):
+    """b_0 .. b_L [L + 1, M, 256]: b_L = (s w_h) * (y_L > 0), b_(l-1) = (b_l W_l) * (y_(l-1) > 0)."""
+    from . import ops
+
+    n_hidden = len(hidden)
+    b = torch.empty_like(y)
+    ops.field_grad_head_fwd(s, w_head, y[n_hidden], out=b[n_hidden])
+    for l in range(n_hidden, 0, -1):
+        ops.gemm_nn_relumask(b[l], hidden[l - 1], y[l - 1], out=b[l - 1])
+    return b
+
+
+class _FieldInputGrad(torch.autograd.Function):
+    """The gradient pass of _FieldValue as a node of its own, so that it can be differentiated in turn (the eikonal regulariser:
+    autograd.grad(sdf, points, create_graph=True), a loss on the result, backward to the weights).  With D_l = (y_l > 0):
+
+        forward    b_L = (s w_h) * D_L,  b_(l-1) = (b_l W_l) * D_(l-1),  g_x = J_e(x)^T (b_0 W_in)
+        backward   given lam = d/d g_x:  dv = J_e(x) lam,  t_0 = (dv W_in^T) * D_0,  t_l = (t_(l-1) W_l^T) * D_l,
+                   dW_in = b_0^T dv,  dW_l = b_l^T t_(l-1),  dw_h = sum_m s[m] t_L[m,:],  ds = t_L w_h^T
+
+    A ReLU stack is piecewise linear: the masks are constants of the point, so the backward is a second forward pass with frozen masks
+    plus one weight-gradient product per layer -- no second derivative of any layer.  The points enter detached: the second-order
+    gradient with respect to x (the embedding's Hessian) is not provided, autograd.grad for it raises "not used in the graph", and a
+    plain backward() leaves it out."""
+
+    @staticmethod
+    def forward(ctx, s, x, y, w_in, w_head, freq, symmetrize, *hidden):
+        from . import ops
+
+        b = _field_grad_chain(s, y, w_head, hidden)
+        ctx.save_for_backward(s, x, y, w_in, w_head, freq, b, *hidden)
+        ctx.symmetrize = symmetrize
+        return ops.harmonic_embed_bwd_raw(b[0].mm(w_in), x, freq, symmetrize, True)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, lam):
+        from . import ops
+
+        s, x, y, w_in, w_head, freq, b = ctx.saved_tensors[:7]
+        hidden = ctx.saved_tensors[7:]
+        n_hidden = len(hidden)
+        need = ctx.needs_input_grad  # (s, x, y, w_in, w_head, freq, symmetrize, *hidden)
+        dv = ops.harmonic_embed_jvp(x, lam, freq, ctx.symmetrize, True)
+        t = torch.empty_like(y)  # t_0 .. t_L
+        ops.gemm_nt_relumask(dv, w_in, y[0], out=t[0])
+        for l in range(1, n_hidden + 1):
+            ops.gemm_nt_relumask(t[l - 1], hidden[l - 1], y[l], out=t[l])
+        g_in = _tn_products(b[:1], dv[None])[0] if need[3] else None
+        g_head, g_s = ops.field_grad_head_bwd(s, t[n_hidden], w_head, need_s=need[0]) if (need[4] or need[0]) else (None, None)
+        g_hidden = [None] * n_hidden
+        if any(need[7:]):
+            prods = _tn_products(b[1:], t[:-1])
+            g_hidden = [prods[l] if need[7 + l] else None for l in range(n_hidden)]
+        return (g_s, None, None, g_in, g_head if need[4] else None, None, None, *g_hidden)
+
+
+class _FieldWeightTap(torch.autograd.Function):
+    """Where _FieldValue's FIRST-ORDER weight gradients are computed: dW_in = b_0^T e, dW_l = b_l^T y_(l-1), dw_h = s^T y_L.
+
+    A Function's backward cannot know which of its input gradients the engine wants, and the regulariser asks for d sdf / d points alone:
+    six products per call would be computed and thrown away.  So the weights reach _FieldValue through this node: its forward returns an
+    [M,1] buffer that nobody reads (no launch), _FieldValue hands the buffer's "gradient" s on unchanged, and the engine runs this backward
+    only when a weight gradient is wanted -- never under autograd.grad(sdf, points).  ``box`` is filled by _FieldValue.forward with the
+    embedding and the activations.  First-order only."""
+
+    @staticmethod
+    def forward(ctx, box, m, w_in, w_head, *hidden):
+        ctx.box = box
+        ctx.save_for_backward(w_head, *hidden)
+        return torch.empty((m, 1), dtype=w_in.dtype, device=w_in.device)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, s):
+        e, y = ctx.box["e"], ctx.box["y"]
+        w_head, hidden = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        need = ctx.needs_input_grad  # (box, m, w_in, w_head, *hidden)
+        b = _field_grad_chain(s, y, w_head, hidden)
+        g_in = _tn_products(b[:1], e[None])[0] if need[2] else None
+        g_head = s.reshape(1, -1).mm(y[-1]) if need[3] else None
+        g_hidden = [None] * len(hidden)
+        if any(need[4:]):
+            prods = _tn_products(b[1:], y[:-1])
+            g_hidden = [prods[l] if need[4 + l] else None for l in range(len(hidden))]
+        return (None, None, g_in, g_head, *g_hidden)
+
+
+class _FieldValue(torch.autograd.Function):
+    """A scalar coordinate field over a short point list that requires grad, out = y_L w_h^T with y_0 = relu(embed(x) W_in^T) (the
+    in_layer's bias folded in as the ones column) and y_l = relu(y_(l-1) W_l^T): the library GEMMs of _stack_forward, written into one
+    [L + 1, M, 256] buffer, and a backward that is itself a differentiable node (_FieldInputGrad; no once_differentiable here).  The
+    weights' own first-order gradients go through ``tap`` (_FieldWeightTap); use :func:`_field_value`."""
+
+    @staticmethod
+    def forward(ctx, x, tap, box, w_in, w_head, freq, symmetrize, *hidden):
+        from . import ops
+
+        e = ops.harmonic_embed_raw(x, freq, symmetrize, True)
+        y = torch.empty((len(hidden) + 1, x.shape[0], 256), dtype=torch.float32, device=x.device)
+        zero = _zero_bias(e, w_in)
+        torch._addmm_activation(zero, e, w_in.t(), use_gelu=False, out=y[0])
+        for l, w in enumerate(hidden):
+            torch._addmm_activation(zero, y[l], w.t(), use_gelu=False, out=y[l + 1])
+        box.update(e=e, y=y)
+        ctx.save_for_backward(x, y, w_in, w_head, freq, *hidden)
+        ctx.symmetrize = bool(symmetrize)
+        return y[-1].mm(w_head.t())
+
+    @staticmethod
+    def backward(ctx, s):
+        x, y, w_in, w_head, freq = ctx.saved_tensors[:5]
+        hidden = ctx.saved_tensors[5:]
+        g_x = _FieldInputGrad.apply(s, x.detach(), y, w_in, w_head, freq, ctx.symmetrize, *hidden) if ctx.needs_input_grad[0] else None
+        return (g_x, s if ctx.needs_input_grad[1] else None, None, None, None, None, None, *([None] * len(hidden)))
+
+
+def _field_value(x, w_in, w_head, freq, symmetrize, *hidden):
+    box = {}
+    tap = _FieldWeightTap.apply(box, x.shape[0], w_in, w_head, *hidden)
+    return _FieldValue.apply(x, tap, box, w_in, w_head, freq, symmetrize, *hidden)
+
+
 def _long_list(x, weight):
     return (x.is_cuda and x.dim() == 2 and x.shape[0] >= SPLITK_MIN_ROWS and x.shape[0] % SPLITK_PARTS == 0 and x.is_contiguous()
             and x.dtype == torch.float32 and torch.is_grad_enabled() and weight.requires_grad)
@@ -357,6 +493,8 @@ class CoordMLP(nn.Module):
             feat = feat[feat_index]
         if feat is None and self._stack_ok(x, False):
             return self._stacked(x, None, None)
+        if feat is None and self._field_grad_ok(x):
+            return self._field_grad(x)
         if feat is None and self._fused_input_ok(x):
             out = self.mlp(self._fused_input(x))
             if self.min_max is not None:
@@ -418,6 +556,33 @@ class CoordMLP(nn.Module):
         h = ops.harmonic_embed(x, self.embedder._frequencies(x.device), symmetrize=self.symmetrize, ones=True)
         weight = torch.cat([self.in_layer.weight, self.in_layer.bias[:, None]], dim=1)
         return linear_relu(h, weight, None)
+
+    def _field_grad_ok(self, x):
+        """A short list of points that REQUIRE GRAD through a scalar field of the standard shape (the SDF under the eikonal regulariser):
+        embedding + concatenated points (an even number of frequencies: K = 4 + 6n is then a multiple of 4), a biased in_layer of 256
+        outputs, bias-free 256 x 256 Linear/ReLU pairs, one bias-free Linear(256 -> 1); nothing else behind it.  Everything else -- the
+        grad-free grid pass, points that do not require grad, narrow nets, features -- keeps its path."""
+        if not (USE_FIELD_GRAD and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == 3 and 1 <= x.shape[0] < SPLITK_MIN_ROWS
+                and x.requires_grad and torch.is_grad_enabled() and self.embedder is not None and self.embed_concat_pts
+                and len(self.embedder.frequencies) % 2 == 0 and self.in_layer.bias is not None and self.in_layer.weight.shape[0] == 256
+                and self.in_layer.weight.dtype == torch.float32 and self.min_max is None and self.extra_feat_dim == 0):
+            return False
+        layers = list(self.mlp.network)
+        if len(layers) < 3 or len(layers) % 2 == 0:
+            return False
+        for i, layer in enumerate(layers[:-1]):
+            if i % 2 == 1 and not isinstance(layer, nn.ReLU):
+                return False
+            if i % 2 == 0 and not (isinstance(layer, nn.Linear) and layer.bias is None and tuple(layer.weight.shape) == (256, 256)):
+                return False
+        head = layers[-1]
+        return isinstance(head, nn.Linear) and head.bias is None and tuple(head.weight.shape) == (1, 256) and head.weight.dtype == torch.float32
+
+    def _field_grad(self, x):
+        w_in = torch.cat([self.in_layer.weight, self.in_layer.bias[:, None]], dim=1)
+        layers = list(self.mlp.network)
+        return _field_value(x, w_in, layers[-1].weight, self.embedder._frequencies(x.device), bool(self.symmetrize),
+                            *[l.weight for l in layers[:-1:2]])
 
     def _stack_ok(self, x, with_feat):
         """The whole hidden stack as one autograd node (_FieldStack): long list, training, 256-wide bias-free Linear/ReLU pairs."""

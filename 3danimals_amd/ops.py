@@ -2288,9 +2288,33 @@ class _HarmonicEmbed(torch.autograd.Function):
         return g_x, None, None, None
 
 
+def harmonic_embed_raw(x, freq, symmetrize, ones):
+    """harmonic_embed without an autograd node (inside hostnets' Functions)."""
+    return _HarmonicEmbed.forward(_NoCtx(), x, freq, symmetrize, ones)
+
+
+def harmonic_embed_bwd_raw(g, x, freq, symmetrize, ones):
+    """g [P, 3 + 6n (+1)] -> J_e(x)^T g [P,3]: harmonic_embed's adjoint as a plain call (inside hostnets' Functions)."""
+    require_device(g, x, freq, what="harmonic_embed_bwd")
+    x, freq = f32c(x), f32c(freq)
+    if tuple(g.shape) != (x.shape[0], 3 + 6 * freq.shape[0] + int(ones)):
+        raise ValueError(f"harmonic_embed_bwd: g must be [{x.shape[0]},{3 + 6 * freq.shape[0] + int(ones)}], got {list(g.shape)}")
+    g_x = torch.empty_like(x)
+    call("a3d_harmonic_embed_bwd", ptr(f32h(g)), ptr(x), ptr(freq), freq.shape[0], int(symmetrize), int(ones), x.shape[0], ptr(g_x), stream())
+    return g_x
+
+
+class _NoCtx:
+    """Stands in for the autograd context where a Function's forward is called as a plain function."""
+
+    def save_for_backward(self, *tensors):
+        pass
+
+
 def harmonic_embed(x, freq, symmetrize=False, ones=False):
     """[P,3] -> [P, 3 + 6n (+1)] = [x (|x_0| if symmetrize), sin(x_c f_k), cos(x_c f_k), (1)] (csrc/embed.hip).  First-order
-    differentiable only (double backward raises): the SDF regulariser, which differentiates the field twice, takes the torch path."""
+    differentiable only (double backward raises): the SDF regulariser, which differentiates the field twice, calls the kernels as plain
+    functions (harmonic_embed_raw, harmonic_embed_bwd_raw, harmonic_embed_jvp) from hostnets' own Functions, or takes the torch path."""
     if x.dim() != 2 or x.shape[1] != 3 or freq.dim() != 1 or freq.shape[0] < 1:
         raise ValueError(f"harmonic_embed: expected x [P,3] and n >= 1 frequencies [n], got {list(x.shape)} and {list(freq.shape)}")
     if not (x.is_floating_point() and freq.is_floating_point()):
@@ -2299,7 +2323,16 @@ def harmonic_embed(x, freq, symmetrize=False, ones=False):
 
 
 # ---------------------------------------------------------------------------------------------- fp32 MFMA GEMM + ReLU adjoint
-def gemm_nn_relumask(a, b, x=None):
+def _rows256_out(what, out, m, device):
+    """The [M,256] float32 result buffer: a fresh one, or the caller's ``out`` (a layer's slice of a stacked buffer)."""
+    if out is None:
+        return torch.empty((m, 256), dtype=torch.float32, device=device)
+    if tuple(out.shape) != (m, 256) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != device:
+        raise ValueError(f"{what}: out must be float32, contiguous and [{m},256] on {device}, got {out.dtype} {list(out.shape)} on {out.device}")
+    return out
+
+
+def gemm_nn_relumask(a, b, x=None, out=None):
     """(a [M,K] @ b [K,256]) * (x [M,256] > 0)  (x None: plain product) -- csrc/gemm.hip, fp32 MFMA.  No autograd: it is the
     input-gradient GEMM inside hostnets' stack backward.  The mask is read in place: float32, contiguous, and only for K >= 256."""
     if a.dim() != 2 or b.dim() != 2 or a.shape[1] < 32 or a.shape[1] % 32 or tuple(b.shape) != (a.shape[1], 256):
@@ -2310,9 +2343,85 @@ def gemm_nn_relumask(a, b, x=None):
     require_device(a, b, x, what="gemm_nn_relumask")
     a, b = f32c(a), f32c(b)
     M, K = a.shape
-    c = torch.empty((M, 256), dtype=torch.float32, device=a.device)
+    c = _rows256_out("gemm_nn_relumask", out, M, a.device)
     call("a3d_gemm_nn_relumask", ptr(a), ptr(b), ptr(x), M, 256, K, ptr(c), stream())
     return c
+
+
+def gemm_nt_relumask(a, w, x=None, out=None):
+    """(a [M,K] @ w [256,K]^T) * (x [M,256] > 0)  (x None: plain product) -- csrc/gemm.hip, fp32 MFMA on 64 x 128 tiles, made for short
+    point lists.  ``w`` is a Linear's [out,in] weight as stored; K a multiple of 4.  No autograd: it is the forward product with a foreign
+    (frozen) ReLU mask inside hostnets' field-gradient adjoint."""
+    if a.dim() != 2 or w.dim() != 2 or a.shape[1] < 4 or a.shape[1] % 4 or tuple(w.shape) != (256, a.shape[1]):
+        raise ValueError(f"gemm_nt_relumask: expected a [M,K] and w [256,K] with K a positive multiple of 4, got {list(a.shape)} and {list(w.shape)}")
+    if x is not None and (tuple(x.shape) != (a.shape[0], 256) or x.dtype != torch.float32 or not x.is_contiguous()):
+        raise ValueError(f"gemm_nt_relumask: the mask must be float32, contiguous and [M,256] = [{a.shape[0]},256]; got {x.dtype} {list(x.shape)} "
+                         f"with strides {list(x.stride())}")
+    require_device(a, w, x, what="gemm_nt_relumask")
+    a, w = f32c(a), f32c(w)
+    M, K = a.shape
+    c = _rows256_out("gemm_nt_relumask", out, M, a.device)
+    call("a3d_gemm_nt_relumask", ptr(a), ptr(w), ptr(x), M, 256, K, ptr(c), stream(), tag=f"[K{K}]")
+    return c
+
+
+def gemm_tn_splitk(p, q):
+    """[p_b^T @ q_b] [B,256,C] for p [B,M,256] and q [B,M,C] (C a multiple of 4, at most 256): the weight gradients of a short point list,
+    all layers in one call -- csrc/gemm.hip, fp32 MFMA, split-K over the rows with the partial products added in a fixed order.  No autograd."""
+    if p.dim() != 3 or q.dim() != 3 or p.shape[2] != 256 or tuple(q.shape[:2]) != tuple(p.shape[:2]) or not 4 <= q.shape[2] <= 256 or q.shape[2] % 4 \
+            or not 1 <= p.shape[0] <= 64 or p.shape[1] < 1:
+        raise ValueError(f"gemm_tn_splitk: expected p [B,M,256] and q [B,M,C] with 1 <= B <= 64, M >= 1 and C a multiple of 4 up to 256, got "
+                         f"{list(p.shape)} and {list(q.shape)}")
+    require_device(p, q, what="gemm_tn_splitk")
+    p, q = f32c(p), f32c(q)
+    B, M, C = q.shape
+    scratch = torch.empty(_lib.lib().a3d_gemm_tn_splitk_scratch_bytes(M, C, B), dtype=torch.uint8, device=p.device)
+    out = torch.empty((B, 256, C), dtype=torch.float32, device=p.device)
+    call("a3d_gemm_tn_splitk", ptr(p), ptr(q), M, C, B, ptr(scratch), ptr(out), stream(), tag=f"[n{B}x{C}]")
+    return out
+
+
+def harmonic_embed_jvp(x, lam, freq, symmetrize=False, ones=False):
+    """J_e(x) lam [P, 3 + 6n (+1)]: the tangent of :func:`harmonic_embed` along ``lam`` [P,3] (csrc/embed.hip).  No autograd."""
+    if x.dim() != 2 or x.shape[1] != 3 or tuple(lam.shape) != tuple(x.shape) or freq.dim() != 1 or freq.shape[0] < 1:
+        raise ValueError(f"harmonic_embed_jvp: expected x and lam [P,3] and n >= 1 frequencies [n], got {list(x.shape)}, {list(lam.shape)} and "
+                         f"{list(freq.shape)}")
+    require_device(x, lam, freq, what="harmonic_embed_jvp")
+    x, lam, freq = f32c(x), f32c(lam), f32c(freq)
+    P, n = x.shape[0], freq.shape[0]
+    out = torch.empty((P, 3 + 6 * n + int(ones)), dtype=torch.float32, device=x.device)
+    call("a3d_harmonic_embed_jvp", ptr(x), ptr(lam), ptr(freq), n, int(symmetrize), int(ones), P, ptr(out), stream())
+    return out
+
+
+def _field_grad_head_args(what, s, w, y):
+    if y.dim() != 2 or y.shape[1] != _lib.FIELD_HEAD_WIDTH or y.shape[0] < 1 or s.numel() != y.shape[0] or w.numel() != _lib.FIELD_HEAD_WIDTH:
+        raise ValueError(f"{what}: expected s [M] or [M,1], w [256] or [1,256] and [M,256] hidden vectors with M >= 1, got {list(s.shape)}, "
+                         f"{list(w.shape)} and {list(y.shape)}")
+    return int(y.shape[0])
+
+
+def field_grad_head_fwd(s, w, y, out=None):
+    """b [M,256] = (s[m] w[k]) * (y[m,k] > 0): the start of a scalar field's input-gradient chain (csrc/fieldhead.hip).  No autograd."""
+    M = _field_grad_head_args("field_grad_head_fwd", s, w, y)
+    require_device(s, w, y, what="field_grad_head_fwd")
+    s, w, y = f32c(s), f32c(w), f32c(y)
+    b = _rows256_out("field_grad_head_fwd", out, M, y.device)
+    call("a3d_field_grad_head_fwd", ptr(s), ptr(w), ptr(y), M, ptr(b), stream())
+    return b
+
+
+def field_grad_head_bwd(s, t, w, need_s=False):
+    """(g_w [1,256] = sum_m s[m] t[m,:], g_s [M,1] = t @ w^T or None) -- the adjoint of :func:`field_grad_head_fwd` behind the frozen mask;
+    per-work-group partial sums added in a fixed order (no atomics, the same bits on every run).  No autograd."""
+    M = _field_grad_head_args("field_grad_head_bwd", s, w, t)
+    require_device(s, t, w, what="field_grad_head_bwd")
+    s, t, w = f32c(s), f32c(t), f32c(w)
+    scratch = torch.empty(_lib.lib().a3d_field_grad_head_scratch_bytes(M), dtype=torch.uint8, device=t.device)
+    g_w = torch.empty((1, _lib.FIELD_HEAD_WIDTH), dtype=torch.float32, device=t.device)
+    g_s = torch.empty((M, 1), dtype=torch.float32, device=t.device) if need_s else None
+    call("a3d_field_grad_head_bwd", ptr(s), ptr(t), ptr(w), M, ptr(scratch), ptr(g_w), ptr(g_s), stream())
+    return g_w, g_s
 
 
 def _field_head_args(what, h, weight, scale, act):
