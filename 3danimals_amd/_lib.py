@@ -313,6 +313,23 @@ FIELD_GRAD_SIGNATURES = {
 }
 assert not set(FIELD_GRAD_SIGNATURES) & set(SIGNATURES)
 
+# Internal entry points (csrc/articulation.h): the per-bone descriptors and the angle limits of articulation.py.  As above: bound by
+# lib(), flat arguments, no part of the public surface.
+ARTICULATION_CHUNK = 32  # feature columns per work-group of the descriptor kernels (A3D_ARTICULATION_CHUNK)
+ARTICULATION_MAX_BONES = 64
+ARTICULATION_MAX_SIDE = 4096
+ARTICULATION_MAX_ANGLES = 1 << 20
+ARTICULATION_MAX_IMAGES = 65535
+_i64 = ctypes.c_int64
+ARTICULATION_SIGNATURES = {
+    "a3d_bone_inputs_fwd": (_c_int, [_p, _c_int, _p, _p, _c_float, _c_float, _p, _p, _i64, _i64, _i64, _i64, _c_int, _c_int, _c_int, _c_int,
+                                     _c_int, _c_int, _p, _p, _p]),
+    "a3d_bone_inputs_bwd": (_c_int, [_p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _i64, _i64, _i64, _i64, _p]),
+    "a3d_constrain_angles_fwd": (_c_int, [_p, _p, _c_float, _c_int, _c_int, _p, _p, _p]),
+    "a3d_constrain_angles_bwd": (_c_int, [_p, _p, _p, _p, _c_float, _c_int, _c_int, _p, _p]),
+}
+assert not set(ARTICULATION_SIGNATURES) & (set(SIGNATURES) | set(FIELD_GRAD_SIGNATURES))
+
 ABI_VERSION = 405  # a3d_version() of the library these signatures belong to (include/a3d.h)
 _lib = None
 
@@ -331,7 +348,7 @@ def lib():
                 "(or __graft_entry__.build()).  There is no CPU fallback for the HIP hot path."
             )
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(FIELD_GRAD_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(FIELD_GRAD_SIGNATURES.items()) + list(ARTICULATION_SIGNATURES.items()):
             fn = getattr(handle, name)  # AttributeError here == ABI drift
             fn.restype, fn.argtypes = res, args
         if handle.a3d_version() != ABI_VERSION:  # same symbols, other argument lists: a stale build must not be called

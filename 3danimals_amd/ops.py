@@ -3731,6 +3731,155 @@ def nearest_visible_vertex(uv, visibility, keypoints):
     return idx.long()
 
 
+# ---------------------------------------------------------------------------------------------- articulation glue (csrc/articulation.h)
+def _dense_strides(t):
+    """The strides of ``t`` when its elements are dense in some order and do not overlap (NCHW, a permuted NHWC view, ...), else None."""
+    dims = sorted((d for d in range(t.dim()) if t.shape[d] > 1), key=t.stride)
+    expect = 1
+    for d in dims:
+        if t.stride(d) != expect:
+            return None
+        expect *= t.shape[d]
+    return tuple(max(int(s), 1) if t.shape[d] > 1 else expect for d, s in enumerate(t.stride()))
+
+
+def _bone_inputs_launch(bones, mvp, w2c, feat, patch_feat, z_offset, spatial_scale):
+    N, K = int(mvp.shape[0]), int(bones.shape[1])
+    D = 0 if feat is None else int(feat.shape[1])
+    C, h, w = (0, 1, 1) if patch_feat is None else (int(v) for v in patch_feat.shape[1:])
+    bones, mvp, w2c = f32c(bones), f32c(mvp), f32c(w2c)
+    feat = None if feat is None else f32c(feat)
+    if patch_feat is not None and patch_feat.dtype != torch.float32:
+        patch_feat = patch_feat.float()  # (keeps the strides of a dense tensor; never a .contiguous() copy of a float32 one)
+    strides =(0, 0, 0, 0) if patch_feat is None else tuple(int(s) for s in patch_feat.stride())
+    pos_in = torch.empty((N, K, 9), dtype=torch.float32, device=mvp.device)
+    bones_feat = torch.empty((N, K, D + C), dtype=torch.float32, device=mvp.device) if D + C else None
+    call("a3d_bone_inputs_fwd", ptr(bones), int(bones.shape[0] == 1 and N != 1), ptr(mvp), ptr(w2c), float(z_offset), float(spatial_scale), ptr(feat),
+         ptr(patch_feat), *strides, N, K, D, C, h, w, ptr(bones_feat), ptr(pos_in), stream())
+    return bones_feat, pos_in
+
+
+class _BoneInputs(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, bones, mvp, w2c, feat, patch_feat, z_offset, spatial_scale):
+        bones_feat, pos_in = _bone_inputs_launch(bones, mvp, w2c, feat, patch_feat, z_offset, spatial_scale)
+        ctx.mark_non_differentiable(pos_in)
+        ctx.save_for_backward(pos_in)
+        ctx.D = 0 if feat is None else int(feat.shape[1])
+        ctx.patch = None if patch_feat is None else (tuple(patch_feat.shape), _dense_strides(patch_feat))
+        return bones_feat, pos_in
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out, _g_pos):
+        (pos_in,) = ctx.saved_tensors
+        N, K, D = int(pos_in.shape[0]), int(pos_in.shape[1]), ctx.D
+        want_feat = D > 0 and ctx.needs_input_grad[3]
+        want_patch = ctx.patch is not None and ctx.needs_input_grad[4]
+        if not (want_feat or want_patch):
+            return (None,) * 7
+        C, h, w = (0, 1, 1) if ctx.patch is None else ctx.patch[0][1:]
+        g_feat = torch.empty((N, D), dtype=torch.float32, device=pos_in.device) if want_feat else None
+        g_patch, gs = None, (0, 0, 0, 0)
+        if want_patch:  # every element is written by the kernel: no zero-fill here
+            shape, strides = ctx.patch
+            g_patch = (torch.empty(shape, dtype=torch.float32, device=pos_in.device) if strides is None else
+                       torch.empty_strided(shape, strides, dtype=torch.float32, device=pos_in.device))
+            gs = tuple(max(int(s), 1) for s in g_patch.stride())
+        call("a3d_bone_inputs_bwd", ptr(f32h(g_out)), ptr(pos_in), N, K, D, C, h, w, ptr(g_feat), ptr(g_patch), *gs, stream())
+        return None, None, None, g_feat, g_patch, None, None
+
+
+class _ConstrainAngles(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, S, multiplier, want_reg):
+        x = f32c(x)
+        N, K = int(x.shape[0]), int(x.shape[1])
+        angles = torch.empty_like(x)
+        reg = torch.empty((), dtype=torch.float32, device=x.device) if want_reg else None
+        call("a3d_constrain_angles_fwd", ptr(x), ptr(S), float(multiplier), N, K, ptr(angles), ptr(reg), stream())
+        ctx.save_for_backward(x, S)
+        ctx.multiplier = float(multiplier)
+        ctx.set_materialize_grads(False)
+        return (angles, reg) if want_reg else angles
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_angles, g_reg=None):
+        x, S = ctx.saved_tensors
+        if g_angles is None and g_reg is None:
+            return None, None, None, None
+        g_x = torch.empty_like(x)
+        call("a3d_constrain_angles_bwd", None if g_angles is None else ptr(f32h(g_angles)), None if g_reg is None else ptr(f32h(g_reg)), ptr(x), ptr(S),
+             ctx.multiplier, int(x.shape[0]), int(x.shape[1]), ptr(g_x), stream())
+        return g_x, None, None, None
+
+
+def _float_tensor(t, dims, last, what):
+    if not torch.is_tensor(t) or not t.is_floating_point() or t.dim() != dims or tuple(t.shape[dims - len(last):]) != tuple(last):
+        raise ValueError(f"{what}, got {getattr(t, 'dtype', type(t))} {list(getattr(t, 'shape', []))}")
+
+
+def bone_inputs_limits_ok(N, K, D, C, h, w):
+    """Whether the descriptor kernels take these sizes (csrc/articulation.h)."""
+    return (1 <= K <= _lib.ARTICULATION_MAX_BONES and 0 <= N <= _lib.ARTICULATION_MAX_IMAGES and
+            (C == 0 or (1 <= h <= _lib.ARTICULATION_MAX_SIDE and 1 <= w <= _lib.ARTICULATION_MAX_SIDE)) and
+            max(N * K * (D + C), N * K * 9, N * C * h * w) < 1 << 31)
+
+
+def bone_inputs(bones, mvp, w2c, cam_pos_z_offset, spatial_scale, feat=None, patch_feat=None):
+    """The per-bone descriptors of the articulation network (reference InstancePredictorBase.py:337-382): bones [N,K,2,3] or [1,K,2,3]
+    (shared by the images), mvp and w2c [N,4,4], feat [N,D] or None, patch_feat [N,C,h,w] of any strides or None, all on the current
+    device -> (bones_feat [N,K,D+C] or None when neither is given, bones_pos_in [N,K,9]).  One launch forward, one backward
+    (csrc/articulation.hip), no memset, no atomics, the same bits on every run.  Gradients reach feat and patch_feat only;
+    bones_pos_in never requires grad.  The gradient of patch_feat has its strides when it is dense in some order, else it is contiguous.
+    A midpoint whose projected coordinate is not finite samples 0 and scatters nothing; a finite coordinate of any size is classified
+    inside or outside the image in floating point.  Limits: 1 <= K <= 64, 1 <= h, w <= 4096, N <= 65535, every count below 2^31."""
+    _float_tensor(bones, 4, (2, 3), "bone_inputs: expected float bones [N,K,2,3] or [1,K,2,3]")
+    _float_tensor(mvp, 3, (4, 4), "bone_inputs: expected a float mvp [N,4,4]")
+    _float_tensor(w2c, 3, (4, 4), "bone_inputs: expected a float w2c [N,4,4]")
+    N, K = int(mvp.shape[0]), int(bones.shape[1])
+    if w2c.shape[0] != N or bones.shape[0] not in (1, N):
+        raise ValueError(f"bone_inputs: bones {list(bones.shape)}, mvp {list(mvp.shape)} and w2c {list(w2c.shape)} do not belong together")
+    if feat is not None:
+        _float_tensor(feat, 2, (), "bone_inputs: expected a float feat [N,D]")
+    if patch_feat is not None:
+        _float_tensor(patch_feat, 4, (), "bone_inputs: expected a float patch_feat [N,C,h,w]")
+    if (feat is not None and feat.shape[0] != N) or (patch_feat is not None and patch_feat.shape[0] != N):
+        raise ValueError(f"bone_inputs: feat / patch_feat do not have the {N} images of mvp")
+    D = 0 if feat is None else int(feat.shape[1])
+    C, h, w = (0, 1, 1) if patch_feat is None else (int(v) for v in patch_feat.shape[1:])
+    if (feat is not None and D < 1) or (patch_feat is not None and min(C, h, w) < 1) or N < 1 or not bone_inputs_limits_ok(N, K, D, C, h, w):
+        raise ValueError(f"bone_inputs: N = {N}, K = {K}, D = {D}, patch_feat [{C},{h},{w}] is outside 1 <= K <= {_lib.ARTICULATION_MAX_BONES}, "
+                         f"1 <= h, w <= {_lib.ARTICULATION_MAX_SIDE}, 1 <= N <= {_lib.ARTICULATION_MAX_IMAGES}, every count below 2^31")
+    if not (math.isfinite(float(cam_pos_z_offset)) and math.isfinite(float(spatial_scale)) and float(spatial_scale) != 0.0):
+        raise ValueError(f"bone_inputs: cam_pos_z_offset {cam_pos_z_offset} / spatial_scale {spatial_scale} must be finite, the scale not 0")
+    require_device(bones, mvp, w2c, feat, patch_feat, what="bone_inputs")
+    bones, mvp, w2c = bones.detach(), mvp.detach(), w2c.detach()
+    if D + C == 0:
+        with torch.no_grad():
+            return _bone_inputs_launch(bones.float(), mvp.float(), w2c.float(), None, None, cam_pos_z_offset, spatial_scale)
+    return _BoneInputs.apply(bones, mvp, w2c, feat, patch_feat, float(cam_pos_z_offset), float(spatial_scale))
+
+
+def constrain_angles(x, scale, multiplier, return_reg=False):
+    """angles = scale[k,c] * tanh(multiplier * x) for x [N,K,3] and a float32 table scale [K,3], both on the current device, and with
+    ``return_reg`` also reg = mean(angles^2) (a 0-dim float32 tensor: the reference's arti_reg_loss), differentiable through the same
+    backward kernel.  One launch forward, one backward (csrc/articulation.hip: one work-group, double sums in a fixed order, the same
+    bits on every run).  The backward recomputes tanh from x, so a zero of ``scale`` gives exactly 0 out and exactly 0 gradient, also
+    at x = +-inf.  Limits: 1 <= K <= 64, N * K * 3 <= 2^20."""
+    _float_tensor(x, 3, (3,), "constrain_angles: expected a float x [N,K,3]")
+    N, K = int(x.shape[0]), int(x.shape[1])
+    if not torch.is_tensor(scale) or scale.dtype != torch.float32 or tuple(scale.shape) != (K, 3):
+        raise ValueError(f"constrain_angles: expected a float32 scale [{K},3], got {getattr(scale, 'dtype', type(scale))} {list(getattr(scale, 'shape', []))}")
+    if N < 1 or not 1 <= K <= _lib.ARTICULATION_MAX_BONES or N * K * 3 > _lib.ARTICULATION_MAX_ANGLES:
+        raise ValueError(f"constrain_angles: x {list(x.shape)} is outside N >= 1, 1 <= K <= {_lib.ARTICULATION_MAX_BONES}, N * K * 3 <= 2^20")
+    if not math.isfinite(float(multiplier)):
+        raise ValueError(f"constrain_angles: multiplier {multiplier} is not finite")
+    require_device(x, scale, what="constrain_angles")
+    return _ConstrainAngles.apply(x, scale.detach().contiguous(), float(multiplier), bool(return_reg))
+
+
 # ---------------------------------------------------------------------------------------------- mixed precision
 def _amp_wrap_functions():
     """Every autograd.Function of this module runs its forward with autocast OFF on float32 copies of half-precision inputs, and its
