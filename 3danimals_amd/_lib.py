@@ -330,6 +330,20 @@ ARTICULATION_SIGNATURES = {
 }
 assert not set(ARTICULATION_SIGNATURES) & (set(SIGNATURES) | set(FIELD_GRAD_SIGNATURES))
 
+# Internal entry points (csrc/pose.h): the pose heads, the hypothesis pick with its look-at rotation, the cameras of a pose and Fauna's
+# random-view cameras of pose.py.  As above: bound by lib(), flat arguments, no part of the public surface.  ``proj`` is a host pointer.
+POSE_MAX_HYPOS = 8
+POSE_MAX_IMAGES = 65535
+_pose_common = [_p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_float, _c_float, _c_float, _i64, _c_float, _p]
+POSE_SIGNATURES = {
+    "a3d_pose_cameras_fwd": (_c_int, _pose_common + [_p] * 12),
+    "a3d_pose_cameras_bwd": (_c_int, _pose_common + [_p] * 11),
+    "a3d_cameras_from_pose_fwd": (_c_int, [_p, _c_int, _c_float, _p, _p, _p, _p, _p]),
+    "a3d_cameras_from_pose_bwd": (_c_int, [_p, _c_int, _c_float, _p, _p, _p, _p, _p, _p]),
+    "a3d_random_view_cameras": (_c_int, [_p, _p, _c_int, _c_float, _p, _p, _p, _p, _p]),
+}
+assert not set(POSE_SIGNATURES) & (set(SIGNATURES) | set(FIELD_GRAD_SIGNATURES) | set(ARTICULATION_SIGNATURES))
+
 ABI_VERSION = 405  # a3d_version() of the library these signatures belong to (include/a3d.h)
 _lib = None
 
@@ -348,7 +362,8 @@ def lib():
                 "(or __graft_entry__.build()).  There is no CPU fallback for the HIP hot path."
             )
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(FIELD_GRAD_SIGNATURES.items()) + list(ARTICULATION_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(FIELD_GRAD_SIGNATURES.items()) + list(ARTICULATION_SIGNATURES.items()) \
+                + list(POSE_SIGNATURES.items()):
             fn = getattr(handle, name)  # AttributeError here == ABI drift
             fn.restype, fn.argtypes = res, args
         if handle.a3d_version() != ABI_VERSION:  # same symbols, other argument lists: a stale build must not be called

@@ -52,6 +52,7 @@ SOURCES = {
     "fieldhead.hip": ["-ffp-contract=off"],
     "keypoints.hip": ["-ffp-contract=off"],
     "articulation.hip": ["-ffp-contract=off"],
+    "pose.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wall",
           "-Wno-unused-function"]

@@ -3880,6 +3880,169 @@ def constrain_angles(x, scale, multiplier, return_reg=False):
     return _ConstrainAngles.apply(x, scale.detach().contiguous(), float(multiplier), bool(return_reg))
 
 
+# ---------------------------------------------------------------------------------------------- camera-pose glue (csrc/pose.h)
+_POSE_TABLES = OrderedDict()  # (the values of a small host table, device) -> its float32 copy on that device
+
+
+def pose_table(t, device):
+    """orthant_signs / max_trans_xyz_range as a contiguous float32 tensor on ``device``: a tensor that is already there is taken as it
+    is; a host table is copied once per distinct content and kept (these are a model's constants)."""
+    if t.device == device:
+        return f32c(t.detach())
+    host = f32c(t.detach().cpu())
+    key = (host.numpy().tobytes(), tuple(host.shape), str(device))
+    if key not in _POSE_TABLES:
+        if len(_POSE_TABLES) >= 32:
+            _POSE_TABLES.popitem(last=False)
+        _POSE_TABLES[key] = host.to(device)
+    return _POSE_TABLES[key]
+
+
+_POSE_PROJ = {}
+
+
+def _proj_host(proj16):
+    """The 16 floats of a projection as the host array the pose entry points read during the call (kept: a model has one or two)."""
+    if proj16 not in _POSE_PROJ:
+        if len(_POSE_PROJ) >= 32:
+            _POSE_PROJ.clear()
+        _POSE_PROJ[proj16] = (ctypes.c_float * 16)(*proj16)
+    return _POSE_PROJ[proj16]
+
+
+class _PoseCameras(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, raw, signs, trans, rand_perm, best_perm, oct, zeroy, temp, naive_weight, best_below, offset_z, proj16):
+        raw = f32c(raw)
+        N, W = int(raw.shape[0]), int(raw.shape[1])
+        H = (W - 3) // 4
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=raw.device)
+        poses_raw, pose_raw, pose, mvp, w2c, campos = new(N, W), new(N, 6), new(N, 12), new(N, 4, 4), new(N, 4, 4), new(N, 3)
+        rot_prob, rot_logit, rots_probs = new(N), new(N), new(N, H)
+        rot_idx = torch.empty((N,), dtype=torch.int64, device=raw.device)
+        rand_flag = torch.empty((N,), dtype=torch.int64, device=raw.device)
+        common = (ptr(raw), ptr(signs), ptr(trans), ptr(rand_perm), ptr(best_perm), N, H, int(oct), int(zeroy), float(temp), float(naive_weight),
+                  float(1 - naive_weight), int(best_below), float(offset_z), _proj_host(proj16))
+        call("a3d_pose_cameras_fwd", *common, ptr(poses_raw), ptr(pose_raw), ptr(pose), ptr(mvp), ptr(w2c), ptr(campos), ptr(rot_idx),
+             ptr(rot_prob), ptr(rot_logit), ptr(rots_probs), ptr(rand_flag), stream())
+        ctx.save_for_backward(raw, signs, trans, rand_perm, best_perm)
+        ctx.common = common[5:]
+        ctx.mark_non_differentiable(rot_idx, rand_flag)
+        ctx.set_materialize_grads(False)
+        return poses_raw, pose_raw, pose, mvp, w2c, campos, rot_idx, rot_prob, rot_logit, rots_probs, rand_flag
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_poses_raw, g_pose_raw, g_pose, g_mvp, g_w2c, g_campos, _g_idx, g_rot_prob, g_rot_logit, g_rots_probs, _g_flag):
+        grads = (g_poses_raw, g_pose_raw, g_pose, g_mvp, g_w2c, g_campos, g_rot_prob, g_rot_logit, g_rots_probs)
+        if not ctx.needs_input_grad[0] or all(g is None for g in grads):
+            return (None,) * 12
+        raw, signs, trans, rand_perm, best_perm = ctx.saved_tensors
+        g_raw = torch.empty_like(raw)
+        call("a3d_pose_cameras_bwd", ptr(raw), ptr(signs), ptr(trans), ptr(rand_perm), ptr(best_perm), *ctx.common,
+             *(None if g is None else ptr(f32h(g)) for g in grads), ptr(g_raw), stream())
+        return (g_raw,) + (None,) * 11
+
+
+class _CamerasFromPose(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pose, offset_z, proj16):
+        pose = f32c(pose)
+        N = int(pose.shape[0])
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=pose.device)
+        mvp, w2c, campos = new(N, 4, 4), new(N, 4, 4), new(N, 3)
+        call("a3d_cameras_from_pose_fwd", ptr(pose), N, float(offset_z), _proj_host(proj16), ptr(mvp), ptr(w2c), ptr(campos), stream())
+        ctx.save_for_backward(pose)
+        ctx.consts = (float(offset_z), proj16)
+        ctx.set_materialize_grads(False)
+        return mvp, w2c, campos
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_mvp, g_w2c, g_campos):
+        if g_mvp is None and g_w2c is None and g_campos is None:
+            return None, None, None
+        (pose,) = ctx.saved_tensors
+        g_pose = torch.empty_like(pose)
+        call("a3d_cameras_from_pose_bwd", ptr(pose), int(pose.shape[0]), ctx.consts[0], _proj_host(ctx.consts[1]),
+             *(None if g is None else ptr(f32h(g)) for g in (g_mvp, g_w2c, g_campos)), ptr(g_pose), stream())
+        return g_pose, None, None
+
+
+def _pose_proj(proj16, who):
+    proj16 = tuple(float(v) for v in proj16)
+    if len(proj16) != 16 or not all(math.isfinite(v) for v in proj16):
+        raise ValueError(f"{who}: expected the 16 finite numbers of a row-major projection")
+    return proj16
+
+
+def predict_cameras(raw, orthant_signs, max_trans, rand_perm, best_perm, oct, zeroy, temp, naive_weight, best_below, offset_z, proj16):
+    """Heads, pick and cameras of the pose path in one launch (reference InstancePredictorBase.py:257-304, 623-663, 606-620): raw
+    [N,4H+3], orthant_signs [H,3] and max_trans [3] float32, rand_perm / best_perm [N] int64 or both None, all on the current device;
+    temp, naive_weight in [0,1], best_below (image n keeps its best hypothesis where best_perm[n] < best_below), offset_z (added to the
+    translation's z) and the 16 numbers of the projection on the host -> (poses_raw, pose_raw, pose, mvp, w2c, campos, rot_idx,
+    rot_prob, rot_logit, rots_probs, rand_pose_flag).  One launch backward (csrc/pose.hip), which takes the gradients of all nine float
+    outputs and returns the gradient of raw; no memset, no atomics, the same bits on every run.  Limits: 1 <= H <= 8, 1 <= N <= 65535."""
+    _float_tensor(raw, 2, (), "predict_cameras: expected a float raw [N,4H+3]")
+    N, W = int(raw.shape[0]), int(raw.shape[1])
+    H = (W - 3) // 4
+    if W != 4 * H + 3 or not 1 <= H <= _lib.POSE_MAX_HYPOS or not 1 <= N <= _lib.POSE_MAX_IMAGES:
+        raise ValueError(f"predict_cameras: raw {list(raw.shape)} is outside [N,4H+3] with 1 <= H <= {_lib.POSE_MAX_HYPOS}, 1 <= N <= {_lib.POSE_MAX_IMAGES}")
+    for t, shape, name in ((orthant_signs, (H, 3), "orthant_signs"), (max_trans, (3,), "max_trans")):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"predict_cameras: expected a contiguous float32 {name} {list(shape)}, got {getattr(t, 'dtype', type(t))} {list(getattr(t, 'shape', []))}")
+    if (rand_perm is None) != (best_perm is None):
+        raise ValueError("predict_cameras: rand_perm and best_perm are given together or not at all")
+    for t, name in ((rand_perm, "rand_perm"), (best_perm, "best_perm")):
+        if t is not None and (not torch.is_tensor(t) or t.dtype != torch.int64 or tuple(t.shape) != (N,)):
+            raise ValueError(f"predict_cameras: expected an int64 {name} [{N}], got {getattr(t, 'dtype', type(t))} {list(getattr(t, 'shape', []))}")
+    if not (math.isfinite(float(temp)) and float(temp) > 0 and 0.0 <= float(naive_weight) <= 1.0 and math.isfinite(float(offset_z))) \
+            or not 0 <= int(best_below) <= N:
+        raise ValueError(f"predict_cameras: temp {temp}, naive_weight {naive_weight}, best_below {best_below}, offset_z {offset_z}: expected "
+                         f"temp > 0, 0 <= naive_weight <= 1, 0 <= best_below <= {N}, a finite offset")
+    proj16 = _pose_proj(proj16, "predict_cameras")
+    require_device(raw, orthant_signs, max_trans, rand_perm, best_perm, what="predict_cameras")
+    if rand_perm is not None:
+        rand_perm, best_perm = rand_perm.contiguous(), best_perm.contiguous()
+    return _PoseCameras.apply(raw, orthant_signs.detach(), max_trans.detach(), rand_perm, best_perm, bool(oct), bool(zeroy), float(temp),
+                              float(naive_weight), int(best_below), float(offset_z), proj16)
+
+
+def cameras_from_pose(pose, offset_z, proj16):
+    """pose [N,12] (a row-major 3x3 R, then t) on the current device -> (mvp, w2c [N,4,4], campos [N,3]): w2c = [[R^T, t + (0, 0,
+    offset_z)], [0,0,0,1]], mvp = proj @ w2c, campos = -R (t + (0, 0, offset_z)) (reference InstancePredictorBase.py:606-620).  One
+    launch forward, one backward (csrc/pose.hip); the gradient goes to pose.  Limit: 1 <= N <= 65535."""
+    _float_tensor(pose, 2, (12,), "cameras_from_pose: expected a float pose [N,12]")
+    if not 1 <= int(pose.shape[0]) <= _lib.POSE_MAX_IMAGES or not math.isfinite(float(offset_z)):
+        raise ValueError(f"cameras_from_pose: pose {list(pose.shape)} / offset_z {offset_z} is outside 1 <= N <= {_lib.POSE_MAX_IMAGES}, a finite offset")
+    proj16 = _pose_proj(proj16, "cameras_from_pose")
+    require_device(pose, what="cameras_from_pose")
+    return _CamerasFromPose.apply(pose, float(offset_z), proj16)
+
+
+def random_view_cameras(w2c_pred, rand_degree, delta_angle, proj16):
+    """Fauna's random-view cameras (reference Fauna.py:112-142) for the first b = len(rand_degree) images of w2c_pred [>= b,4,4] on the
+    current device; rand_degree an integer tensor on any device (copied over without a synchronisation when it is on the host), the
+    float32 delta_angle = 2 pi / bins and the projection on the host -> (mvp, w2c [b,4,4], campos [b,3]), none requiring grad.  One
+    launch (csrc/pose.hip).  Limit: 1 <= b <= 65535."""
+    _float_tensor(w2c_pred, 3, (4, 4), "random_view_cameras: expected a float w2c_pred [N,4,4]")
+    if not torch.is_tensor(rand_degree) or rand_degree.is_floating_point() or rand_degree.dim() != 1 \
+            or not 1 <= int(rand_degree.shape[0]) <= min(int(w2c_pred.shape[0]), _lib.POSE_MAX_IMAGES):
+        raise ValueError(f"random_view_cameras: expected an integer rand_degree [b], 1 <= b <= min({w2c_pred.shape[0]}, {_lib.POSE_MAX_IMAGES}), got "
+                         f"{getattr(rand_degree, 'dtype', type(rand_degree))} {list(getattr(rand_degree, 'shape', []))}")
+    if not math.isfinite(float(delta_angle)):
+        raise ValueError(f"random_view_cameras: delta_angle {delta_angle} is not finite")
+    proj16 = _pose_proj(proj16, "random_view_cameras")
+    require_device(w2c_pred, what="random_view_cameras")
+    b = int(rand_degree.shape[0])
+    w2c_pred = f32c(w2c_pred.detach())
+    degree = rand_degree.detach().to(device=w2c_pred.device, dtype=torch.int64, non_blocking=True).contiguous()
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=w2c_pred.device)
+    mvp, w2c, campos = new(b, 4, 4), new(b, 4, 4), new(b, 3)
+    call("a3d_random_view_cameras", ptr(w2c_pred), ptr(degree), b, float(delta_angle), _proj_host(proj16), ptr(mvp), ptr(w2c), ptr(campos), stream())
+    return mvp, w2c, campos
+
+
 # ---------------------------------------------------------------------------------------------- mixed precision
 def _amp_wrap_functions():
     """Every autograd.Function of this module runs its forward with autocast OFF on float32 copies of half-precision inputs, and its

@@ -1,0 +1,404 @@
+"""3danimals_amd/pose.py without a GPU: the torch statements against what the reference's own functions returned
+(tests/golden/pose_*.npz: equal bits) and against the float64 restatement of tests/pose_ref.py (the MEASURED table), the restatement's
+hand-written gradients against autograd in float64, argument validation, the routing, the internal entry points against their header
+and argument refusal through the loaded library."""
+import importlib
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import pose_cases as C  # noqa: E402
+import pose_ref as R  # noqa: E402
+
+P = importlib.import_module("3danimals_amd.pose")
+L = importlib.import_module("3danimals_amd._lib")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+OUTPUTS = ("poses_raw", "pose_raw", "pose", "mvp", "w2c", "campos")
+CAMERA_KEYS = ("mvp", "w2c", "campos")
+
+
+# ---------------------------------------------------------------------------------------------------------------- running a case
+def _kwargs(c, device):
+    kw = C.fused_kwargs(c)
+    for k in ("rand_perm", "best_perm"):
+        kw[k] = None if kw[k] is None else kw[k].to(device)
+    return kw
+
+
+def run_fused(c, device="cpu", grads=None, dtype=torch.float32, fn=None):
+    """predict_cameras on case ``c`` -> the nine float outputs, the two integer ones, and g_raw for the upstream gradients ``grads``
+    (default: the case's own list)."""
+    raw = c["raw"].to(device=device, dtype=dtype).requires_grad_(True)
+    out = (fn or P.predict_cameras)(raw, c["total_iter"], **_kwargs(c, device))
+    res = dict(zip(OUTPUTS, out[:6]))
+    res.update(out[6])
+    grads = c["grads"] if grads is None else grads
+    res["g_raw"] = torch.autograd.grad([res[k] for k in grads], raw, [c["g"][k].to(device=device, dtype=dtype) for k in grads])[0]
+    res["_raw_leaf"] = raw
+    return res
+
+
+def run_cameras(c, device="cpu", grads=CAMERA_KEYS, dtype=torch.float32):
+    pose = c["pose"].to(device=device, dtype=dtype).requires_grad_(True)
+    res = dict(zip(CAMERA_KEYS, P.cameras_from_pose(pose, C.Z_OFFSET, C.FOV, offset_extra=c["offset_extra"])))
+    res["g_pose"] = torch.autograd.grad([res[k] for k in grads], pose, [c["g"][k].to(device=device, dtype=dtype) for k in grads])[0]
+    return res
+
+
+def run_random_view(c, device="cpu", degree_device=None):
+    out = P.random_view_cameras(c["w2c_pred"].to(device), c["rand_degree"].to(degree_device or device), C.FOV, c["bins"])
+    return dict(zip(CAMERA_KEYS, out))
+
+
+def compare(out, ref):
+    """key -> units for the float quantities; the integer ones must be equal."""
+    res = {}
+    for k, v in ref.items():
+        if isinstance(v, tuple):
+            res[k] = R.units(out[k], *v)
+        else:
+            assert out[k].dtype == torch.int64 and np.array_equal(out[k].cpu().numpy(), v), k
+    return res
+
+
+def measure(name):
+    """Units the torch float32 statements reach on one case (CPU, one thread)."""
+    prev = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        kind, _, row = name.partition("/")
+        if kind == "fused":
+            c = C.build_fused(row)
+            return compare(run_fused(c), R.evaluate_fused(c))
+        if kind == "fused_each":  # g_raw with all nine outputs fed, and with each fed alone
+            c = C.build_fused(row)
+            lists = dict({"g_all": C.FLOAT_OUTPUTS}, **{"g_" + k: (k,) for k in C.FLOAT_OUTPUTS})
+            return {key: R.units(run_fused(c, grads=grads)["g_raw"], *R.evaluate_fused(c, grads)["g_raw"]) for key, grads in lists.items()}
+        if kind == "cameras":
+            c = C.build_cameras(row)
+            return compare(run_cameras(c), R.evaluate_cameras(c))
+        if kind == "cameras_each":
+            c = C.build_cameras(row)
+            return {"g_" + k: R.units(run_cameras(c, grads=(k,))["g_pose"], *R.evaluate_cameras(c, (k,))["g_pose"]) for k in CAMERA_KEYS}
+        assert kind == "random_view", name
+        c = C.build_random_view(row)
+        return compare(run_random_view(c), R.evaluate_random_view(c))
+    finally:
+        torch.set_num_threads(prev)
+
+
+EACH_CASES = ("n5_h8_oct_it7000_rand", "hand_h4_it7000_rand", "n3_h4_it0_norand_only_probs")
+NAMES = ([f"fused/{n}" for n in C.FUSED_CASES] + [f"fused_each/{n}" for n in EACH_CASES] + [f"cameras/{n}" for n in C.CAMERA_CASES]
+         + [f"cameras_each/{n}" for n in C.CAMERA_CASES] + [f"random_view/{n}" for n in C.RANDOM_VIEW_CASES])
+
+
+def measure_all():
+    """The table pose_ref.MEASURED is written from (third decimal rounded up):
+    python -c 'import sys; sys.path.insert(0, "tests"); import test_pose_cpu as t; t.print_table()'"""
+    return {n: {k: float(np.ceil(u * 1000) / 1000) for k, u in measure(n).items()} for n in NAMES}
+
+
+def print_table():
+    for n, row in measure_all().items():
+        print(f'    "{n}": {{' + ", ".join(f'"{k}": {v}' for k, v in row.items()) + "},")
+
+
+@pytest.fixture(scope="module")
+def fresh():
+    return {n: measure(n) for n in NAMES}
+
+
+def test_measured_table_is_current(fresh):
+    """Every figure of pose_ref.MEASURED against a fresh measurement: not below it (third decimal rounded up), not more than the rounding
+    above it -- with a relative slack of 1e-3 for another summation order of a matrix product."""
+    assert sorted(R.MEASURED) == sorted(NAMES)
+    for n, row in fresh.items():
+        assert sorted(row) == sorted(R.MEASURED[n]), n
+        for k, u in row.items():
+            print(f"{n}: {k} {u:.4f} units (table {R.MEASURED[n][k]})")
+            assert np.isfinite(u), (n, k)
+            assert u <= R.MEASURED[n][k] * (1 + 1e-3) + 1e-9 and R.MEASURED[n][k] <= u * (1 + 1e-3) + 1.001e-3, (n, k, u, R.MEASURED[n][k])
+
+
+# ---------------------------------------------------------------------------------------------------------------- golden fixtures
+def _gold(which):
+    return np.load(os.path.join(GOLDEN, f"pose_{which}.npz"))
+
+
+def _same_bits(t, gold):
+    a = t.detach().numpy()
+    return a.dtype == gold.dtype and a.shape == gold.shape and a.tobytes() == gold.tobytes()
+
+
+@pytest.mark.parametrize("name", list(C.FUSED_CASES))
+def test_torch_statements_equal_what_the_reference_returned(name):
+    """forward_pose, sample_pose_hypothesis_from_quad_predictions (Fauna's where the clip is 10) and get_camera_extrinsics_from_pose of
+    the reference on the case's inputs: the three torch statements, called one by one, give the same bits; so does predict_cameras."""
+    c = C.build_fused(name)
+    heads, pick, cams = _gold("heads"), _gold("pick"), _gold("cameras")
+    if c["random_sample"]:  # the permutations the reference drew are the inputs recorded beside its results
+        assert np.array_equal(pick[name + "/rand_perm"], c["rand_perm"].numpy()) and np.array_equal(pick[name + "/best_perm"], c["best_perm"].numpy())
+    poses_raw = P.pose_heads(c["raw"], c["signs"], c["max_trans"], oct=c["oct"], lookat_zeroy=c["zeroy"])
+    assert _same_bits(poses_raw, heads[name])
+    pose_raw, pose, aux = P.pick_hypothesis(poses_raw, c["total_iter"], 1.0, c["H"], C.NAIVE_ITER, C.BEST_ITER, c["random_sample"],
+                                            c["temp_clip_max"], c["rand_perm"], c["best_perm"])
+    assert _same_bits(pose_raw, pick[name + "/pose_raw"]) and _same_bits(pose, pick[name + "/pose"])
+    assert sorted(aux) == sorted(P.AUX_KEYS)
+    for k in P.AUX_KEYS:
+        assert _same_bits(aux[k], pick[f"{name}/{k}"]), k
+    out = P.cameras_from_pose(pose, C.Z_OFFSET, C.FOV, offset_extra=c["offset_extra"])
+    for k, t in zip(CAMERA_KEYS, out):
+        assert _same_bits(t, cams[f"{name}/{k}"]), k
+    fused = P.predict_cameras(c["raw"], c["total_iter"], **C.fused_kwargs(c))  # on the CPU: the three functions chained
+    for a, b in zip(fused[:6], (poses_raw, pose_raw, pose) + tuple(out)):
+        assert torch.equal(a, b)
+    assert all(torch.equal(fused[6][k], aux[k]) for k in P.AUX_KEYS)
+    if name in C.TIE_CASES and not c["random_sample"]:
+        assert (aux["rot_idx"] == 0).all() and (aux["rots_probs"] == 1.0 / c["H"]).all()  # exact ties: hypothesis 0
+
+
+@pytest.mark.parametrize("name", list(C.CAMERA_CASES))
+def test_cameras_alone_equal_what_the_reference_returned(name):
+    c = C.build_cameras(name)
+    cams = _gold("cameras")
+    for k, t in zip(CAMERA_KEYS, P.cameras_from_pose(c["pose"], C.Z_OFFSET, C.FOV, offset_extra=c["offset_extra"])):
+        assert _same_bits(t, cams[f"alone_{name}/{k}"]), k
+
+
+@pytest.mark.parametrize("name", list(C.RANDOM_VIEW_CASES))
+def test_random_view_equals_what_the_reference_returned(name):
+    c = C.build_random_view(name)
+    views = _gold("random_view")
+    assert np.array_equal(views[name + "/rand_degree"], c["rand_degree"].numpy())
+    out = run_random_view(c)
+    for k in CAMERA_KEYS:
+        assert _same_bits(out[k], views[f"{name}/{k}"]) and not out[k].requires_grad, k
+    assert out["mvp"].shape[0] == len(c["degree"]) < c["w2c_pred"].shape[0]
+    for dtype in (torch.int32, torch.int16):  # any integer type
+        again = P.random_view_cameras(c["w2c_pred"], c["rand_degree"].to(dtype), C.FOV, c["bins"])
+        assert all(torch.equal(a, out[k]) for a, k in zip(again, CAMERA_KEYS))
+
+
+def test_a_seeded_run_draws_the_permutations_in_the_references_order():
+    c = C.build_fused("n5_h4_it200000_rand_boundary")
+    poses_raw = P.pose_heads(c["raw"], c["signs"], c["max_trans"])
+    torch.manual_seed(11)
+    first, second = torch.randperm(5), torch.randperm(5)
+    torch.manual_seed(11)
+    drawn = P.pick_hypothesis(poses_raw, 200000)
+    given = P.pick_hypothesis(poses_raw, 200000, rand_perm=first, best_perm=second)
+    assert all(torch.equal(drawn[2][k], given[2][k]) for k in P.AUX_KEYS) and torch.equal(drawn[1], given[1])
+    torch.manual_seed(11)
+    fused = P.predict_cameras(c["raw"], 200000, **dict(C.fused_kwargs(c), rand_perm=None, best_perm=None))
+    assert torch.equal(fused[6]["rot_idx"], given[2]["rot_idx"]) and torch.equal(fused[2], given[1])
+
+
+# ---------------------------------------------------------------------------------------------------------------- the rules
+def test_the_boundary_of_the_best_or_random_decision_is_torchs():
+    """perm / N < p as torch evaluates it (a float32 quotient against p rounded to float32) is perm < best_below(N, p); at N = 5,
+    p = 0.8 the value 4 is NOT below (4 / 5 and 0.8 round to the same float32), in exact arithmetic neither, in float64 against the
+    float32 quotient it would be."""
+    assert P.best_below(5, 0.8) == 4 and float(np.float32(4) / np.float32(5)) > 0.8
+    for N in (1, 2, 3, 5, 7, 10, 64, 65, 257, 1000):
+        for p in (0.0, 0.1, 0.25, 0.5, 0.3, 0.7, 0.8):
+            perm = torch.arange(N)
+            want = (perm / N < p)
+            assert torch.equal(want, perm < P.best_below(N, p)), (N, p)
+    gold = _gold("pick")
+    name = "n5_h4_it200000_rand_boundary"
+    c = C.build_fused(name)
+    flags = gold[name + "/rand_pose_flag"]
+    assert flags.sum() == 1 and c["best_perm"][int(flags.argmax())] == 4
+
+
+def test_argmax_takes_the_first_nan_else_the_lowest_index_among_equal_maxima():
+    H = 4
+    raw = torch.zeros(4, 4 * H + 3)
+    raw[0, 0:16:4] = torch.tensor([1.0, 0.5, 0.5, 2.0])  # two equal minima of the logit: two equal maxima of the probability
+    raw[1, 0:16:4] = torch.tensor([1.0, float("nan"), 0.0, float("nan")])
+    raw[2, 0:16:4] = torch.tensor([3.0, 3.0, 3.0, 3.0])
+    raw[3, 0:16:4] = torch.tensor([3.0, 2.0, 1.0, 0.0])
+    raw[:, 1:16:4] = 1.0
+    _, _, aux = P.pick_hypothesis(raw, 7000, random_sample=False)
+    assert aux["rot_idx"].tolist() == [1, 0, 0, 3]  # (a NaN logit makes the whole softmax row NaN: the first NaN is element 0)
+    _, _, aux = P.pick_hypothesis(raw, 1500, random_sample=False)
+    assert aux["rot_idx"][2] == 0 and aux["rot_idx"][3] == 0 and (aux["rots_probs"][3] == 0.25).all()  # the uniform blend: exact ties
+
+
+def test_restatement_gradients_agree_with_autograd_in_float64():
+    """tests/pose_ref.py writes every adjoint by hand; the torch statements run in float64 under autograd are a second opinion on the
+    values (to 1e-9 of the magnitude), for every output, every case and both kinds of gradient lists."""
+    for name in C.FUSED_CASES:
+        c = C.build_fused(name)
+        for grads in (c["grads"], C.FLOAT_OUTPUTS):
+            ref = R.evaluate_fused(c, grads)
+            out = run_fused(c, grads=grads, dtype=torch.float64)
+            for k, v in ref.items():
+                if isinstance(v, tuple):
+                    got = out[k].detach().numpy()
+                    assert (np.abs(got - v[0]) <= 1e-9 * v[1] + 1e-300).all(), (name, k, float(np.abs(got - v[0]).max()))
+    for name in C.CAMERA_CASES:
+        c = C.build_cameras(name)
+        ref, out = R.evaluate_cameras(c), run_cameras(c, dtype=torch.float64)
+        for k, v in ref.items():
+            assert (np.abs(out[k].detach().numpy() - v[0]) <= 1e-9 * v[1]).all(), (name, k)
+
+
+def test_bounds_catch_a_small_error_and_pass_the_rounded_restatement():
+    name = "n5_h8_oct_it7000_rand"
+    c = C.build_fused(name)
+    ref = R.evaluate_fused(c)
+    for k, v in ref.items():
+        if isinstance(v, tuple):
+            fig = R.figure(f"fused/{name}", k)
+            assert len(R.bad_elements(torch.from_numpy(v[0]).float(), *v, fig)) == 0, k
+            broken = v[0].copy()
+            i = np.unravel_index(v[1].argmax(), broken.shape)
+            broken[i] += 2.0 ** -18 * v[1][i]  # 64 units on one element
+            assert len(R.bad_elements(broken, *v, fig)) == 1, k
+
+
+# ---------------------------------------------------------------------------------------------------------------- arguments
+def test_malformed_arguments_raise_value_error():
+    c = C.build_fused("n3_h4_it7000_rand")
+    kw = C.fused_kwargs(c)
+    raw = c["raw"]
+    for bad in (dict(raw=raw[:, :18]), dict(raw=raw[0]), dict(raw=raw.long()), dict(raw=raw[:0]), dict(num_hypos=8), dict(orthant_signs=c["signs"][:3]),
+                dict(max_trans_xyz_range=c["max_trans"][:2]), dict(rand_perm=c["rand_perm"][:2]), dict(best_perm=c["best_perm"].float()),
+                dict(total_iter=float("nan")), dict(total_iter=-1), dict(rot_temp_scalar=0.0), dict(temp_clip_max=0.5), dict(fov=0.0),
+                dict(fov=float("inf")), dict(cam_pos_z_offset=float("nan")), dict(znear=1.0, zfar=1.0), dict(random_sample=False)):
+        args = dict(kw, raw=raw, total_iter=7000)
+        args.update(bad)
+        r, it = args.pop("raw"), args.pop("total_iter")
+        with pytest.raises(ValueError):
+            P.predict_cameras(r, it, **args)
+    poses_raw = P.pose_heads(raw, c["signs"], c["max_trans"])
+    for bad in (lambda: P.pose_heads(raw[:, :18], c["signs"], c["max_trans"]), lambda: P.pose_heads(raw, c["signs"], (1.0, 2.0)),
+                lambda: P.pose_heads([1.0], c["signs"], c["max_trans"]), lambda: P.pick_hypothesis(poses_raw, 7000, num_hypos=3),
+                lambda: P.pick_hypothesis(poses_raw.int(), 7000), lambda: P.pick_hypothesis(poses_raw, 7000, rand_perm=torch.arange(4)),
+                lambda: P.pick_hypothesis(poses_raw, 7000, random_sample=False, best_perm=torch.arange(3)),
+                lambda: P.cameras_from_pose(torch.zeros(3, 11), 10.0, 25.0), lambda: P.cameras_from_pose(torch.zeros(3, 12).long(), 10.0, 25.0),
+                lambda: P.cameras_from_pose(torch.zeros(0, 12), 10.0, 25.0), lambda: P.cameras_from_pose(torch.zeros(3, 12), 10.0, 180.0),
+                lambda: P.random_view_cameras(torch.zeros(3, 4, 4), torch.zeros(3), 25.0), lambda: P.random_view_cameras(torch.zeros(3, 4, 4), torch.zeros(4).long(), 25.0),
+                lambda: P.random_view_cameras(torch.zeros(3, 3, 4), torch.zeros(3).long(), 25.0), lambda: P.random_view_cameras(torch.zeros(3, 4, 4), torch.zeros(3).long(), 25.0, bins=0),
+                lambda: P.random_view_cameras(torch.zeros(3, 4, 4), torch.zeros(0).long(), 25.0)):
+        with pytest.raises(ValueError):
+            bad()
+    assert P.pose_heads(raw, c["signs"].tolist(), list(C.MAX_TRANS)).equal(poses_raw)  # sequences are tables too
+
+
+def test_nothing_is_written_into_an_argument():
+    c = C.build_fused("n5_h8_oct_zeroy_it200000_rand")
+    ins = [c["raw"], c["signs"], c["max_trans"], c["rand_perm"], c["best_perm"]]
+    before = [t.clone() for t in ins]
+    out = P.predict_cameras(c["raw"], c["total_iter"], **C.fused_kwargs(c))
+    P.cameras_from_pose(out[2], C.Z_OFFSET, C.FOV)
+    v = C.build_random_view("bins7")
+    w2c_before = v["w2c_pred"].clone()
+    P.random_view_cameras(v["w2c_pred"], v["rand_degree"], C.FOV, 7)
+    assert all(torch.equal(a, b) for a, b in zip(ins, before)) and torch.equal(v["w2c_pred"], w2c_before)
+
+
+# ---------------------------------------------------------------------------------------------------------------- routing
+class _Recorder:
+    def __init__(self):
+        self.calls = []
+
+    def pose_table(self, t, device):
+        return t
+
+    def __getattr__(self, name):
+        def record(*a, **k):
+            self.calls.append(name)
+            raise _Reached(name)
+
+        return record
+
+
+class _Reached(Exception):
+    pass
+
+
+def test_routing(monkeypatch):
+    """CPU tensors never reach ops; tensors that say they are on the device do, unless DEVICE is False or the size is one the kernels
+    refuse (H > 8, more than 65535 images), which take the torch statements."""
+    rec = _Recorder()
+    monkeypatch.setattr(P, "_ops", lambda: rec)
+    c = C.build_fused("n3_h4_it7000_rand")
+    v = C.build_random_view("bins7")
+    assert P.DEVICE is True
+    P.predict_cameras(c["raw"], 7000, **C.fused_kwargs(c))
+    P.cameras_from_pose(torch.zeros(3, 12), 10.0, 25.0)
+    P.random_view_cameras(v["w2c_pred"], v["rand_degree"], 25.0, 7)
+    assert rec.calls == []
+    monkeypatch.setattr(torch.Tensor, "is_cuda", property(lambda self: True), raising=False)
+    for call, name in ((lambda: P.predict_cameras(c["raw"], 7000, **C.fused_kwargs(c)), "predict_cameras"),
+                       (lambda: P.cameras_from_pose(torch.zeros(3, 12), 10.0, 25.0), "cameras_from_pose"),
+                       (lambda: P.random_view_cameras(v["w2c_pred"], v["rand_degree"], 25.0, 7), "random_view_cameras")):
+        with pytest.raises(_Reached, match=name):
+            call()
+    assert rec.calls == ["predict_cameras", "cameras_from_pose", "random_view_cameras"]
+    del rec.calls[:]
+    # sizes the kernels refuse
+    H = L.POSE_MAX_HYPOS + 1
+    signs = torch.ones(H, 3)
+    out = P.predict_cameras(torch.randn(2, 4 * H + 3), 7000, orthant_signs=signs, max_trans_xyz_range=c["max_trans"], cam_pos_z_offset=10.0, fov=25.0,
+                            num_hypos=H)
+    assert out[0].shape == (2, 4 * H + 3) and out[6]["rots_probs"].shape == (2, H)
+    many = L.POSE_MAX_IMAGES + 1
+    out = P.predict_cameras(torch.randn(many, 19), 7000, **dict(C.fused_kwargs(c), rand_perm=None, best_perm=None))
+    assert out[3].shape == (many, 4, 4)
+    assert P.cameras_from_pose(torch.zeros(many, 12), 10.0, 25.0)[0].shape == (many, 4, 4)
+    assert rec.calls == []
+    monkeypatch.setattr(P, "DEVICE", False)
+    P.predict_cameras(c["raw"], 7000, **C.fused_kwargs(c))
+    P.cameras_from_pose(torch.zeros(3, 12), 10.0, 25.0)
+    P.random_view_cameras(v["w2c_pred"], v["rand_degree"], 25.0, 7)
+    assert rec.calls == []
+
+
+# ---------------------------------------------------------------------------------------------------------------- the registry
+def test_the_internal_entry_points_match_their_header_and_stay_out_of_the_public_registry():
+    import ctypes
+
+    import abi_check as Abi
+
+    header = os.path.join(os.path.dirname(os.path.abspath(L.__file__)), "csrc", "pose.h")
+    protos = Abi.prototypes(header)
+    assert set(protos) == set(L.POSE_SIGNATURES) and len(protos) == 5
+    assert not any(k.startswith("?") for ret, params in protos.values() for k in [ret] + params)
+    assert all(protos[name] == Abi.kinds(sig) for name, sig in L.POSE_SIGNATURES.items())
+    assert not set(L.POSE_SIGNATURES) & (set(L.SIGNATURES) | set(L.FIELD_GRAD_SIGNATURES) | set(L.ARTICULATION_SIGNATURES))
+    assert len(L.SIGNATURES) == 126 and L.ABI_VERSION == 405
+    assert len([v for v in vars(L).values() if isinstance(v, type) and issubclass(v, ctypes.Structure) and v is not ctypes.Structure]) == 13
+    assert Abi.defines(header) == {"A3D_POSE_MAX_HYPOS": L.POSE_MAX_HYPOS, "A3D_POSE_MAX_IMAGES": L.POSE_MAX_IMAGES}
+    assert not os.path.exists(os.path.join(Abi.INCLUDE, "a3d_pose.h"))
+    lib = L.lib()
+    assert lib.a3d_version() == 405
+    for name, (res, args) in L.POSE_SIGNATURES.items():
+        fn = getattr(lib, name)
+        assert fn.restype is res and list(fn.argtypes) == list(args), name
+    overlay = importlib.import_module("3danimals_amd.overlay")
+    assert len(overlay.MODULES) == 9
+
+
+def test_arguments_are_refused_before_anything_is_launched():
+    """Through the loaded library, without a device: H of 0 and 9, N of 0, 65536 and 2^31 - 1, a null operand."""
+    import ctypes
+
+    lib = L.lib()
+    proj = (ctypes.c_float * 16)()
+    fwd = lambda N, H, p=proj: lib.a3d_pose_cameras_fwd(None, None, None, None, None, N, H, 0, 0, 1.0, 0.0, 1.0, 0, 0.0, p, *([None] * 12))
+    bwd = lambda N, H, p=proj: lib.a3d_pose_cameras_bwd(None, None, None, None, None, N, H, 0, 0, 1.0, 0.0, 1.0, 0, 0.0, p, *([None] * 11))
+    for f in (fwd, bwd):
+        for N, H in ((1, 0), (1, 9), (0, 4), (-1, 4), (65536, 4), (2 ** 31 - 1, 4), (3, 4)):  # (the last: null operands)
+            assert f(N, H) != 0, (N, H)
+            assert b"invalid argument" in lib.a3d_last_error()
+    for N in (0, 65536, 2 ** 31 - 1, 3):
+        assert lib.a3d_cameras_from_pose_fwd(None, N, 0.0, proj, None, None, None, None) != 0
+        assert lib.a3d_cameras_from_pose_bwd(None, N, 0.0, proj, None, None, None, None, None) != 0
+        assert lib.a3d_random_view_cameras(None, None, N, 0.1, proj, None, None, None, None) != 0
