@@ -1,5 +1,5 @@
-"""ctypes binding of liba3d_hip.so: SURFACES registers each public header of include/ with its entry points, struct mirrors and
-constants.  No fallback: if the library is missing we say so and stop."""
+"""ctypes binding of liba3d_hip.so: SURFACES registers each public header of include/, INTERNAL_SURFACES each internal header of csrc/,
+with its entry points, struct mirrors and constants.  No fallback: if the library is missing we say so and stop."""
 from __future__ import annotations
 
 import ctypes
@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("A3D_LIB") or os.path.join(_HERE, "lib", "liba3d_hip.s
 _c_int, _c_float, _c_size_t, _p = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_void_p
 
 
-# ---- ctypes mirrors of the headers' structs (registered by their C names in SURFACES below)
+# ---- ctypes mirrors of the headers' structs (registered by their C names in SURFACES / INTERNAL_SURFACES below)
 class DmtetOrder(ctypes.Structure):
     _fields_ = [("size", ctypes.c_uint32), ("group_slots", ctypes.c_int32), ("vertex_of_rank", _p), ("edges_ranked", _p), ("edge_of_row", _p),
                 ("tets_ranked", _p), ("tet_of_row", _p), ("edge_groups", _p), ("tet_groups", _p)]
@@ -96,7 +96,11 @@ class EnvShadeDesc(ctypes.Structure):
                 ("g_out", _p), ("g_in", _p * 4)]
 
 
-# ---- Python values of the headers' macros (registered by their C names in SURFACES below)
+class EbFpsTail(ctypes.Structure):  # (internal, csrc/eb_common.h: the bytes behind a3d_estimate_bones_args; no ``size`` of its own)
+    _fields_ = [("k", ctypes.c_int32), ("sample_only", ctypes.c_int32), ("start", _p), ("sampled", _p), ("idx", _p)]
+
+
+# ---- Python values of the headers' macros (registered by their C names in SURFACES / INTERNAL_SURFACES below)
 BSDF_TILE = 1024
 BSDF_MAX_DIMS = 4
 DERIV_MAX_SELECTED = 64
@@ -122,6 +126,18 @@ EB_WIDE_SLAB = 1024
 EB_WIDE_FIXED_WORDS = 16640
 EB_WIDE_WORDS_PER_INSTANCE = 15
 EB_WIDE_WORDS_PER_SLAB = 6
+FPS_TAIL_SIZE = 32  # sizeof(a3d_eb_fps_tail): the resample tail behind a3d_estimate_bones_args
+FPS_MAX_V = 131072
+FPS_REG_MAX_V = 16384  # beyond it the sampler keeps its running distances in the workspace
+GBUFFER_GRAD_COLS = 16
+TEX_MAX_LEVELS = 16
+ARTICULATION_CHUNK = 32  # feature columns per work-group of the descriptor kernels
+ARTICULATION_MAX_BONES = 64
+ARTICULATION_MAX_SIDE = 4096
+ARTICULATION_MAX_ANGLES = 1 << 20
+ARTICULATION_MAX_IMAGES = 65535
+POSE_MAX_HYPOS = 8
+POSE_MAX_IMAGES = 65535
 
 
 def eb_wide_workspace_words(N, V):
@@ -130,14 +146,20 @@ def eb_wide_workspace_words(N, V):
 
 
 class Surface(NamedTuple):
-    """One public header of the library and everything this module mirrors of it.  tests/test_abi_cpu.py holds every field of every
-    entry to the header; a new entry point is a line in its header's table, a new header one more entry ("Adding an
-    entry point")."""
+    """One header of the library and everything this module mirrors of it: a public one of include/ (SURFACES) or an internal one of
+    csrc/ (INTERNAL_SURFACES: bound by lib() like the others, no part of the public surface or of a3d_version()).
+    tests/test_abi_cpu.py holds every field of every entry to the header; a new entry point is a line in its header's table, a new
+    header one more entry ("Adding an entry point")."""
 
-    header: str  # file name under include/
+    header: str  # file name under include/, or under csrc/ when internal
     signatures: dict  # entry point -> (restype, argtypes)
     structs: dict  # C struct name -> its ctypes mirror
     constants: dict  # macro name -> the Python value that mirrors it
+    internal: bool = False
+
+    @property
+    def path(self):
+        return os.path.join(_HERE, "csrc", self.header) if self.internal else os.path.join(os.path.dirname(_HERE), "include", self.header)
 
 
 SURFACES = (
@@ -241,7 +263,9 @@ SURFACES = (
         "a3d_ca_buffer": CaBuffer, "a3d_tex_desc": TexDesc, "a3d_env_desc": EnvDesc},
        {"A3D_EB_ONE_GROUP_MAX_N": EB_ONE_GROUP_MAX_N, "A3D_EB_ONE_GROUP_MAX_POINTS": EB_ONE_GROUP_MAX_POINTS,
         "A3D_EB_WIDE_MAX_POINTS": EB_WIDE_MAX_POINTS, "A3D_EB_WIDE_SLAB": EB_WIDE_SLAB, "A3D_EB_WIDE_FIXED_WORDS": EB_WIDE_FIXED_WORDS,
-        "A3D_EB_WIDE_WORDS_PER_INSTANCE": EB_WIDE_WORDS_PER_INSTANCE, "A3D_EB_WIDE_WORDS_PER_SLAB": EB_WIDE_WORDS_PER_SLAB}),
+        "A3D_EB_WIDE_WORDS_PER_INSTANCE": EB_WIDE_WORDS_PER_INSTANCE, "A3D_EB_WIDE_WORDS_PER_SLAB": EB_WIDE_WORDS_PER_SLAB,
+        "A3D_FPS_TAIL_SIZE": FPS_TAIL_SIZE, "A3D_FPS_MAX_V": FPS_MAX_V, "A3D_FPS_REG_MAX_V": FPS_REG_MAX_V,
+        "A3D_GBUFFER_GRAD_COLS": GBUFFER_GRAD_COLS, "A3D_TEX_MAX_LEVELS": TEX_MAX_LEVELS}),
     Surface("a3d_bsdf.h", {
         "a3d_bsdf_rows": (ctypes.c_int64, [_p]),
         "a3d_bsdf_fwd": (_c_int, [_p, _p]),
@@ -297,52 +321,42 @@ SURFACES = (
         "a3d_nearest_visible_vertex_fwd": (_c_int, [_p, _p, _p, _c_int, _c_int, _c_int, _p, _p, _p]),
     }, {}, {"A3D_NVV_THREADS": NVV_THREADS, "A3D_NVV_MAX_TRIPS": NVV_MAX_TRIPS, "A3D_NVV_KEYPOINT_TILE": NVV_KEYPOINT_TILE}),
 )
-SIGNATURES = {name: sig for s in SURFACES for name, sig in s.signatures.items()}  # every entry point of the library: what lib() binds
-assert len(SIGNATURES) == sum(len(s.signatures) for s in SURFACES), "an entry point is registered in two surfaces"
-
-# Internal entry points (csrc/fieldgrad.h): the SDF input-gradient route of hostnets.USE_FIELD_GRAD.  Bound by lib() like the public ones,
-# no part of the public surface: no header under include/ declares them, SURFACES / SIGNATURES and a3d_version() do not change.
-FIELD_GRAD_SIGNATURES = {
-    "a3d_gemm_nt_relumask": (_c_int, [_p, _p, _p, ctypes.c_int64, _c_int, _c_int, _p, _p]),
-    "a3d_harmonic_embed_jvp": (_c_int, [_p, _p, _p, _c_int, _c_int, _c_int, ctypes.c_int64, _p, _p]),
-    "a3d_field_grad_head_fwd": (_c_int, [_p, _p, _p, ctypes.c_int64, _p, _p]),
-    "a3d_field_grad_head_scratch_bytes": (_c_size_t, [ctypes.c_int64]),
-    "a3d_field_grad_head_bwd": (_c_int, [_p, _p, _p, ctypes.c_int64, _p, _p, _p, _p]),
-    "a3d_gemm_tn_splitk_scratch_bytes": (_c_size_t, [ctypes.c_int64, _c_int, _c_int]),
-    "a3d_gemm_tn_splitk": (_c_int, [_p, _p, ctypes.c_int64, _c_int, _c_int, _p, _p, _p]),
-}
-assert not set(FIELD_GRAD_SIGNATURES) & set(SIGNATURES)
-
-# Internal entry points (csrc/articulation.h): the per-bone descriptors and the angle limits of articulation.py.  As above: bound by
-# lib(), flat arguments, no part of the public surface.
-ARTICULATION_CHUNK = 32  # feature columns per work-group of the descriptor kernels (A3D_ARTICULATION_CHUNK)
-ARTICULATION_MAX_BONES = 64
-ARTICULATION_MAX_SIDE = 4096
-ARTICULATION_MAX_ANGLES = 1 << 20
-ARTICULATION_MAX_IMAGES = 65535
 _i64 = ctypes.c_int64
-ARTICULATION_SIGNATURES = {
-    "a3d_bone_inputs_fwd": (_c_int, [_p, _c_int, _p, _p, _c_float, _c_float, _p, _p, _i64, _i64, _i64, _i64, _c_int, _c_int, _c_int, _c_int,
-                                     _c_int, _c_int, _p, _p, _p]),
-    "a3d_bone_inputs_bwd": (_c_int, [_p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _i64, _i64, _i64, _i64, _p]),
-    "a3d_constrain_angles_fwd": (_c_int, [_p, _p, _c_float, _c_int, _c_int, _p, _p, _p]),
-    "a3d_constrain_angles_bwd": (_c_int, [_p, _p, _p, _p, _c_float, _c_int, _c_int, _p, _p]),
-}
-assert not set(ARTICULATION_SIGNATURES) & (set(SIGNATURES) | set(FIELD_GRAD_SIGNATURES))
-
-# Internal entry points (csrc/pose.h): the pose heads, the hypothesis pick with its look-at rotation, the cameras of a pose and Fauna's
-# random-view cameras of pose.py.  As above: bound by lib(), flat arguments, no part of the public surface.  ``proj`` is a host pointer.
-POSE_MAX_HYPOS = 8
-POSE_MAX_IMAGES = 65535
-_pose_common = [_p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_float, _c_float, _c_float, _i64, _c_float, _p]
-POSE_SIGNATURES = {
-    "a3d_pose_cameras_fwd": (_c_int, _pose_common + [_p] * 12),
-    "a3d_pose_cameras_bwd": (_c_int, _pose_common + [_p] * 11),
-    "a3d_cameras_from_pose_fwd": (_c_int, [_p, _c_int, _c_float, _p, _p, _p, _p, _p]),
-    "a3d_cameras_from_pose_bwd": (_c_int, [_p, _c_int, _c_float, _p, _p, _p, _p, _p, _p]),
-    "a3d_random_view_cameras": (_c_int, [_p, _p, _c_int, _c_float, _p, _p, _p, _p, _p]),
-}
-assert not set(POSE_SIGNATURES) & (set(SIGNATURES) | set(FIELD_GRAD_SIGNATURES) | set(ARTICULATION_SIGNATURES))
+_pose_common = [_p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_float, _c_float, _c_float, _i64, _c_float, _p]  # (``proj``, last: a host pointer)
+INTERNAL_SURFACES = (
+    Surface("fieldgrad.h", {  # the SDF input-gradient route of hostnets.USE_FIELD_GRAD
+        "a3d_gemm_nt_relumask": (_c_int, [_p, _p, _p, _i64, _c_int, _c_int, _p, _p]),
+        "a3d_harmonic_embed_jvp": (_c_int, [_p, _p, _p, _c_int, _c_int, _c_int, _i64, _p, _p]),
+        "a3d_field_grad_head_fwd": (_c_int, [_p, _p, _p, _i64, _p, _p]),
+        "a3d_field_grad_head_scratch_bytes": (_c_size_t, [_i64]),
+        "a3d_field_grad_head_bwd": (_c_int, [_p, _p, _p, _i64, _p, _p, _p, _p]),
+        "a3d_gemm_tn_splitk_scratch_bytes": (_c_size_t, [_i64, _c_int, _c_int]),
+        "a3d_gemm_tn_splitk": (_c_int, [_p, _p, _i64, _c_int, _c_int, _p, _p, _p]),
+    }, {}, {}, internal=True),
+    Surface("articulation.h", {  # the per-bone descriptors and the angle limits of articulation.py
+        "a3d_bone_inputs_fwd": (_c_int, [_p, _c_int, _p, _p, _c_float, _c_float, _p, _p, _i64, _i64, _i64, _i64, _c_int, _c_int, _c_int, _c_int,
+                                         _c_int, _c_int, _p, _p, _p]),
+        "a3d_bone_inputs_bwd": (_c_int, [_p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _i64, _i64, _i64, _i64, _p]),
+        "a3d_constrain_angles_fwd": (_c_int, [_p, _p, _c_float, _c_int, _c_int, _p, _p, _p]),
+        "a3d_constrain_angles_bwd": (_c_int, [_p, _p, _p, _p, _c_float, _c_int, _c_int, _p, _p]),
+    }, {}, {"A3D_ARTICULATION_CHUNK": ARTICULATION_CHUNK, "A3D_ARTICULATION_MAX_BONES": ARTICULATION_MAX_BONES,
+            "A3D_ARTICULATION_MAX_SIDE": ARTICULATION_MAX_SIDE, "A3D_ARTICULATION_MAX_ANGLES": ARTICULATION_MAX_ANGLES,
+            "A3D_ARTICULATION_MAX_IMAGES": ARTICULATION_MAX_IMAGES}, internal=True),
+    Surface("pose.h", {  # the pose heads, the hypothesis pick with its look-at rotation, the cameras of a pose, Fauna's random views (pose.py)
+        "a3d_pose_cameras_fwd": (_c_int, _pose_common + [_p] * 12),
+        "a3d_pose_cameras_bwd": (_c_int, _pose_common + [_p] * 11),
+        "a3d_cameras_from_pose_fwd": (_c_int, [_p, _c_int, _c_float, _p, _p, _p, _p, _p]),
+        "a3d_cameras_from_pose_bwd": (_c_int, [_p, _c_int, _c_float, _p, _p, _p, _p, _p, _p]),
+        "a3d_random_view_cameras": (_c_int, [_p, _p, _c_int, _c_float, _p, _p, _p, _p, _p]),
+    }, {}, {"A3D_POSE_MAX_HYPOS": POSE_MAX_HYPOS, "A3D_POSE_MAX_IMAGES": POSE_MAX_IMAGES}, internal=True),
+    Surface("eb_common.h", {}, {"a3d_eb_fps_tail": EbFpsTail}, {}, internal=True),  # what ops.pack_fps_block puts behind a3d_estimate_bones_args
+)
+ALL_SURFACES = SURFACES + INTERNAL_SURFACES
+SIGNATURES = {name: sig for s in SURFACES for name, sig in s.signatures.items()}  # the public entry points
+BOUND_SIGNATURES = {name: sig for s in ALL_SURFACES for name, sig in s.signatures.items()}  # every entry point of the library: what lib() binds
+for _kind in ("signatures", "structs", "constants"):
+    _names = [name for s in ALL_SURFACES for name in getattr(s, _kind)]
+    assert len(_names) == len(set(_names)), f"registered in two surfaces: {sorted(n for n in set(_names) if _names.count(n) > 1)}"
 
 ABI_VERSION = 405  # a3d_version() of the library these signatures belong to (include/a3d.h)
 _lib = None
@@ -362,8 +376,7 @@ def lib():
                 "(or __graft_entry__.build()).  There is no CPU fallback for the HIP hot path."
             )
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(FIELD_GRAD_SIGNATURES.items()) + list(ARTICULATION_SIGNATURES.items()) \
-                + list(POSE_SIGNATURES.items()):
+        for name, (res, args) in BOUND_SIGNATURES.items():
             fn = getattr(handle, name)  # AttributeError here == ABI drift
             fn.restype, fn.argtypes = res, args
         if handle.a3d_version() != ABI_VERSION:  # same symbols, other argument lists: a stale build must not be called

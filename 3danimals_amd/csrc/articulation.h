@@ -1,6 +1,6 @@
 /* liba3d_hip: the articulation glue of the posing path -- per-bone descriptors (the reference's get_bones / get_bones_from_articulation
  * arithmetic) and the angle limits (apply_articulation_constraints with arti_reg_loss); DESIGN.md section 36.  An INTERNAL header: these
- * entry points serve the package's own articulation.py / ops.py, are bound from _lib.ARTICULATION_SIGNATURES and are no part of the public
+ * entry points serve the package's own articulation.py / ops.py, are registered in _lib.INTERNAL_SURFACES and are no part of the public
  * surface under include/ (126 entry points, a3d_version() 405: both unchanged).  Same conventions as include/a3d.h: flat C, device
  * pointers + sizes + a3d_stream_t, int status with the message in a3d_last_error(), arguments validated before anything is launched, no
  * allocation and no synchronisation inside a call.  Every call is ONE launch, without memset and without atomics: the same bits on every
@@ -20,6 +20,8 @@
 #define A3D_ARTICULATION_MAX_SIDE 4096
 /* most elements (N * K * 3) the one work-group of the limits kernels strides over */
 #define A3D_ARTICULATION_MAX_ANGLES 1048576
+/* most images of one call: the descriptor kernels take the image from the grid's y */
+#define A3D_ARTICULATION_MAX_IMAGES 65535
 
 #ifdef __cplusplus
 extern "C" {

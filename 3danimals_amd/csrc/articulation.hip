@@ -242,7 +242,7 @@ __global__ __launch_bounds__(CA_THREADS) void constrain_angles_bwd_kernel(const 
     A3D_CHECK_ARG(K >= 1 && K <= A3D_ARTICULATION_MAX_BONES && N >= 0 && D >= 0 && C >= 0);                                \
     A3D_CHECK_ARG(C == 0 || (h >= 1 && h <= A3D_ARTICULATION_MAX_SIDE && w >= 1 && w <= A3D_ARTICULATION_MAX_SIDE));       \
     A3D_CHECK_ARG((long long)N * K * ((long long)D + C) < (1ll << 31) && (long long)N * K * 9 < (1ll << 31));              \
-    A3D_CHECK_ARG((long long)N * D < (1ll << 31) && (long long)N * C < (1ll << 31) && N <= 65535)
+    A3D_CHECK_ARG((long long)N * D < (1ll << 31) && (long long)N * C < (1ll << 31) && N <= A3D_ARTICULATION_MAX_IMAGES)
 
 extern "C" int a3d_bone_inputs_fwd(const float* bones, int bones_shared, const float* mvp, const float* w2c, float cam_pos_z_offset,
                                    float spatial_scale, const float* feat, const float* patch, int64_t sn, int64_t sc, int64_t sh, int64_t sw, int N,

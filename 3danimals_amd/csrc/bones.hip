@@ -429,7 +429,7 @@ extern "C" int a3d_estimate_bones(const a3d_estimate_bones_args* args, a3d_strea
         A3D_CHECK_ARG(tail->k >= 1 && tail->k <= args->V);
         A3D_CHECK_ARG(tail->start && tail->sampled);
         A3D_CHECK_ARG(args->V <= A3D_FPS_REG_MAX_V || args->workspace);  // (beyond the register regime the running distances live there)
-        if (tail->sample_only) return a3d_eb_fps_launch(whole, tail, (hipStream_t)stream);
+        if (tail->sample_only) return eb_fps_launch(whole, tail, (hipStream_t)stream);
         resampled = *args;  // the bones of the sampled clouds: validated below like any call, before the sampler is launched
         resampled.size = sizeof(a3d_estimate_bones_args); resampled.pos = tail->sampled; resampled.V = tail->k;
         args = &resampled;
@@ -441,10 +441,10 @@ extern "C" int a3d_estimate_bones(const a3d_estimate_bones_args* args, a3d_strea
     A3D_CHECK_ARG(!wide || ((uintptr_t)args->workspace & 15) == 0);  // (histogram rows are read 16 bytes at a time, keys and sums are 8-byte words)
     A3D_CHECK_ARG(args->n_leg == 0 || (args->attach[0] < args->n_body && args->attach[1] < args->n_body && args->attach[2] < args->n_body && args->attach[3] < args->n_body));
     if (tail) {
-        const int rc = a3d_eb_fps_launch(whole, tail, (hipStream_t)stream);
+        const int rc = eb_fps_launch(whole, tail, (hipStream_t)stream);
         if (rc != A3D_OK) return rc;
     }
-    if (wide) return a3d_eb_wide_launch(args, (hipStream_t)stream);
+    if (wide) return eb_wide_launch(args, (hipStream_t)stream);
     EbParams p;
     p.pos = args->pos; p.N = args->N; p.V = args->V; p.n_body = args->n_body; p.n_leg = args->n_leg; p.yplus = args->body_mode_y_plus;
     p.fauna = args->use_y_threshold; p.y_q = args->y_threshold;

@@ -398,7 +398,7 @@ __global__ __launch_bounds__(EBW_THREADS) void ebw_finish_kernel(const EbwParams
 }  // namespace
 
 // the launches of a validated wide call (a3d_estimate_bones, bones.hip)
-int a3d_eb_wide_launch(const a3d_estimate_bones_args* args, hipStream_t stream) {
+int eb_wide_launch(const a3d_estimate_bones_args* args, hipStream_t stream) {
     EbwParams p;
     p.pos = args->pos; p.N = args->N; p.V = args->V; p.slabs = a3d_div_up(args->V, A3D_EB_WIDE_SLAB);
     p.n_body = args->n_body; p.n_leg = args->n_leg; p.yplus = args->body_mode_y_plus; p.fauna = args->use_y_threshold; p.y_q = args->y_threshold;

@@ -8,10 +8,11 @@
 #include "a3d_common.h"
 
 // the launches of a call on the multi-work-group path (bones_wide.hip); a3d_estimate_bones (bones.hip) has validated ``args``
-int a3d_eb_wide_launch(const a3d_estimate_bones_args* args, hipStream_t stream);
+int eb_wide_launch(const a3d_estimate_bones_args* args, hipStream_t stream);
 
 // The resample tail of a3d_estimate_bones (include/a3d.h describes it in words: the public struct stays as it is).  A caller that wants
 // the clouds resampled first passes  size >= sizeof(a3d_estimate_bones_args) + A3D_FPS_TAIL_SIZE  and these bytes behind the public struct.
+// (_lib.EbFpsTail mirrors it, registered on this header's entry of _lib.INTERNAL_SURFACES; no ``size`` of its own: it is no public struct.)
 typedef struct a3d_eb_fps_tail {
     int32_t k;             /* points kept per cloud, 1 <= k <= V */
     int32_t sample_only;   /* non-zero: the sampler alone; bones, nearest, ok are not touched and may be null */
@@ -24,7 +25,7 @@ static_assert(sizeof(a3d_eb_fps_tail) == A3D_FPS_TAIL_SIZE, "include/a3d.h state
 static_assert(offsetof(a3d_eb_fps_tail, k) == 0 && offsetof(a3d_eb_fps_tail, sample_only) == 4 && offsetof(a3d_eb_fps_tail, start) == 8 &&
               offsetof(a3d_eb_fps_tail, sampled) == 16 && offsetof(a3d_eb_fps_tail, idx) == 24, "include/a3d.h states the tail's byte layout");
 // the sampler of a call with the tail (fps.hip); a3d_estimate_bones (bones.hip) has validated both
-int a3d_eb_fps_launch(const a3d_estimate_bones_args* args, const a3d_eb_fps_tail* tail, hipStream_t stream);
+int eb_fps_launch(const a3d_estimate_bones_args* args, const a3d_eb_fps_tail* tail, hipStream_t stream);
 
 #define EB_MAXSEL 12   // ranks looked for at once: 2 coordinates x 3 quantiles x the two neighbours a quantile interpolates between
 #define EB_MAXGROUP 6  // ... of one coordinate

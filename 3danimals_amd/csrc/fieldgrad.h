@@ -1,6 +1,6 @@
 /* liba3d_hip: the input gradient of a scalar coordinate field and its adjoint -- the kernels behind hostnets.USE_FIELD_GRAD (the eikonal
- * regulariser).  An INTERNAL header: these entry points serve the package's own hostnets / ops.py, are bound from
- * _lib.FIELD_GRAD_SIGNATURES and are no part of the public surface under include/ (126 entry points, a3d_version() 405: both unchanged).
+ * regulariser).  An INTERNAL header: these entry points serve the package's own hostnets / ops.py, are registered in
+ * _lib.INTERNAL_SURFACES and are no part of the public surface under include/ (126 entry points, a3d_version() 405: both unchanged).
  * Same conventions as include/a3d.h: flat C, device pointers + sizes + a3d_stream_t, int status with the message in a3d_last_error(),
  * arguments validated before anything is launched, no allocation and no synchronisation inside a call. */
 #ifndef A3D_FIELDGRAD_H

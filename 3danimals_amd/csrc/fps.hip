@@ -191,7 +191,7 @@ void fps_launch_reg(const FpsParams& p, int N, hipStream_t stream) {
 }  // namespace
 
 // the sampler of a validated call with the resample tail (a3d_estimate_bones, bones.hip)
-int a3d_eb_fps_launch(const a3d_estimate_bones_args* args, const a3d_eb_fps_tail* tail, hipStream_t stream) {
+int eb_fps_launch(const a3d_estimate_bones_args* args, const a3d_eb_fps_tail* tail, hipStream_t stream) {
     FpsParams p;
     p.pos = args->pos; p.start = tail->start; p.sampled = tail->sampled; p.idx = tail->idx;
     p.dist = reinterpret_cast<unsigned*>(args->workspace); p.V = args->V; p.k = tail->k;

@@ -1,7 +1,7 @@
 /* liba3d_hip: the camera-pose glue of the predictors -- the heads of the pose network's output, the pick of one hypothesis with its
  * look-at rotation, the cameras of a pose, and Fauna's random-view cameras (the reference's forward_pose,
  * sample_pose_hypothesis_from_quad_predictions, get_camera_extrinsics_from_pose and get_random_view_mask arithmetic); DESIGN.md section
- * 37.  An INTERNAL header: these entry points serve the package's own pose.py / ops.py, are bound from _lib.POSE_SIGNATURES and are no
+ * 37.  An INTERNAL header: these entry points serve the package's own pose.py / ops.py, are registered in _lib.INTERNAL_SURFACES and are no
  * part of the public surface under include/ (126 entry points, a3d_version() 405: both unchanged).  Same conventions as include/a3d.h:
  * flat C, device pointers + sizes + a3d_stream_t, int status with the message in a3d_last_error(), arguments validated before anything
  * is launched, no allocation and no synchronisation inside a call.  Every call is ONE launch of one thread per image, without memset

@@ -9,7 +9,6 @@ from __future__ import annotations
 import ctypes
 import math
 import os
-import struct
 from collections import OrderedDict
 
 import torch
@@ -441,24 +440,21 @@ def _linspace01(n):
     return _linspace_cache[n]
 
 
-# ---- the resample tail of a3d_estimate_bones (include/a3d.h; csrc/eb_common.h: a3d_eb_fps_tail).  Packed here, behind the public struct:
-# the registry of _lib mirrors the public headers and the tail is in none of them.
-FPS_TAIL = struct.Struct("<iiQQQ")  # k, sample_only, start, sampled, idx
-FPS_TAIL_FIELDS = ("k", "sample_only", "start", "sampled", "idx")
-FPS_TAIL_SIZE = 32   # A3D_FPS_TAIL_SIZE
-FPS_MAX_V = 131072   # A3D_FPS_MAX_V
-FPS_REG_MAX_V = 16384  # A3D_FPS_REG_MAX_V: beyond it the sampler keeps its running distances in the workspace
+# ---- the resample tail of a3d_estimate_bones (include/a3d.h; csrc/eb_common.h: a3d_eb_fps_tail).  _lib.EbFpsTail is its registered
+# mirror (the eb_common.h entry of _lib.INTERNAL_SURFACES); filled here, behind the public struct.
+FPS_TAIL_SIZE, FPS_MAX_V, FPS_REG_MAX_V = _lib.FPS_TAIL_SIZE, _lib.FPS_MAX_V, _lib.FPS_REG_MAX_V
 
 
 def pack_fps_block(public, k, sample_only, start, sampled, idx):
     """The bytes a3d_estimate_bones takes for a call that resamples first: ``public`` (an _lib.EstimateBonesArgs; its ``size`` is set
-    here) followed by the tail -- k, the sample-only flag and three device addresses (0 = null).  8-byte aligned, like the struct."""
+    here) followed by the tail -- k, the sample-only flag and three device addresses (None = null).  8-byte aligned, like the struct."""
     n_public = ctypes.sizeof(_lib.EstimateBonesArgs)
-    assert n_public % 8 == 0 and FPS_TAIL.size == FPS_TAIL_SIZE
+    assert n_public % 8 == 0 and ctypes.sizeof(_lib.EbFpsTail) == FPS_TAIL_SIZE
     public.size = n_public + FPS_TAIL_SIZE
     block = (ctypes.c_uint64 * ((n_public + FPS_TAIL_SIZE) // 8))()
     ctypes.memmove(block, ctypes.addressof(public), n_public)
-    FPS_TAIL.pack_into(block, n_public, int(k), int(bool(sample_only)), start or 0, sampled or 0, idx or 0)
+    tail = _lib.EbFpsTail.from_buffer(block, n_public)
+    tail.k, tail.sample_only, tail.start, tail.sampled, tail.idx = int(k), int(bool(sample_only)), start, sampled, idx
     return block
 
 
@@ -1317,7 +1313,7 @@ def _interpolate_da_torch(attr, rast, tri, rast_db, diff_attrs="all"):
 
 
 # ---------------------------------------------------------------------------------------------- fused G-buffer
-GBUFFER_GRAD_COLS = 16  # A3D_GBUFFER_GRAD_COLS of include/a3d.h
+GBUFFER_GRAD_COLS = _lib.GBUFFER_GRAD_COLS
 
 
 def _round_up(n, m):
@@ -2474,7 +2470,7 @@ def field_head_bwd(g_out, s, h, weight, scale=None, act=0):
 # ---------------------------------------------------------------------------------------------- texture sampling
 _TEX_FILTERS = {"nearest": 0, "linear": 1, "linear-mipmap-nearest": 2, "linear-mipmap-linear": 3}
 _TEX_BOUNDARIES = {"wrap": 0, "clamp": 1, "zero": 2, "cube": 3}
-TEX_MAX_LEVELS = 16  # A3D_TEX_MAX_LEVELS of include/a3d.h
+TEX_MAX_LEVELS = _lib.TEX_MAX_LEVELS
 
 
 def texture_filter_mode(filter_mode, uv_da=None, mip_level_bias=None):

@@ -62,23 +62,12 @@ def test_shortfall_of_a_greedy_run_is_zero_and_of_a_wrong_pick_is_not():
     assert R.pick_shortfall(pts, picks)[40] == 1.0
 
 
-# ---- the tail: ops.py's packing against csrc/eb_common.h, read the way abi_check reads the public headers
-def tail_fields():
-    path = os.path.join(os.path.dirname(A.INCLUDE), "3danimals_amd", "csrc", "eb_common.h")
-    code = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S))
-    (body,) = re.findall(r"typedef struct a3d_eb_fps_tail \{(.*?)\} a3d_eb_fps_tail;", code, flags=re.S)
-    fields = []
-    for decl in (re.sub(r"\s+", " ", d.strip()) for d in body.split(";") if d.strip()):
-        base, star, name = re.match(r"(?:const )?(\w+) ?(\*?) ?(\w+)$", decl).groups()
-        fields.append((name, ctypes.c_void_p if star else A._FIELD_TYPES[base]))
-    return fields
-
-
+# ---- the tail: ops.py's packing against csrc/eb_common.h, through the registered mirror (tests/test_abi_cpu.py holds it to the header too)
 def test_tail_packing_matches_the_c_definition():
-    fields = tail_fields()
-    mirror = type("Tail", (ctypes.Structure,), {"_fields_": fields})
-    assert tuple(n for n, _ in fields) == ops.FPS_TAIL_FIELDS
-    assert ctypes.sizeof(mirror) == ops.FPS_TAIL.size == ops.FPS_TAIL_SIZE == MACROS["A3D_FPS_TAIL_SIZE"]
+    fields = A.struct_fields("a3d_eb_fps_tail")
+    mirror = type("Tail", (ctypes.Structure,), {"_fields_": fields})  # (built from the header: the packed block is read back with it)
+    assert fields == L.EbFpsTail._fields_
+    assert ctypes.sizeof(mirror) == ctypes.sizeof(L.EbFpsTail) == ops.FPS_TAIL_SIZE == MACROS["A3D_FPS_TAIL_SIZE"]
     assert MACROS["A3D_FPS_MAX_V"] == ops.FPS_MAX_V >= 131072 and MACROS["A3D_FPS_REG_MAX_V"] == ops.FPS_REG_MAX_V
     # the header's byte table
     text = open(os.path.join(A.INCLUDE, "a3d.h")).read()
