@@ -18,9 +18,12 @@ DESIGN.md "What is not a HIP kernel"): split-K weight gradients (``_LinearSplitK
 (``CoordMLP._fused_input``), the output stage Linear(256 -> C <= 16) [+ sigmoid] [+ min_max] and its adjoint as one HIP pass over the
 hidden vectors each way (``_FieldStackHead``, csrc/fieldhead.hip), and the frequency table kept on the device.  Short lists take the plain
 torch path, except the one that needs double backward: points that require grad through the 256-wide SDF field (the eikonal regulariser)
-take hand-written value / gradient / adjoint chains (``_field_value``, ``USE_FIELD_GRAD``).
+take hand-written value / gradient / adjoint chains (``_field_value``, ``USE_FIELD_GRAD``).  The weight-modulated
+field (``CoordMLP_Mod``) takes the same routes with its effective weights when ``USE_FIELD_MOD`` is on.
 """
 from __future__ import annotations
+
+import os
 
 import torch
 import torch.nn as nn
@@ -554,18 +557,14 @@ class CoordMLP(nn.Module):
         from . import ops
 
         h = ops.harmonic_embed(x, self.embedder._frequencies(x.device), symmetrize=self.symmetrize, ones=True)
-        weight = torch.cat([self.in_layer.weight, self.in_layer.bias[:, None]], dim=1)
-        return linear_relu(h, weight, None)
+        return linear_relu(h, self._w_in(), None)
 
     def _field_grad_ok(self, x):
         """A short list of points that REQUIRE GRAD through a scalar field of the standard shape (the SDF under the eikonal regulariser):
         embedding + concatenated points (an even number of frequencies: K = 4 + 6n is then a multiple of 4), a biased in_layer of 256
         outputs, bias-free 256 x 256 Linear/ReLU pairs, one bias-free Linear(256 -> 1); nothing else behind it.  Everything else -- the
         grad-free grid pass, points that do not require grad, narrow nets, features -- keeps its path."""
-        if not (USE_FIELD_GRAD and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == 3 and 1 <= x.shape[0] < SPLITK_MIN_ROWS
-                and x.requires_grad and torch.is_grad_enabled() and self.embedder is not None and self.embed_concat_pts
-                and len(self.embedder.frequencies) % 2 == 0 and self.in_layer.bias is not None and self.in_layer.weight.shape[0] == 256
-                and self.in_layer.weight.dtype == torch.float32 and self.min_max is None and self.extra_feat_dim == 0):
+        if not self._field_grad_input_ok(x):
             return False
         layers = list(self.mlp.network)
         if len(layers) < 3 or len(layers) % 2 == 0:
@@ -578,16 +577,22 @@ class CoordMLP(nn.Module):
         head = layers[-1]
         return isinstance(head, nn.Linear) and head.bias is None and tuple(head.weight.shape) == (1, 256) and head.weight.dtype == torch.float32
 
+    def _field_grad_input_ok(self, x):
+        """_field_grad_ok without the walk over self.mlp's layers: the point list, the embedding and the in_layer (shared with CoordMLP_Mod,
+        whose layers are effective weights rather than modules)."""
+        return (USE_FIELD_GRAD and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == 3 and 1 <= x.shape[0] < SPLITK_MIN_ROWS
+                and x.requires_grad and torch.is_grad_enabled() and self.embedder is not None and self.embed_concat_pts
+                and len(self.embedder.frequencies) % 2 == 0 and self.in_layer.bias is not None and self.in_layer.weight.shape[0] == 256
+                and self.in_layer.weight.dtype == torch.float32 and self.min_max is None and self.extra_feat_dim == 0)
+
     def _field_grad(self, x):
-        w_in = torch.cat([self.in_layer.weight, self.in_layer.bias[:, None]], dim=1)
         layers = list(self.mlp.network)
-        return _field_value(x, w_in, layers[-1].weight, self.embedder._frequencies(x.device), bool(self.symmetrize),
+        return _field_value(x, self._w_in(), layers[-1].weight, self.embedder._frequencies(x.device), bool(self.symmetrize),
                             *[l.weight for l in layers[:-1:2]])
 
     def _stack_ok(self, x, with_feat):
         """The whole hidden stack as one autograd node (_FieldStack): long list, training, 256-wide bias-free Linear/ReLU pairs."""
-        if not (USE_FIELD_STACK and self._fused_input_ok(x) and torch.is_grad_enabled() and x.shape[0] % SPLITK_PARTS == 0
-                and self.in_layer.weight.requires_grad and self.in_layer.weight.shape[0] == 256):
+        if not self._stack_input_ok(x):
             return False
         layers = list(self.mlp.network)
         n_pairs = 0
@@ -599,17 +604,25 @@ class CoordMLP(nn.Module):
             n_pairs += 1
         return n_pairs >= 1
 
+    def _stack_input_ok(self, x):
+        """_stack_ok without the walk over self.mlp's layers (shared with CoordMLP_Mod)."""
+        return bool(USE_FIELD_STACK and self._fused_input_ok(x) and torch.is_grad_enabled() and x.shape[0] % SPLITK_PARTS == 0
+                    and self.in_layer.weight.requires_grad and self.in_layer.weight.shape[0] == 256)
+
     def _fused_head(self, tail):
         """(weight, lo, scale, act) when ``tail`` -- the layers behind the stack's Linear/ReLU pairs -- is exactly one bias-free
         Linear(256 -> C <= 16), optionally followed by a Sigmoid, with an optional min_max: the output stage _FieldStackHead fuses.
         None for everything else (tanh, dropout, a biased head ...), which keeps the layer-by-layer tail of _stacked.  Reached only
         from _stacked, that is behind _stack_ok: long lists with grad enabled -- never the SDF's grad-free grid pass or a short list."""
-        if not USE_FIELD_HEAD or not 1 <= len(tail) <= 2 or not isinstance(tail[0], nn.Linear) or tail[0].bias is not None:
-            return None
-        weight = tail[0].weight
-        if weight.shape[1] != 256 or not 1 <= weight.shape[0] <= 16 or weight.dtype != torch.float32:
+        if not 1 <= len(tail) <= 2 or not isinstance(tail[0], nn.Linear) or tail[0].bias is not None:
             return None
         if len(tail) == 2 and not isinstance(tail[1], nn.Sigmoid):
+            return None
+        return self._fused_head_of(tail[0].weight, len(tail) - 1)
+
+    def _fused_head_of(self, weight, act):
+        """_fused_head for a bias-free head given by its weight [C,256] (shared with CoordMLP_Mod)."""
+        if not USE_FIELD_HEAD or weight.shape[1] != 256 or not 1 <= weight.shape[0] <= 16 or weight.dtype != torch.float32:
             return None
         lo = scale = None
         if self.min_max is not None:
@@ -617,27 +630,37 @@ class CoordMLP(nn.Module):
                 return None
             lo = self.min_max[:, 0].contiguous()
             scale = self.min_max[:, 1] - self.min_max[:, 0]
-        return weight, lo, scale, len(tail) - 1
+        return weight, lo, scale, act
 
-    def _stacked(self, x, feat, feat_index):
+    def _w_in(self):
+        """The in_layer's weight with its bias as the column that multiplies the embedding's ones."""
+        return torch.cat([self.in_layer.weight, self.in_layer.bias[:, None]], dim=1)
+
+    def _stack_node(self, x, per_image, index, w_first, hidden, head):
+        """The stack node over the fused input stage for the 256 x 256 weights ``hidden``: with the output stage ``head`` (what _fused_head /
+        _fused_head_of returned) in it, or without (None: the caller runs the tail).  Shared with CoordMLP_Mod, whose weights are tensors."""
         from . import ops
 
+        x_emb = ops.harmonic_embed(x, self.embedder._frequencies(x.device), symmetrize=self.symmetrize, ones=True)
+        if head is not None:
+            return _FieldStackHead.apply(x_emb, self._w_in(), per_image, index, w_first, *head, *hidden)
+        return _FieldStack.apply(x_emb, self._w_in(), per_image, index, w_first, *hidden)
+
+    def _stacked(self, x, feat, feat_index):
         layers = list(self.mlp.network)
         pairs, i = [], 0
         while i + 1 < len(layers) and isinstance(layers[i], nn.Linear) and isinstance(layers[i + 1], nn.ReLU):
             pairs.append(layers[i])
             i += 2
-        x_emb = ops.harmonic_embed(x, self.embedder._frequencies(x.device), symmetrize=self.symmetrize, ones=True)
-        w_in = torch.cat([self.in_layer.weight, self.in_layer.bias[:, None]], dim=1)
         per_image = w_first = None
         if feat is not None:
             first, pairs = pairs[0].weight, pairs[1:]
             per_image = F.linear(torch.relu(feat), first[:, 256:])  # [B, 256]
             w_first = first[:, :256].contiguous()
         head = self._fused_head(layers[i:])
+        h = self._stack_node(x, per_image, feat_index if feat is not None else None, w_first, [l.weight for l in pairs], head)
         if head is not None:
-            return _FieldStackHead.apply(x_emb, w_in, per_image, feat_index if feat is not None else None, w_first, *head, *[l.weight for l in pairs])
-        h = _FieldStack.apply(x_emb, w_in, per_image, feat_index if feat is not None else None, w_first, *[l.weight for l in pairs])
+            return h
         for layer in layers[i:]:
             h = linear(h, layer.weight, layer.bias) if isinstance(layer, nn.Linear) else layer(h)
         if self.min_max is not None:
@@ -673,7 +696,14 @@ class CoordMLP(nn.Module):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # Weight-modulated field of the pan-category model (Fauna): same classes and state_dict layout as the reference's
 # CoordMLP_Mod / MLP_Mod / Linear_Mod (networks/MLPs.py:104-247).  One 128-d embedding per batch modulates and demodulates every
-# layer's weight (StyleGAN2 style); plain torch.
+# layer's weight (StyleGAN2 style); plain torch, unless USE_FIELD_MOD is on.
+#
+# A Linear_Mod is a bias-free Linear whose weight is a function of the style, so with the effective weights W'_l in hand the field is the
+# Linear/ReLU stack CoordMLP's routes are made for (linear_relu, _FieldStack / _FieldStackHead, _field_value).  OFF
+# unless A3D_FIELD_MOD=1: switching a route on by default changes recorded behaviour.
+USE_FIELD_MOD = os.environ.get("A3D_FIELD_MOD", "0") not in ("0", "")
+
+
 class Linear_Mod(nn.Module):
     def __init__(self, in_features, out_features, bias=True):
         super().__init__()
@@ -689,12 +719,16 @@ class Linear_Mod(nn.Module):
             bound = 1 / fan_in ** 0.5 if fan_in > 0 else 0
             nn.init.uniform_(self.bias, -bound, bound)
 
-    def forward(self, x, style):
+    def effective_weight(self, style):
+        """W'[o,i] = W[o,i] s[i] / sqrt(sum_j (W[o,j] s[j])^2 + 1e-5): the weight forward multiplies with, the reference's three statements
+        (MLPs.py:234-240) in their order.  Differentiable with respect to the weight and the style."""
         if style.dim() > 1:  # one style per batch: the first row (MLPs.py:233-235)
             style = style.reshape(-1, style.shape[-1])[0]
         weight = self.weight * style.unsqueeze(0)
-        weight = weight / ((weight * weight).sum(dim=-1, keepdim=True) + 1e-5).sqrt()
-        return F.linear(x, weight, self.bias)
+        return weight / ((weight * weight).sum(dim=-1, keepdim=True) + 1e-5).sqrt()
+
+    def forward(self, x, style):
+        return F.linear(x, self.effective_weight(style), self.bias)
 
 
 class MLP_Mod(nn.Module):
@@ -708,6 +742,13 @@ class MLP_Mod(nn.Module):
             self.relu = nn.ReLU(inplace=True)
             for i in range(num_layers):
                 setattr(self, f"linear_{i}", Linear_Mod(cin if i == 0 else nf, cout if i == num_layers - 1 else nf, bias=False))
+
+    def layers(self):
+        return [self.network] if self.num_layers == 1 else [getattr(self, f"linear_{i}") for i in range(self.num_layers)]
+
+    def effective_weights(self, style):
+        """[W'_0 .. W'_(L-1)]: every layer's modulated and demodulated weight for one style, bit for bit what Linear_Mod.forward builds."""
+        return [layer.effective_weight(style) for layer in self.layers()]
 
     def forward(self, x, style):
         if self.num_layers == 1:
@@ -735,6 +776,7 @@ class CoordMLP_Mod(nn.Module):
         self.relu = nn.ReLU(inplace=True)
         self.mlp = MLP_Mod(nf, cout, num_layers, nf, dropout, activation)
         self.style_mlp = MLP(condition_dim, nf, 2, nf, dropout, None)
+        self.dropout = dropout
         self.symmetrize = symmetrize
         if min_max is not None:
             self.register_buffer("min_max", min_max)
@@ -742,8 +784,62 @@ class CoordMLP_Mod(nn.Module):
             self.min_max = None
         self.bsdf = None
 
+    # the halves of CoordMLP's gates that look at the point list, the embedding and the in_layer -- the same functions, not copies
+    _fused_input_ok = CoordMLP._fused_input_ok
+    _fused_input = CoordMLP._fused_input
+    _stack_input_ok = CoordMLP._stack_input_ok
+    _field_grad_input_ok = CoordMLP._field_grad_input_ok
+    _fused_head_of = CoordMLP._fused_head_of
+    _w_in = CoordMLP._w_in
+    _stack_node = CoordMLP._stack_node
+
+    def _field_mod_ok(self, x, feat):
+        """USE_FIELD_MOD's gate: a float32 point list [M,3] on the GPU, the standard input stage (embedding with concatenated points, an
+        even number of frequencies), width 256, at least one hidden layer, no dropout, one float32 style of condition_dim columns.
+        Everything else -- narrow nets, no embedder, CPU, float64, inputs an autocast region cast -- takes the plain torch code."""
+        if not (USE_FIELD_MOD and not REFERENCE_FORMULATION and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
+                and x.shape[1] == 3 and x.shape[0] >= 1 and not torch.is_autocast_enabled()
+                and self.embedder is not None and self.embed_concat_pts and len(self.embedder.frequencies) % 2 == 0
+                and self.in_layer.bias is not None and self.in_layer.weight.dtype == torch.float32 and self.in_layer.weight.shape[0] == 256
+                and self.mlp.num_layers >= 2 and not getattr(self, "dropout", 0)
+                and feat.is_cuda and feat.dtype == torch.float32 and feat.shape[-1] == self.condition_dim):
+            return False
+        layers = self.mlp.layers()
+        return (all(tuple(l.weight.shape) == (256, 256) for l in layers[:-1]) and layers[-1].weight.shape[1] == 256
+                and all(l.weight.dtype == torch.float32 and l.bias is None for l in layers))
+
+    def _forward_field(self, x, feat):
+        """The field with its effective weights W'_l (MLP_Mod.effective_weights, once per call) on CoordMLP's routes: a bias-free Linear/ReLU
+        stack of width 256 behind the fused input stage.  The kernels return gradients with respect to W'_l; autograd carries them through
+        the modulation statements to the weights, the style network and the embedding.  Inherited limits: the stack nodes are once
+        differentiable, and _field_value gives no second-order gradient with respect to the points."""
+        *hidden, w_head = self.mlp.effective_weights(self.style_mlp(feat))
+        if self._stack_input_ok(x):  # a long list with grad enabled
+            head = self._fused_head_of(w_head, 0)
+            out = self._stack_node(x, None, None, None, hidden, head)
+            if head is not None:
+                return out
+            out = linear(out, w_head)
+        elif self._field_grad_input_ok(x) and tuple(w_head.shape) == (1, 256):  # the eikonal call: a short list that requires grad
+            return _field_value(x, self._w_in(), w_head, self.embedder._frequencies(x.device), bool(self.symmetrize), *hidden)
+        else:  # grad disabled (the grid pass), or nothing that needs the hand-written backward: ReLU in the epilogue where the list is long
+            if self._fused_input_ok(x):
+                h = self._fused_input(x)
+            else:
+                if self.symmetrize:
+                    x = torch.cat([x[..., :1].abs(), x[..., 1:]], -1)
+                h = linear_relu(torch.cat([x, self.embedder(x)], -1), self.in_layer.weight, self.in_layer.bias)
+            for w in hidden:
+                h = linear_relu(h, w)
+            out = linear(h, w_head)
+        if self.min_max is not None:
+            out = out * (self.min_max[:, 1] - self.min_max[:, 0]) + self.min_max[:, 0]
+        return out
+
     def forward(self, x, feat=None):
         assert feat is not None and feat.shape[-1] == self.condition_dim
+        if self._field_mod_ok(x, feat):
+            return self._forward_field(x, feat)
         if self.symmetrize:
             x = torch.cat([x[..., :1].abs(), x[..., 1:]], -1)
         x_in = x
